@@ -7,6 +7,7 @@ rank 0 when N > 1).  The index (3.1 G symbols incl. 24 sentinels, u32, sampling 
 is built on the GPU before the timed region and is not timed.
 
     python bench.py --gpus N --steps K --warmup W [--workload hg38|mixed|cfg2|small] [--op count+locate|count]
+                    [--dump-outputs DIR]
 
 For N > 1 launch one rank per GPU with torch.distributed.run; the index is replicated and results are gathered to rank 0
 over RCCL.  The run first gives every rank its own batch of nq queries (`weak_scaling`), then shards ONE batch of nq
@@ -49,6 +50,7 @@ from benchlib.baseline import *  # noqa: E402,F401,F403
 from benchlib.multi import *  # noqa: E402,F401,F403
 from benchlib.end_to_end import *  # noqa: E402,F401,F403
 from benchlib.secondaries import *  # noqa: E402,F401,F403
+from benchlib.dump import *  # noqa: E402,F401,F403
 
 
 def parse_args():
@@ -114,7 +116,13 @@ def parse_args():
     ap.add_argument("--side-file", default=os.environ.get("GDX_BENCH_SIDE_FILE", os.path.join("gpurun_out", "bench_secondary.json")),
                     help="where everything beside the contract line goes (secondaries, ladder, end-to-end, bandwidths, notes): "
                          "the one stdout line stays below 4 KB")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (counts, status, hit offsets and hits of a "
+                         "fixed sample of the queries and of the hits; rank 0's own batch at N > 1) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     explicit = (args.jump_bytes is not None or args.top_depth is not None or args.no_pair_lines or args.full_sa or args.text_units)
     if explicit:  # hand-picked structures (ladder rungs of the PMC children, experiments)
         args.index = "tables"
@@ -251,10 +259,12 @@ def main():
     gather, count_of, gathered_bytes = None, None, 0
     if world > 1:
         gather, count_of, gathered_bytes = make_gather(torch, gdist, runner, dev, do_locate)
-    elapsed, _ = timed_steps(torch, gdist, runner, args.steps, args.warmup, dev, gather, count_of,
-                             overlap=do_locate and args.overlap)
+    elapsed, last_slot = timed_steps(torch, gdist, runner, args.steps, args.warmup, dev, gather, count_of,
+                                     overlap=do_locate and args.overlap)
     runner.check_totals()
     narrow_offsets = runner.widen_offsets()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(np, torch, runner, last_slot, args.dump_outputs)
     ms_per_step = elapsed / args.steps * 1e3
     value = nq * world / (ms_per_step / 1e3)
     search_ms = runner.mean_ms(runner.ev_search)

@@ -416,3 +416,51 @@ def test_committed_round6_line_is_what_the_driver_can_read():
     assert g["aux_structures"]["default_shape"] is True and g["oracle_gate"]["hits_identical"] is True
     assert side["config"]["aux_structures"]["default_shape"] is True
     assert side["end_to_end"]["fastq_to_hits"]["hits_identical_to_device_path"] is True
+
+
+def test_dump_outputs_is_a_fixed_sample_of_the_last_step(tmp_path):
+    """--dump-outputs on CPU tensors: float32 / float64 files under the 64 MB limit, a sample that is the same from run to run,
+    and values that are the step's own (counts, status, hit offsets, hits; positions above 2^31 read as unsigned)."""
+    import numpy as np
+    import torch
+
+    rng = np.random.default_rng(7)
+    nq = 3 * bench.DUMP_SAMPLE
+    counts = rng.choice([0, 1, 2], size=nq, p=[0.2, 0.7, 0.1]).astype(np.int32)
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    total = int(off[-1])
+    hits = np.stack([rng.integers(0, 24, total), rng.integers(0, 1 << 32, total)], axis=1).astype(np.int64)
+    status = (rng.random(nq) < 0.01).astype(np.uint8)
+
+    class Runner:
+        pass
+
+    r = Runner()
+    r.nq, r.do_locate, r.total_hits = nq, True, total
+    # slot 1 is the last step's; slot 0 holds another batch's results, which must not be what is written
+    r.outs = [{"status": torch.zeros(nq, dtype=torch.uint8), "hit_offsets": torch.zeros(nq + 1, dtype=torch.int64)},
+              {"status": torch.from_numpy(status), "hit_offsets": torch.from_numpy(off)}]
+    r.hits = [torch.zeros((total + 5, 2), dtype=torch.int32), torch.from_numpy(np.concatenate([hits, np.zeros((5, 2), np.int64)]).astype(np.int32))]
+    r.counts = lambda o: torch.from_numpy(counts) if o is r.outs[1] else torch.zeros(nq, dtype=torch.int32)
+    r.status = lambda o: o["status"]
+    shapes = bench.dump_outputs(np, torch, r, 1, str(tmp_path / "a"))
+    bench.dump_outputs(np, torch, r, 1, str(tmp_path / "b"))
+    names = {"query_index", "counts", "status", "hit_offsets", "hit_index", "hit_text_id", "hit_position", "totals"}
+    assert set(shapes) == names and sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in names)
+    d = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in names) <= bench.DUMP_LIMIT_BYTES
+    for n in names:
+        assert np.array_equal(d[n], np.load(tmp_path / "b" / (n + ".npy")))
+    qi, hi = d["query_index"].astype(np.int64), d["hit_index"].astype(np.int64)
+    assert qi.size == bench.DUMP_SAMPLE and np.all(np.diff(qi) > 0) and qi[-1] < nq
+    assert hi.size == bench.DUMP_SAMPLE and np.all(np.diff(hi) > 0) and hi[-1] < total
+    assert np.array_equal(d["counts"], counts[qi]) and np.array_equal(d["status"], status[qi])
+    assert np.array_equal(d["hit_offsets"], off[qi])
+    assert np.array_equal(d["hit_text_id"], hits[hi, 0]) and np.array_equal(d["hit_position"], hits[hi, 1])
+    assert d["totals"].tolist() == [nq, total]
+    # count only: no hits; a batch below the sample size is written whole
+    r.do_locate, r.nq, r.total_hits = False, 1000, int(counts[:1000].sum())
+    shapes = bench.dump_outputs(np, torch, r, 1, str(tmp_path / "c"))
+    assert set(shapes) == {"query_index", "counts", "status", "totals"} and shapes["counts"] == (1000,)
+    assert np.array_equal(np.load(tmp_path / "c" / "counts.npy"), counts[:1000])
