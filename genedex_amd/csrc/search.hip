@@ -1114,6 +1114,14 @@ constexpr uint32_t kStatePacked = 1u << 23, kStatePlain = 1u << 22;
 // entry names such a record (kSeedPairInfo): the read is decided by that one 32-byte record.  3 << 24 / 4 << 24 in the rows' place:
 // the index is that of the k-mer's 64-byte record in IndexView::seed_quads (kSeedQuadInfo)
 constexpr uint32_t kStatePair = 1u << 21;
+// the fields of a packed state's second word: symbols left (bits 0-20), the three flags, rows (bits 24-31, fewer than 256)
+constexpr uint32_t kStateSymbolsMask = 0x1fffffu, kStateRowsShift = 24, kStateRowsMask = 0xffu << kStateRowsShift;
+static_assert((kStatePacked & kStatePlain) == 0u && (kStatePacked & kStatePair) == 0u && (kStatePlain & kStatePair) == 0u,
+              "state flags overlap");
+static_assert(((kStatePacked | kStatePlain | kStatePair) & kStateSymbolsMask) == 0u, "a state flag overlaps the symbols left");
+static_assert(((kStatePacked | kStatePlain | kStatePair) & kStateRowsMask) == 0u, "a state flag overlaps the rows");
+static_assert((kStateSymbolsMask & kStateRowsMask) == 0u && kStateRowsShift + 8u == 32u, "the symbols left overlap the rows, or rows < 256 do not fill the top byte");
+static_assert(kStateSymbolsMask >= 32u && (kStateSymbolsMask & (kStateSymbolsMask + 1u)) == 0u, "symbols left: a low bit field");
 
 struct FastView {
     const uint2 *top;
@@ -1280,7 +1288,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
             uint4 resume = make_uint4(0u, 0u, 0u, 0u);
             if (list != nullptr && state != nullptr) resume = state[q];
             // (a read that is finished from its packed state never asks where its bytes are)
-            const bool from_state = state_packed != 0u && (resume.y & kStatePacked) != 0u && (resume.y & 0x1fffffu) <= 32u;
+            const bool from_state = state_packed != 0u && (resume.y & kStatePacked) != 0u && (resume.y & kStateSymbolsMask) <= 32u;
             uint64_t begin = 0, len = 0;
             const uint64_t *wbase = nullptr;
             uint32_t off0 = 0;
@@ -1306,13 +1314,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                 bail = false;
                 lo = resume.x;
                 hi = resume.z;
-                rem = resume.y & 0x1fffffu;
+                rem = resume.y & kStateSymbolsMask;
                 progressed = true;
             } else if (state_packed != 0u && (resume.y & kStatePacked) != 0u) {
                 bail = false;
                 lo = resume.x;
-                hi = lo + (resume.y >> 24);
-                rem = resume.y & 0x1fffffu;
+                hi = lo + (resume.y >> kStateRowsShift);
+                rem = resume.y & kStateSymbolsMask;
                 progressed = true;
                 if (from_state) {
                     // the window from the state: levels 0 | 1 and 2 | 3 (eight symbols each, the first of a level in its top
@@ -2290,7 +2298,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) 
             if (kSeed && state != nullptr) st = state[q];
             // (a read that is finished from its packed state never asks where its bytes are: the seed kernel has checked its length)
             const bool from_state = kSeed && state != nullptr && state_packed != 0u && wide_to_list != 0u && (st.y & kStatePacked) != 0u &&
-                                    (st.y & 0x1fffffu) <= 32u;
+                                    (st.y & kStateSymbolsMask) <= 32u;
             const uint64_t begin = from_state ? 0ull : query_begin(qbeg, ulen, q);
             const uint64_t len = from_state ? 0ull : query_end(qend, ulen, q) - begin;
             bool bail = from_state ? false
@@ -2305,11 +2313,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) 
             uint32_t pos = 0;              // SA of this lane's row
             bool resumed = false;
             const uint64_t state_codes = (static_cast<uint64_t>(st.z) << 32) | st.w;  // from_state: the symbols in front of the seed
-            if (from_state && (st.y & kStatePair) != 0u && (st.y >> 24) > 2u) {
+            if (from_state && (st.y & kStatePair) != 0u && (st.y >> kStateRowsShift) > 2u) {
                 // three or four copies: the same from a 64-byte record, lane `sub` of the group decides row `sub`
                 const u32x4 *qr = vv.seed_quads + 4ull * st.x;
                 const u32x4 q0 = qr[0], q1 = qr[1], q2 = qr[2], q3 = qr[3];
-                const uint32_t n_v = st.y & 0x1fffffu, rows_q = st.y >> 24;
+                const uint32_t n_v = st.y & kStateSymbolsMask, rows_q = st.y >> kStateRowsShift;
                 const uint64_t vm64 = n_v == 32u ? ~0ull : ~0ull << (2u * (32u - n_v));
                 const uint32_t p_me = sel4(sub, q0.x, q0.y, q0.z, q0.w);
                 const uint64_t t_me = (static_cast<uint64_t>(sel4(sub, q1.y, q1.w, q2.y, q2.w)) << 32) | sel4(sub, q1.x, q1.z, q2.x, q2.z);
@@ -2345,7 +2353,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) 
                 // suffix-array line, no text lines; the record's contexts are whole, so the compare is all there is to decide
                 const u32x4 *pr = vv.seed_pairs + 2ull * st.x;
                 const u32x4 r0 = pr[0], r1 = pr[1];
-                const uint32_t n_v = st.y & 0x1fffffu;  // 1 .. 32 symbols in front of the seed
+                const uint32_t n_v = st.y & kStateSymbolsMask;  // 1 .. 32 symbols in front of the seed
                 const uint64_t vm64 = n_v == 32u ? ~0ull : ~0ull << (2u * (32u - n_v));
                 const uint64_t t1 = (static_cast<uint64_t>(r0.w) << 32) | r0.z, t2 = (static_cast<uint64_t>(r1.y) << 32) | r1.x;
                 const bool ok1 = ((state_codes ^ t1) & vm64) == 0ull && r0.x >= n_v, ok2 = ((state_codes ^ t2) & vm64) == 0ull && r0.y >= n_v;
@@ -2364,8 +2372,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) 
             if (from_state) {
                 resumed = true;
                 lo = st.x;
-                hi = lo + (st.y >> 24);
-                rem = st.y & 0x1fffffu;
+                hi = lo + (st.y >> kStateRowsShift);
+                rem = st.y & kStateSymbolsMask;
             } else if (kSeed && !bail && state != nullptr) {
                 // the seed kernel found the k-mer on several rows: {lo, hi, symbols, 1}, or one of the packed forms
                 const bool plain = state_packed == 0u && st.w == 1u;
@@ -2375,8 +2383,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) 
                     rem = static_cast<uint32_t>(len);
                     w = fast_window<kXlate>(vv, s_dense, wbase, off0, rem, sub);
                     lo = st.x;
-                    hi = plain ? st.y : (p_rows ? lo + (st.y >> 24) : st.z);
-                    rem = plain ? st.z : st.y & 0x1fffffu;
+                    hi = plain ? st.y : (p_rows ? lo + (st.y >> kStateRowsShift) : st.z);
+                    rem = plain ? st.z : st.y & kStateSymbolsMask;
                     shift = vv.seed_k >> 3;
                     part = vv.seed_k & 7u;
                 }
@@ -2801,8 +2809,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                             if (!kExact && state) {
                                 if (state_packed == 0u) state[q] = make_uint4(ey, ez, a_rem, 1u);
                                 else if (state_packed == 2u && (ex & (kSeedPairInfo | kSeedQuadInfo)) != 0u && a_rem - 1u < 32u)
-                                    state[q] = make_uint4(ew, ((ez - ey) << 24) | kStatePacked | kStatePair | a_rem, a_qh, a_ql);
-                                else if (ez - ey < 256u) state[q] = make_uint4(ey, ((ez - ey) << 24) | kStatePacked | a_rem, a_qh, a_ql);
+                                    state[q] = make_uint4(ew, ((ez - ey) << kStateRowsShift) | kStatePacked | kStatePair | a_rem, a_qh, a_ql);
+                                else if (ez - ey < 256u) state[q] = make_uint4(ey, ((ez - ey) << kStateRowsShift) | kStatePacked | a_rem, a_qh, a_ql);
                                 else state[q] = make_uint4(ey, kStatePlain | a_rem, ez, 0u);
                             }
                             if (!kExact && out_compact) out_compact[q] = kCompactSee;
@@ -3058,10 +3066,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kXlate =
             if (state) {
                 if (state_packed == 0u) state[q] = make_uint4(ey, ez, rem, 1u);
                 else if (state_packed == 2u && (ex & (kSeedPairInfo | kSeedQuadInfo)) != 0u && rem - 1u < 32u)  // (kStatePair: ew = the record's index)
-                    state[q] = make_uint4(ew, ((ez - ey) << 24) | kStatePacked | kStatePair | rem, static_cast<uint32_t>(qcode >> 32),
+                    state[q] = make_uint4(ew, ((ez - ey) << kStateRowsShift) | kStatePacked | kStatePair | rem, static_cast<uint32_t>(qcode >> 32),
                                           static_cast<uint32_t>(qcode));
                 else if (ez - ey < 256u)
-                    state[q] = make_uint4(ey, ((ez - ey) << 24) | kStatePacked | rem, static_cast<uint32_t>(qcode >> 32),
+                    state[q] = make_uint4(ey, ((ez - ey) << kStateRowsShift) | kStatePacked | rem, static_cast<uint32_t>(qcode >> 32),
                                           static_cast<uint32_t>(qcode));
                 else state[q] = make_uint4(ey, kStatePlain | rem, ez, 0u);
             }

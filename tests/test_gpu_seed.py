@@ -782,7 +782,19 @@ def test_reads_from_repeats_of_two_to_four_copies_are_decided_by_their_records(r
     co, _, _ = c.locate_many(qs)
     counts = np.diff(co)
     assert all(int((counts == m).sum()) > 200 for m in (1, 2, 3, 4))
-    check_against_oracle(g, c, qs, texts)
+    want = check_against_oracle(g, c, qs, texts)
+    for compact, fused in ((True, False), (True, True), (True, "search"), (False, True)):
+        off, hits, cnt, stat, _ = device_locate(g, qs, compact, fused=fused)
+        assert off.tolist() == want[0].tolist() and not stat.any()
+        assert hits[:, 0].tolist() == want[1].astype(np.uint32).tolist() and hits[:, 1].tolist() == want[2].astype(np.uint32).tolist()
+        assert cnt.tolist() == counts.astype(np.uint32).tolist()
+        for max_hits in (1, 3):  # reads with more hits than the cap are counted but get no slots
+            off, hits, _, _, _ = device_locate(g, qs, compact, fused=fused, max_hits=max_hits)
+            keep = counts <= max_hits
+            assert off.tolist() == np.concatenate([[0], np.cumsum(np.where(keep, counts, 0))]).astype(np.uint64).tolist()
+            sel = np.repeat(keep, counts.astype(np.int64))
+            assert hits[:, 0].tolist() == want[1][sel].astype(np.uint32).tolist()
+            assert hits[:, 1].tolist() == want[2][sel].astype(np.uint32).tolist()
 
 
 @pytest.mark.parametrize("structures", ["seed+sa", "seed+jump32"])
