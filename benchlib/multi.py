@@ -227,8 +227,9 @@ def gathered_shards(torch, gdist, gather, slot, shard_len, sizes, do_locate):
 
 def strong_scaling(torch, gdist, eng, io_text, lengths, wl, nq_total, do_locate, args, rank, world, dev):
     """BASELINE.json configs[3]: the N = 1 batch (seed 43) split into `world` contiguous shards (dist.shard_range), one
-    per rank, results gathered to rank 0; value = nq_total / max-over-ranks step time.  Rank 0 also runs the whole
-    batch alone once and requires the concatenated shard results to equal it bit for bit."""
+    per rank, results gathered to rank 0; value = nq_total / max-over-ranks step time.  With --full the same step is also
+    timed without the gather, and rank 0 runs the whole batch alone once and requires the concatenated shard results to
+    equal it bit for bit."""
     from genedex_amd.device import DeviceQueries
 
     full = DeviceQueries.synth(io_text, lengths, nq_total, wl["len_min"], wl["len_max"], wl["sampled_ppm"], seed=43)
@@ -252,6 +253,10 @@ def strong_scaling(torch, gdist, eng, io_text, lengths, wl, nq_total, do_locate,
            "kernel_ms_rank0": {"search": runner.mean_ms(runner.ev_search), "locate": runner.mean_ms(runner.ev_locate)},
            "gathered_bytes_per_rank_and_step": nbytes}
     runner.check_totals()
+    if rank == 0:
+        res["gather_wire"] = getattr(gather, "wire_name", "compact" if getattr(gather, "compact_wire", False) else "arrays")
+    if not args.full:  # a plain run: the sharded step with the gather is the headline, and nothing is measured beside it
+        return res
     # the same sharded step with the results LEFT on their GPUs (no gather): what the kernels and launches of N ranks give; the
     # gather above adds what one direction of the links into rank 0 carries
     e_ng, _ = timed_steps(torch, gdist, runner, steps, args.warmup, dev)
@@ -263,7 +268,6 @@ def strong_scaling(torch, gdist, eng, io_text, lengths, wl, nq_total, do_locate,
     if rank == 0:
         shard_len = [gdist.shard_range(nq_total, r, world, root_weight) for r in range(world)]
         cnt_cat, hit_cat = gathered_shards(torch, gdist, gather, last, shard_len, sizes, do_locate)
-        res["gather_wire"] = getattr(gather, "wire_name", "compact" if getattr(gather, "compact_wire", False) else "arrays")
         del gather, runner
         torch.cuda.empty_cache()
         single = StepRunner(torch, eng, input_form(full, eng.index, args, wl), nq_total, do_locate, args.path, hint=not args.no_hint)

@@ -464,3 +464,13 @@ def test_dump_outputs_is_a_fixed_sample_of_the_last_step(tmp_path):
     shapes = bench.dump_outputs(np, torch, r, 1, str(tmp_path / "c"))
     assert set(shapes) == {"query_index", "counts", "status", "totals"} and shapes["counts"] == (1000,)
     assert np.array_equal(np.load(tmp_path / "c" / "counts.npy"), counts[:1000])
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """A plain run measures the headline alone; everything beside it is asked for with --full (the --no-* options still parse)."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse_args()
+    assert args.full is False and (args.steps, args.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-extras", "--no-cpu-baseline", "--secondary-depth", "0"])
+    args = bench.parse_args()
+    assert args.full is True and args.no_extras and args.no_cpu_baseline and args.secondary_depth == 0

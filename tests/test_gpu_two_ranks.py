@@ -21,7 +21,7 @@ def test_bench_two_ranks_on_one_gpu(wire):
     env = dict(os.environ, GDX_BENCH_ONE_GPU="1", GDX_BENCH_BACKEND="gloo", GDX_BENCH_GATHER=wire)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", {"compact": "29547", "arrays": "29549", "bitmap": "29551"}[wire], os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--workload", "small", "--steps", "3", "--no-bandwidth", "--nq", "1000000"]
+           "--workload", "small", "--steps", "3", "--no-bandwidth", "--nq", "1000000", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -76,7 +76,7 @@ def test_bench_two_ranks_over_rccl():
     env.pop("GDX_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29548", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "small",
-           "--steps", "3", "--no-bandwidth", "--nq", "1000000"]
+           "--steps", "3", "--no-bandwidth", "--nq", "1000000", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
@@ -92,3 +92,24 @@ def test_gather_count_dtype_is_one_rccl_maps():
     src = open(os.path.join(ROOT, "benchlib", "multi.py")).read()
     m = re.search(r"count_dtype = (.*)", src)
     assert m and "int16" not in m.group(1) and "uint8" in m.group(1) and "int32" in m.group(1)
+
+
+@pytest.mark.gpu
+def test_bench_two_ranks_plain_run():
+    """Without --full the N > 1 run times the sharded, gathered step (the headline) and nothing beside it: no preflight, no
+    step without the gather, no check of the shards against the one-rank output."""
+    env = dict(os.environ, GDX_BENCH_ONE_GPU="1", GDX_BENCH_BACKEND="gloo")
+    env.pop("GDX_BENCH_GATHER", None)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
+           "127.0.0.1", "--master-port", "29553", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "small",
+           "--steps", "3", "--nq", "1000000"]
+    res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["steps"] == 3 and d["value"] > 0
+    assert d["config"]["queries_total"] == 1_000_000 and d["weak_scaling"]["value"] > 0
+    assert abs(d["value"] - 1_000_000 / (d["ms_per_step"] / 1e3)) < 1e-4 * d["value"]
+    assert "rccl_ranks" not in d["config"] and "results_sharded" not in d and d["cpu_baseline"] is None
+    assert "shards_equal_single_rank_output" not in d["parity"] and "hits_checked" not in d["parity"]
