@@ -132,6 +132,7 @@ pub struct Gathered {
 pub const GDX_OK: c_int = 0;
 pub const GDX_ERR_CAPACITY: c_int = 5;
 pub const GDX_ERR_QUERY_STATUS: c_int = 6;
+pub const GDX_SEGMENTS_LF_ONLY: u32 = 1;
 
 /// gdx_query_layout_t
 #[repr(C)]
@@ -213,6 +214,18 @@ extern "C" {
     pub fn gdx_cursor_locate_many(
         ix: *const gdx_index_t, start: *const u64, end: *const u64, m: u64, out_hit_offsets: *mut u64,
         hits: *mut Hit, hits_capacity: u64, out_total: *mut u64,
+    ) -> c_int;
+    /// per query its longest matching suffix segments, rightmost first (include/gdx.h "greedy suffix segments");
+    /// flags: 0 or GDX_SEGMENTS_LF_ONLY
+    pub fn gdx_suffix_segments_many(
+        ix: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, max_segments: u32, flags: u32,
+        out_n_segments: *mut u32, out_remaining: *mut u32, out_length: *mut u32, out_start: *mut u64, out_end: *mut u64,
+        out_status: *mut u8,
+    ) -> c_int;
+    pub fn gdx_suffix_segments_many_dev(
+        ix: *const gdx_index_t, d_qbuf: *const c_void, d_qoff: *const c_void, nq: u64, max_segments: u32, flags: u32,
+        d_n_segments: *mut c_void, d_remaining: *mut c_void, d_length: *mut c_void, d_start: *mut c_void,
+        d_end: *mut c_void, d_status: *mut c_void, stream: *mut c_void,
     ) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
@@ -568,6 +581,37 @@ impl GpuFmIndex {
             c.start = start;
             c.end = end;
         }
+    }
+
+    /// Per query its longest matching suffix segments, rightmost first, as (query_end, length, cursor):
+    /// query[query_end - length .. query_end] is the longest suffix of query[..query_end] that occurs; a segment of
+    /// length 0 stands for one symbol that occurs nowhere (its cursor is empty).  At most `max_segments` per query.
+    pub fn suffix_segments_many<'a, Q: AsRef<[u8]>>(
+        &'a self, queries: impl IntoIterator<Item = Q>, max_segments: u32,
+    ) -> Vec<Vec<(usize, usize, GpuCursor<'a>)>> {
+        let (buf, off) = pack(queries);
+        let nq = off.len() - 1;
+        let slots = nq * max_segments as usize;
+        let (mut n_seg, mut remaining, mut length) = (vec![0u32; nq], vec![0u32; nq], vec![0u32; slots]);
+        let (mut s, mut e) = (vec![0u64; slots], vec![0u64; slots]);
+        check(unsafe {
+            gdx_suffix_segments_many(self.raw, buf.as_ptr(), off.as_ptr(), nq as u64, max_segments, 0, n_seg.as_mut_ptr(),
+                                     remaining.as_mut_ptr(), length.as_mut_ptr(), s.as_mut_ptr(), e.as_mut_ptr(),
+                                     std::ptr::null_mut())
+        });
+        (0..nq)
+            .map(|i| {
+                let mut end_at = (off[i + 1] - off[i]) as usize;
+                (0..n_seg[i] as usize)
+                    .map(|j| {
+                        let k = i * max_segments as usize + j;
+                        let seg = (end_at, length[k] as usize, GpuCursor { index: self, start: s[k], end: e[k] });
+                        end_at -= std::cmp::max(length[k] as usize, 1);
+                        seg
+                    })
+                    .collect()
+            })
+            .collect()
     }
 }
 

@@ -27,6 +27,7 @@ GDX_ERR_CAPACITY = 5
 GDX_ERR_QUERY_STATUS = 6
 GDX_ERR_UNSUPPORTED = 7
 
+GDX_SEGMENTS_LF_ONLY = 1  # flags of gdx_suffix_segments_many[_dev]
 GDX_Q_OK = 0
 GDX_Q_INVALID_SYMBOL = 1
 GDX_Q_UNSEARCHABLE_IN_LOOKUP = 2
@@ -218,6 +219,8 @@ SIGNATURES = {
     "gdx_cursor_extend_front_strings_dev": [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp],
     "gdx_cursor_extend_front_chunk_dev": [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp],
     "gdx_cursor_extend_front_strings": [vp, u64p, u64p, u8p, u64p, C.c_uint64, u8p],
+    "gdx_suffix_segments_many": [vp, u8p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u64p, u64p, u8p],
+    "gdx_suffix_segments_many_dev": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp],
     # gdx_bench.h
     "gdx_index_build_stats": [vp, C.POINTER(BuildStats)],
     "gdx_synth_text_dev": [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp],

@@ -1607,6 +1607,39 @@ int gdx_cursor_extend_front_strings(const gdx_index_t *ix, uint64_t *start, uint
     return guarded([&] { return deref(ix).cursor_extend_front_strings(start, end, qbuf, qoff, m, status); });
 }
 
+int gdx_suffix_segments_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint32_t max_segments,
+                             uint32_t flags, uint32_t *out_n_segments, uint32_t *out_remaining, uint32_t *out_length,
+                             uint64_t *out_start, uint64_t *out_end, uint8_t *out_status)
+{
+    return guarded([&] {
+        return deref(ix).suffix_segments_many(qbuf, qoff, nq, max_segments, flags, out_n_segments, out_remaining, out_length,
+                                              out_start, out_end, out_status);
+    });
+}
+
+int gdx_suffix_segments_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq, uint32_t max_segments,
+                                 uint32_t flags, void *d_n_segments, void *d_remaining, void *d_length, void *d_start, void *d_end,
+                                 void *d_status, void *stream)
+{
+    return guarded([&] {
+        const gdx::FmIndex &f = deref(ix);
+        if (max_segments == 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "max_segments must be at least 1");
+        if ((flags & ~static_cast<uint32_t>(GDX_SEGMENTS_LF_ONLY)) != 0u) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "unknown bit in flags");
+        if (nq == 0) return (int)GDX_OK;
+        if ((reinterpret_cast<uintptr_t>(d_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf must be 8-byte aligned");
+        if (!d_qbuf || !d_qoff || !d_n_segments || !d_remaining || !d_length || !d_start || !d_end)
+            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+        DeviceGuard guard(f.config().device_id);
+        gdx::launch_suffix_segments(f.view(), static_cast<const uint8_t *>(d_qbuf), static_cast<const uint64_t *>(d_qoff), nq,
+                                    max_segments, (flags & GDX_SEGMENTS_LF_ONLY) != 0u, static_cast<uint32_t *>(d_n_segments),
+                                    static_cast<uint32_t *>(d_remaining), static_cast<uint32_t *>(d_length),
+                                    static_cast<uint32_t *>(d_start), static_cast<uint32_t *>(d_end),
+                                    static_cast<uint8_t *>(d_status), as_stream(stream), f.query_options());
+        GDX_HIP(hipGetLastError());
+        return (int)GDX_OK;
+    });
+}
+
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {

@@ -2137,6 +2137,38 @@ int FmIndex::cursor_locate_many(const uint64_t *start, const uint64_t *end, uint
     return rc;
 }
 
+int FmIndex::suffix_segments_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint32_t max_segments,
+                                  uint32_t flags, uint32_t *out_n_segments, uint32_t *out_remaining, uint32_t *out_length,
+                                  uint64_t *out_start, uint64_t *out_end, uint8_t *out_status) const
+{
+    if (max_segments == 0) fail(GDX_ERR_INVALID_ARGUMENT, "max_segments must be at least 1");
+    if ((flags & ~static_cast<uint32_t>(GDX_SEGMENTS_LF_ONLY)) != 0u) fail(GDX_ERR_INVALID_ARGUMENT, "unknown bit in flags");
+    check_queries(qbuf, qoff, nq);
+    if (nq == 0) return GDX_OK;
+    if (!out_n_segments || !out_remaining || !out_length || !out_start || !out_end) fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+    for (uint64_t i = 0; i < nq; i++)
+        if (qoff[i + 1] - qoff[i] > 0xffffffffull)
+            fail(GDX_ERR_INVALID_ARGUMENT, "query %llu is longer than 2^32 - 1 symbols", (unsigned long long)i);
+    make_current();
+    hipStream_t stream = hipStreamPerThread;
+    DeviceQueries dq(qbuf, qoff, nq, stream);
+    const uint64_t slots = nq * max_segments;
+    DeviceBuffer<uint32_t> d_n(nq), d_rem(nq), d_len(slots), d_start(slots), d_end(slots);
+    DeviceBuffer<uint8_t> d_status(nq);
+    launch_suffix_segments(view_, dq.qbuf.get(), dq.qoff.get(), nq, max_segments, (flags & GDX_SEGMENTS_LF_ONLY) != 0u, d_n.get(),
+                           d_rem.get(), d_len.get(), d_start.get(), d_end.get(), d_status.get(), stream, query_options());
+    GDX_HIP(hipGetLastError());
+    GDX_HIP(hipMemcpyAsync(out_n_segments, d_n.get(), nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_remaining, d_rem.get(), nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_length, d_len.get(), slots * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    download_widened(d_start.get(), out_start, slots, stream);
+    download_widened(d_end.get(), out_end, slots, stream);
+    std::vector<uint8_t> st(nq);
+    GDX_HIP(hipMemcpy(st.data(), d_status.get(), nq, hipMemcpyDeviceToHost));
+    if (out_status) std::memcpy(out_status, st.data(), nq);
+    return any_status(st.data(), nq);
+}
+
 int FmIndex::rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const
 {
     if (m == 0) return GDX_OK;

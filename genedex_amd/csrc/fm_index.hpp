@@ -125,6 +125,10 @@ public:
                                     uint8_t *status) const;
     int cursor_locate_many(const uint64_t *start, const uint64_t *end, uint64_t m, uint64_t *out_hit_offsets,
                            gdx_hit_t *hits, uint64_t hits_capacity, uint64_t *out_total) const;
+    // gdx_suffix_segments_many: the whole batch staged (copy in, one launch, copy out)
+    int suffix_segments_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint32_t max_segments, uint32_t flags,
+                             uint32_t *out_n_segments, uint32_t *out_remaining, uint32_t *out_length, uint64_t *out_start,
+                             uint64_t *out_end, uint8_t *out_status) const;
     int rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const;
     int symbol_at_many(const uint64_t *idx, uint64_t m, uint8_t *out) const;
 

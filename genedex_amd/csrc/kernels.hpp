@@ -127,6 +127,13 @@ void launch_pack_queries(const IndexView &ix, const uint8_t *d_qbuf, uint64_t n_
                          uint8_t *d_bad_flags, unsigned long long *d_bad_symbols, hipStream_t stream);
 void launch_extend_front(const IndexView &ix, uint32_t *d_start, uint32_t *d_end, const uint8_t *d_io_symbols,
                          uint64_t m, uint8_t *d_out_status, hipStream_t stream);
+// gdx_suffix_segments_many[_dev]: per query the greedy backward factorisation into longest matching suffix segments,
+// one launch.  Segment j of query i in slot i * max_segments + j of d_length / d_start / d_end, unused slots zeroed;
+// lf_only: never leave the occurrence table for the text (same results).  d_status may be null.
+void launch_suffix_segments(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq,
+                            uint32_t max_segments, bool lf_only, uint32_t *d_n_segments, uint32_t *d_remaining,
+                            uint32_t *d_length, uint32_t *d_start, uint32_t *d_end, uint8_t *d_status, hipStream_t stream,
+                            const QueryOptions &qo = QueryOptions());
 // d_error (u32, pre-zeroed) is set to 1 when an argument is out of range
 void launch_rank_many(const IndexView &ix, const uint8_t *d_symbols, const uint32_t *d_idx, uint64_t m,
                       uint32_t *d_out, uint32_t *d_error, hipStream_t stream);

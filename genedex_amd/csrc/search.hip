@@ -3528,6 +3528,169 @@ __global__ __launch_bounds__(kBlock) void extend_front_kernel(IndexView ix, uint
     }
 }
 
+// gdx_suffix_segments_many[_dev]: the greedy backward factorisation of every read into its longest matching suffix
+// segments (include/gdx.h).  A segment is what Cursor::extend_query_front (cursor.rs:34-51) makes of the read's symbols
+// from position e leftwards, starting from [0, n), until a step would empty the interval: the interval BEFORE that step
+// and the number of steps taken.  The next segment starts in front of it, up to max_segments times, all in one launch.
+// kGroup lanes per read and the table access of search_kernel / extend_front_kernel; control flow is uniform inside a
+// group, its first lane writes.  Three routes, identical results:
+//   LF steps    one per symbol: PairTable::lf1 (one 128-byte fetch) for symbols 1..4 on pair lines, else Table::rank2
+//   top table   a segment that has top_depth symbols 1..4 to start with takes their interval from the top table; the
+//               entry of an absent D-mer only says that the segment is shorter, which is then found step by step
+//   text        (kText: the index holds text units, SA and ISA) once the interval is ONE row the rest of the segment
+//               is read off the text in front of p = SA[row]: every lane compares eight symbols, a round covers
+//               8 kGroup, and the row afterwards is ISA[p - matched].  Text symbols outside 1..4 (sentinels, N, the
+//               pad in front of the text) never match; a READ symbol outside 1..4 hands the segment back to the LF
+//               steps, which know what an N matches and report symbols that are not in the alphabet.
+struct SegmentsOut {
+    uint32_t *n_segments, *remaining, *length, *start, *end;
+    uint8_t *status;
+};
+
+// The fetch chain of a read is dependent and latency-bound, so the kernel lives on reads in flight.  Waves per SIMD from
+// the registers the compiler reports (-Rpass-analysis=kernel-resource-usage): pair lines + text route 83 VGPRs = 5 waves
+// (asked for 6 it spills 20 bytes to scratch), the other text and one-lane instances 6 (61 .. 73 VGPRs), the rest 7
+// (53 .. 71); no scratch in any instance.
+template <class Table, int kGroup, bool kPair, bool kText>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((kText && kPair) ? 5 : ((kText || kGroup == 1) ? 6 : 7)))) void suffix_segments_kernel(
+    IndexView ix, const uint8_t *__restrict__ qbuf, const uint64_t *__restrict__ qoff, uint64_t nq, uint32_t max_segments,
+    SegmentsOut out)
+{
+    __shared__ uint8_t s_dense[256];
+    __shared__ uint32_t s_count[257];
+    for (int i = threadIdx.x; i < 256; i += kBlock) s_dense[i] = ix.io_to_dense[i];
+    for (int i = threadIdx.x; i <= ix.sigma; i += kBlock) s_count[i] = ix.count[i];
+    __syncthreads();
+
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * (kBlock / kGroup);
+    const bool writer = (threadIdx.x % kGroup) == 0;
+    const uint32_t sub = threadIdx.x % kGroup;
+    const uint32_t depth = (ix.top != nullptr && ix.layout == 0) ? ix.top_depth : 0u;
+    for (uint64_t q = static_cast<uint64_t>(blockIdx.x) * (kBlock / kGroup) + threadIdx.x / kGroup; q < nq; q += stride) {
+        const uint64_t begin = qoff[q];
+        const uint32_t m = static_cast<uint32_t>(qoff[q + 1] - begin);
+        const uint64_t slot0 = q * max_segments;
+        uint32_t e = m, n_seg = 0, status = GDX_Q_OK;
+        while (e > 0u && n_seg < max_segments) {
+            uint32_t lo = 0, hi = ix.n, len = 0;
+            if (depth != 0u && e >= depth) {  // the segment's first `depth` symbols as top_lookup takes them
+                uint32_t a = 0, b = 0;
+                for (uint32_t s = 0; s < depth; s++) {
+                    const uint32_t c = s_dense[qbuf[begin + e - 1u - s]];
+                    if (s < 8u) a |= c << (4u * (7u - s));
+                    else b |= c << (4u * (15u - s));
+                }
+                uint32_t tlo, thi;
+                if (top_lookup(ix, a, b, tlo, thi) && tlo != thi) {
+                    lo = tlo;
+                    hi = thi;
+                    len = depth;
+                }
+            }
+            QueryWindow win;
+            win.init(qbuf, begin, begin + (e - len));
+            bool text_open = kText;  // false between a read symbol outside 1..4 and the LF step that takes it
+            while (len < e) {
+                if (kText && text_open && len != 0u && hi - lo == 1u) {
+                    uint32_t p = ix.sa_full[lo];  // the suffix at p starts with the segment so far
+                    bool blocked = false;
+                    while (len < e) {
+                        const uint32_t rem = e - len;
+                        const uint64_t at = begin + rem;  // read symbol j of the round sits at at - 1 - j, text symbol at p - 1 - j
+                        // (a round begins with p >= 0 and looks at most 8 kGroup <= 32 symbols back: inside the pad units)
+                        const uint64_t t_hi = static_cast<uint64_t>(p) + 32u * kTextPadUnits - 1u - 8u * sub, t_lo = t_hi - 7u;
+                        const u32x4 u_hi = ix.text_units[t_hi >> 5];
+                        const u32x4 u_lo = (t_lo >> 5) != (t_hi >> 5) ? ix.text_units[t_lo >> 5] : u_hi;
+                        uint32_t mine = 0, dirty = 0;
+                        for (uint32_t k = 0; k < 8u; k++) {
+                            const uint32_t j = 8u * sub + k;
+                            if (j >= rem) break;
+                            const uint32_t c = s_dense[qbuf[at - 1u - j]];
+                            if (c - 1u >= 4u) {
+                                dirty = 1u;
+                                break;
+                            }
+                            const uint64_t t = t_hi - k;
+                            const u32x4 u = (t >> 5) == (t_hi >> 5) ? u_hi : u_lo;
+                            const uint32_t i = static_cast<uint32_t>(t & 31u);
+                            const uint32_t code = ((i < 16u ? u.x >> (2u * i) : u.y >> (2u * (i - 16u)))) & 3u;
+                            if (((u.z >> i) & 1u) != 0u || code != c - 1u) break;
+                            mine++;
+                        }
+                        const uint32_t v = mine | (dirty << 8);
+                        uint32_t total = 0, stop = 0, stop_dirty = 0;
+#pragma unroll
+                        for (int l = 0; l < kGroup; l++) {
+                            const uint32_t vl = kGroup == 1 ? v : static_cast<uint32_t>(__shfl(static_cast<int>(v), l, kGroup));
+                            if (stop == 0u) {
+                                total += vl & 0xffu;
+                                if ((vl & 0xffu) < 8u) {
+                                    stop = 1u;
+                                    stop_dirty = vl >> 8;
+                                }
+                            }
+                        }
+                        p -= total;
+                        len += total;
+                        if (stop != 0u) {
+                            blocked = stop_dirty == 0u;  // a mismatch, a sentinel, the text's or the read's first symbol
+                            break;
+                        }
+                    }
+                    lo = ix.isa[p];
+                    hi = lo + 1u;
+                    if (blocked || len == e) break;
+                    text_open = false;
+                    win.init(qbuf, begin, begin + (e - len));
+                    continue;
+                }
+                const uint32_t c = s_dense[win.get(begin + (e - len) - 1u)];
+                if (c == 0u) {  // alphabet.rs:195-198: cursor.rs:34-38 translates before anything else
+                    status = GDX_Q_INVALID_SYMBOL;
+                    break;
+                }
+                if (lo == hi) break;  // (an index without rows: nothing occurs)
+                uint32_t nlo, nhi;
+                if (kPair && c <= 4u) {
+                    PairTable::lf1<0, kGroup>(ix, c, lo, hi, nlo, nhi);
+                } else {
+                    Table::rank2(ix, c, lo, hi, nlo, nhi);
+                    const uint32_t cc = s_count[c];
+                    nlo += cc;
+                    nhi += cc;
+                }
+                if (nlo == nhi) break;  // the stop rule: the interval from before the step that emptied it
+                lo = nlo;
+                hi = nhi;
+                len++;
+                text_open = kText;
+            }
+            if (status != GDX_Q_OK) break;
+            if (writer) {
+                out.length[slot0 + n_seg] = len;
+                out.start[slot0 + n_seg] = len != 0u ? lo : 0u;
+                out.end[slot0 + n_seg] = len != 0u ? hi : 0u;
+            }
+            e -= len != 0u ? len : 1u;
+            n_seg++;
+        }
+        if (status != GDX_Q_OK) {
+            n_seg = 0;
+            e = m;
+        }
+        if (writer) {
+            for (uint32_t j = n_seg; j < max_segments; j++) {
+                out.length[slot0 + j] = 0u;
+                out.start[slot0 + j] = 0u;
+                out.end[slot0 + j] = 0u;
+            }
+            out.n_segments[q] = n_seg;
+            out.remaining[q] = e;
+            if (out.status != nullptr) out.status[q] = static_cast<uint8_t>(status);
+        }
+    }
+}
+
 template <class Table>
 __global__ __launch_bounds__(kBlock) void rank_many_kernel(IndexView ix, const uint8_t *__restrict__ symbols,
                                                            const uint32_t *__restrict__ idx, uint64_t m,
@@ -4476,6 +4639,31 @@ void launch_extend_front(const IndexView &ix, uint32_t *d_start, uint32_t *d_end
         hipLaunchKernelGGL((extend_front_kernel<GenericTable, 1, false>), dim3(grid_for_items(m)), dim3(kBlock), 0,
                            stream, ix, d_start, d_end, d_io_symbols, m, d_out_status);
     }
+}
+
+void launch_suffix_segments(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq,
+                            uint32_t max_segments, bool lf_only, uint32_t *d_n_segments, uint32_t *d_remaining,
+                            uint32_t *d_length, uint32_t *d_start, uint32_t *d_end, uint8_t *d_status, hipStream_t stream,
+                            const QueryOptions &qo)
+{
+    if (nq == 0) return;
+    const int variant = qo.search_variant >= 0 ? qo.search_variant : search_variant();
+    const bool text = !lf_only && ix.text_units != nullptr && ix.sa_full != nullptr && ix.isa != nullptr;
+    const SegmentsOut out = {d_n_segments, d_remaining, d_length, d_start, d_end, d_status};
+#define GDX_SEGMENTS_LAUNCH(TABLE, GROUP, PAIR)                                                                          \
+    do {                                                                                                                 \
+        if (text)                                                                                                        \
+            hipLaunchKernelGGL((suffix_segments_kernel<TABLE, GROUP, PAIR, true>), dim3(grid_for_items(nq * GROUP)),     \
+                               dim3(kBlock), 0, stream, ix, d_qbuf, d_qoff, nq, max_segments, out);                      \
+        else                                                                                                             \
+            hipLaunchKernelGGL((suffix_segments_kernel<TABLE, GROUP, PAIR, false>), dim3(grid_for_items(nq * GROUP)),    \
+                               dim3(kBlock), 0, stream, ix, d_qbuf, d_qoff, nq, max_segments, out);                      \
+    } while (0)
+    if (ix.layout == 0 && variant == 2 && ix.pair_lines != nullptr) GDX_SEGMENTS_LAUNCH(QuadLineTable, 4, true);
+    else if (ix.layout == 0 && variant != 1) GDX_SEGMENTS_LAUNCH(QuadLineTable, 4, false);
+    else if (ix.layout == 0) GDX_SEGMENTS_LAUNCH(LineTable, 1, false);
+    else GDX_SEGMENTS_LAUNCH(GenericTable, 1, false);
+#undef GDX_SEGMENTS_LAUNCH
 }
 
 void launch_rank_many(const IndexView &ix, const uint8_t *d_symbols, const uint32_t *d_idx, uint64_t m,

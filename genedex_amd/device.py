@@ -363,6 +363,29 @@ class DeviceEngine:
                                                               opt(active_in), opt(n_active_in), opt(active_out),
                                                               opt(n_active_out), _stream()))
 
+    # ---- longest matching suffix segments (gdx_suffix_segments_many_dev) -----------------------------------
+    def alloc_segments(self, nq: int, max_segments: int):
+        d = self.dev
+        slots = max(nq * max_segments, 1)
+        return {
+            "n_segments": torch.empty(max(nq, 1), dtype=torch.int32, device=d),
+            "remaining": torch.empty(max(nq, 1), dtype=torch.int32, device=d),
+            "length": torch.empty(slots, dtype=torch.int32, device=d),
+            "start": torch.empty(slots, dtype=torch.int32, device=d),
+            "end": torch.empty(slots, dtype=torch.int32, device=d),
+            "status": torch.empty(max(nq, 1), dtype=torch.uint8, device=d),
+        }
+
+    def suffix_segments(self, q: DeviceQueries, max_segments: int, out, lf_only: bool = False) -> None:
+        """One fused launch: per query its longest matching suffix segments into `out` (alloc_segments; u32 values in int32
+        tensors, segment j of query i in slot i * max_segments + j).  Plain batches only."""
+        if q.packed or q.uniform_len:
+            raise ValueError("suffix_segments(): plain batches only")
+        _lib.check(self.lib.gdx_suffix_segments_many_dev(
+            self.h, _ptr(q.qbuf), _ptr(q.qoff), q.nq, int(max_segments), _lib.GDX_SEGMENTS_LF_ONLY if lf_only else 0,
+            _ptr(out["n_segments"]), _ptr(out["remaining"]), _ptr(out["length"]), _ptr(out["start"]), _ptr(out["end"]),
+            _ptr(out["status"]) if out.get("status") is not None else None, _stream()))
+
     def search_step_stats(self, q: DeviceQueries):
         """(LF steps, line fetches of all queries, fetch slots their wavefronts spent)"""
         steps = torch.zeros(3, dtype=torch.int64, device=self.dev)

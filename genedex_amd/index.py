@@ -23,6 +23,13 @@ class Hit(NamedTuple):
     position: int
 
 
+class Segment(NamedTuple):
+    """One longest matching suffix segment of a query (FmIndex.suffix_segments_many): query[query_end - length : query_end]"""
+    query_end: int
+    length: int
+    cursor: "Cursor"
+
+
 def _p(a, t):
     return a.ctypes.data_as(t)
 
@@ -414,6 +421,50 @@ class FmIndex:
                                                        _p(qoff, u64p), s.size, _p(st_arr, u8p))
         _lib.check(st, allow=() if strict else (_lib.GDX_ERR_QUERY_STATUS,))
         return s, e, st_arr
+
+    def suffix_segments_raw(self, qbuf, qoff, max_segments, lf_only=False, strict=True):
+        """gdx_suffix_segments_many -> (n_segments u32[nq], remaining u32[nq], length u32[nq * max_segments], start u64, end u64,
+        status u8[nq]): per query its longest matching suffix segments, rightmost first (include/gdx.h has the definition)."""
+        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
+        qoff = np.ascontiguousarray(qoff, dtype=np.uint64)
+        nq = qoff.size - 1
+        slots = max(nq * int(max_segments), 1)
+        n_seg = np.zeros(max(nq, 1), dtype=np.uint32)
+        remaining = np.zeros(max(nq, 1), dtype=np.uint32)
+        length = np.zeros(slots, dtype=np.uint32)
+        start = np.zeros(slots, dtype=np.uint64)
+        end = np.zeros(slots, dtype=np.uint64)
+        status = np.zeros(max(nq, 1), dtype=np.uint8)
+        st = self._lib.gdx_suffix_segments_many(self._h, _p(qbuf, u8p), _p(qoff, u64p), nq, int(max_segments),
+                                                _lib.GDX_SEGMENTS_LF_ONLY if lf_only else 0, _p(n_seg, u32p),
+                                                _p(remaining, u32p), _p(length, u32p), _p(start, u64p), _p(end, u64p),
+                                                _p(status, u8p))
+        _lib.check(st, allow=() if strict else (_lib.GDX_ERR_QUERY_STATUS,))
+        k = nq * int(max_segments)
+        return n_seg[:nq], remaining[:nq], length[:k], start[:k], end[:k], status[:nq]
+
+    def suffix_segments_many(self, queries, max_segments=1):
+        """Per query the list of its Segment(query_end, length, cursor), rightmost first: query[query_end - length : query_end]
+        is the longest suffix of query[:query_end] that occurs, cursor its interval (count() / locate()); a zero-length
+        segment stands for one symbol that occurs nowhere."""
+        qbuf, qoff = pack_queries(queries)
+        n_seg, _, length, start, end, _ = self.suffix_segments_raw(qbuf, qoff, max_segments)
+        out = []
+        for i in range(qoff.size - 1):
+            e = int(qoff[i + 1] - qoff[i])
+            segs = []
+            for j in range(int(n_seg[i])):
+                k = i * max_segments + j
+                segs.append(Segment(e, int(length[k]), Cursor(self, int(start[k]), int(end[k]))))
+                e -= max(int(length[k]), 1)
+            out.append(segs)
+        return out
+
+    def longest_suffix_match(self, query):
+        """(length, Cursor) of the longest suffix of `query` that occurs: length 0 with a cursor of count 0 when its last
+        symbol occurs nowhere, length 0 with cursor_empty() for the empty query"""
+        segs = self.suffix_segments_many([query], 1)[0]
+        return (segs[0].length, segs[0].cursor) if segs else (0, self.cursor_empty())
 
     def rank_many(self, symbols, idx):
         """TextWithRankSupport::rank (text_with_rank_support/mod.rs:106-110), batched."""

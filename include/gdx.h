@@ -344,6 +344,32 @@ int gdx_cursor_locate_many(const gdx_index_t *ix, const uint64_t *start, const u
                            uint64_t m, uint64_t *out_hit_offsets, gdx_hit_t *hits,
                            uint64_t hits_capacity, uint64_t *out_total);
 
+/* Greedy suffix segments: what a read that does not occur as a whole still matches.  For query q of m symbols let e = m
+ * and repeat while e > 0 and fewer than max_segments segments are recorded: start from cursor_empty [0, n) with L = 0;
+ * while e - L > 0 extend the cursor in front by q[e - L - 1] (Cursor::extend_query_front, so alphabets, sentinels and
+ * non-searchable symbols such as N mean what they mean there) -- if the new interval is empty stop and keep the previous
+ * one, else take it and L = L + 1; then record (length L, start, end) and e = e - L, or, if L == 0 (the symbol itself
+ * occurs nowhere), record (0, 0, 0) and e = e - 1.  max_segments = 1 is "the longest suffix that occurs"; more is the
+ * greedy backward factorisation: n_segments - 1 is a lower bound on the read's number of errors, and every segment is a
+ * cursor for gdx_cursor_locate_many.
+ * Per query: out_n_segments, out_remaining = e at the end (0 unless max_segments cut the walk short; the segments tile
+ * q[remaining, m) from the right, a zero-length segment covers one symbol), and the segments in the order found
+ * (rightmost first): segment j of query i in slot i * max_segments + j of out_length / out_start / out_end.  Unused
+ * slots are written as zeros.  A symbol outside the alphabet that the walk REACHES gives the query
+ * GDX_Q_INVALID_SYMBOL, n_segments 0, remaining m and zeroed slots, and the call GDX_ERR_QUERY_STATUS; symbols left
+ * of `remaining` are not looked at.  max_segments == 0, an unknown bit in flags and (host form) a query longer than
+ * 2^32 - 1 symbols: GDX_ERR_INVALID_ARGUMENT.  One fused kernel launch per call; the host form stages the whole batch
+ * (copy in, launch, copy out; no chunked pipeline).  The library picks the route (LF steps, top table, and on an index
+ * that holds text units, full and inverse suffix array the text itself once a segment is down to one row) from what
+ * the index holds; GDX_SEGMENTS_LF_ONLY keeps it on the occurrence table, with the same results.
+ * Handles of the 64-bit engine return GDX_ERR_UNSUPPORTED; gdx_parts_t and gdx_multi_t have no such call. */
+#define GDX_SEGMENTS_LF_ONLY 1u
+int gdx_suffix_segments_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq,
+                             uint32_t max_segments, uint32_t flags,
+                             uint32_t *out_n_segments /*nq*/, uint32_t *out_remaining /*nq*/,
+                             uint32_t *out_length /*nq*max_segments*/, uint64_t *out_start, uint64_t *out_end,
+                             uint8_t *out_status /*nq or NULL*/);
+
 /* ---------------------------------------------------------------------------------------
  * device-resident entry points: all pointers are DEVICE pointers on the handle's GPU, work
  * is enqueued on `stream` (hipStream_t) and the call returns without synchronising.
@@ -352,6 +378,13 @@ int gdx_cursor_locate_many(const gdx_index_t *ix, const uint64_t *start, const u
 int gdx_cursor_extend_front_many_dev(const gdx_index_t *ix, void *d_start /*u32*/, void *d_end /*u32*/,
                                      const void *d_io_symbols, uint64_t m, void *d_out_status,
                                      void *stream);
+/* gdx_suffix_segments_many on device pointers: d_qoff u64[nq + 1], d_n_segments / d_remaining u32[nq], d_length /
+ * d_start / d_end u32[nq * max_segments], d_status u8[nq] or NULL (read it to learn of invalid symbols: the call itself
+ * does not synchronise and returns GDX_OK).  Queries must be shorter than 2^32 symbols. */
+int gdx_suffix_segments_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
+                                 uint32_t max_segments, uint32_t flags, void *d_n_segments, void *d_remaining,
+                                 void *d_length, void *d_start /*u32*/, void *d_end /*u32*/, void *d_status,
+                                 void *stream);
 /* locate for m intervals whose offsets were produced by gdx_hit_offsets_dev; total =
  * d_hit_offsets[m] (the caller reads it back to size d_hits and d_workspace:
  * gdx_locate_workspace_bytes(total)). */
