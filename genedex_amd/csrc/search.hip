@@ -3968,619 +3968,613 @@ __global__ __launch_bounds__(kBlock) void tile_sums_lists_kernel(const uint4 *__
     if ((threadIdx.x & 63u) == 0u && open_slots != 0ull) atomicAdd(rest, open_slots);
 }
 
-void launch_search_call(const IndexView &ix, const SearchCall &call, hipStream_t stream, const QueryOptions &qo)
+// ---- the search launcher: knobs, settings, helpers, stages, driver ---------------------------------------------------------
+// A run-time value as a template argument: f(std::integral_constant<int, V>()) for the V of the list that equals v, the last
+// one when none does.  Only the listed values are instantiated: every call site names exactly the kernels it can launch.
+template <int V, int... Rest, class F>
+static void with_int(int v, F &&f)
 {
-    SearchCall c = call;
-    const uint64_t nq = c.nq;
-    if (nq == 0) return;
-    if (c.mode < 0 || c.mode > 2) fail(GDX_ERR_INVALID_ARGUMENT, "internal: search mode %d", c.mode);
-    const int variant = qo.search_variant >= 0 ? qo.search_variant : search_variant();
-    if (c.packed && (ix.layout != 0 || ix.n_searchable < 4))
-        fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
-    if (c.packed && (c.mode == 2 || c.d_step_stats != nullptr)) fail(GDX_ERR_UNSUPPORTED, "packed queries: search and count / locate only");
-    // Uniform batches (SearchCall::uniform_len): the seed chain and the rank-line kernels compute where a query lies; the
-    // pair-line kernels read offsets, which are then written once into scratch (8 bytes per query, one streaming pass)
-    // (a count / locate call may leave all but a short list to the seed chain, which computes too: decided below)
-    const bool pair_offsets = c.uniform_len != 0u && ix.layout == 0 && variant == 2 && ix.pair_lines != nullptr;
-    uint64_t *d_uniform_off = nullptr;
-    auto dense_uniform_offsets = [&] {
-        d_uniform_off = static_cast<uint64_t *>(stream_scratch(stream, 15, (nq + 1) * sizeof(uint64_t)));
-        hipLaunchKernelGGL(fill_uniform_offsets_kernel, dim3(grid_for_items(nq + 1)), dim3(kBlock), 0, stream, d_uniform_off, nq + 1,
-                           c.uniform_len);
-        c.d_qbeg = d_uniform_off;
-        c.d_qend = d_uniform_off + 1;
-        c.uniform_len = 0;
-    };
-    if (pair_offsets && c.mode != 1) dense_uniform_offsets();
-    const uint32_t ulen = c.uniform_len;
+    if constexpr (sizeof...(Rest) != 0) {
+        if (v != V) return with_int<Rest...>(v, f);
+    }
+    f(std::integral_constant<int, V>());
+}
+template <class F> static void with_bool(bool b, F &&f) { b ? f(std::true_type()) : f(std::false_type()); }
+template <class F> static void with_jump_bytes(int jump_bytes, F &&f) { with_int<32, 16, 8>(jump_bytes, f); }
+// how the kernels get 2-bit codes: 2 = the buffer holds them (packed queries), 1 = v_perm tables, 0 = the table in LDS
+template <class F> static void with_xlate(int xlate, F &&f) { with_int<2, 1, 0>(xlate, f); }
+
+static int env_int(const char *name, int absent) { const char *e = getenv(name); return e ? atoi(e) : absent; }
+static long env_long(const char *name, long absent) { const char *e = getenv(name); return e ? atol(e) : absent; }
+static bool env_set(const char *name) { return getenv(name) != nullptr; }
+
+// The environment variables of the search launcher ("Search knobs"): debugging aids, A/B switches and test hooks,
+// read once per process when the first search is launched.  How each meets QueryOptions is written in SearchSettings.
+// (GDX_SEARCH_VARIANT is search_variant()'s above; GDX_SEARCH_SEED_PAIRS and GDX_SEED_LANE_BLOCKS are read per call.)
+struct SearchKnobs {
+    long grid = env_long("GDX_SEARCH_GRID", 0);  // absolute number of blocks of the group and pair-line kernels; <= 0: computed
+    unsigned pad = static_cast<unsigned>(env_long("GDX_SEARCH_PAD", 0));  // dynamic LDS bytes per block of those kernels
+    int lanes = env_int("GDX_SEARCH_LANES", 4) == 8 ? 8 : 4;  // lanes per query of the pair-line kernels
+    int policy = env_int("GDX_LOAD_POLICY", 0);               // 1: sc1 line / entry loads
+    int schedule = [] { const char *e = getenv("GDX_SEARCH_SCHEDULE"); return (e && e[0] == '0') ? 0 : 1; }();  // 0: keep the query order
+    int defer = env_int("GDX_SEARCH_DEFER", 0);  // load rounds beyond its allowance after which a straggler is parked; 0: never
+    int fast = env_int("GDX_SEARCH_FAST", -1);   // these three: -1 = unset, else they override the options of the same name
+    int exact = env_int("GDX_SEARCH_EXACT", -1);
+    int seed = env_int("GDX_SEARCH_SEED", -1);
+    int text = env_int("GDX_SEARCH_TEXT", 1);                // 0: pair lines only, no text route
+    bool no_perm = env_set("GDX_SEARCH_NO_PERM");            // debug: translate through LDS
+    bool fast_stats = env_set("GDX_SEARCH_FAST_STATS");      // debug: print the size of the leftover lists (synchronises)
+    int seed_lean = env_int("GDX_SEARCH_SEED_LEAN", 1);      // the A/Bs of the seed chain, 0 = off (seed_front) ...
+    int seed_chain = env_int("GDX_SEARCH_SEED_CHAIN", 1);
+    int seed_packed = env_int("GDX_SEARCH_SEED_PACKED", 1);
+    int seed_lane = env_int("GDX_SEED_LANE", 1);             // 0: the four-lane kernel
+    int seed_cursor = env_int("GDX_SEARCH_SEED_CURSOR", 1);  // 0: the exact kernel alone
+    unsigned seed_pad = static_cast<unsigned>(env_long("GDX_SEED_PAD", 0));  // experiments: dynamic LDS bytes per block of the seed kernels, which caps the resident blocks per CU
+    uint32_t seed_lane_range = static_cast<uint32_t>(env_long("GDX_SEED_LANE_RANGE", 0));  // experiments: reads per range of the lane kernel, a multiple of 64 up to kLaneRange
+    unsigned seed_list_blocks = static_cast<unsigned>(env_long("GDX_SEED_LIST_BLOCKS", 1792));  // grid cap of the verify kernel over a list
+};
+static const SearchKnobs &search_knobs() { static const SearchKnobs knobs; return knobs; }
+
+// What a call runs with, resolved from QueryOptions, the knobs and the index: every precedence rule is written here, once.
+struct SearchSettings {
+    int variant;     // QueryOptions::search_variant, else set_search_variant() / GDX_SEARCH_VARIANT, else 2 (pair lines)
+    int lanes;       // lanes per query of the pair-line kernels: 8 (one 16-byte chunk per lane) or 4 (two chunks per lane, twice the
+                     // queries in flight); QueryOptions::search_lanes, else GDX_SEARCH_LANES, else 4
+    int policy;      // cache policy of their line / entry loads (SearchLauncher::pair_lines): QueryOptions::load_policy / GDX_LOAD_POLICY=0|1
+    int schedule;    // ranges whose query lengths are spread out are searched in length order (order_range_by_length);
+                     // QueryOptions::length_schedule / GDX_SEARCH_SCHEDULE=0 keeps the query order
+    // Stragglers are parked after their allowance + defer_after load rounds and finished together (search_pair_body);
+    // QueryOptions::search_defer_after (resolved per index by FmIndex::query_options: on when the text is repetitive) /
+    // GDX_SEARCH_DEFER; 0 = never.  The accounting kernels never park (their per-query round counts describe the plain
+    // lock-step schedule).
+    uint32_t defer_after;
+    int fast;         // GDX_SEARCH_FAST (a debug override), else QueryOptions::search_fast (which arrives resolved by
+                      // FmIndex::query_options): 0 = no fast-path / verify kernel, 2 = with sixteen-row rounds, else 1
+    bool exact;       // GDX_SEARCH_EXACT, else QueryOptions::search_exact: search_exact_kernel4 in front of the general kernel
+    bool seed;        // GDX_SEARCH_SEED, else QueryOptions::search_seed: the seed table's kernels
+    bool perm;        // the index has v_perm tables and GDX_SEARCH_NO_PERM is not set
+    int xlate;        // with_xlate: packed queries 2, else perm
+    bool text_route;  // the text route in the jump table's place (search_exact_kernel4<0, ., ., true>); GDX_SEARCH_TEXT=0: pair lines only
+
+    SearchSettings(const IndexView &ix, const QueryOptions &qo, const SearchKnobs &k, const SearchCall &c)
+    {
+        variant = qo.search_variant >= 0 ? qo.search_variant : search_variant();
+        lanes = (qo.search_lanes == 4 || qo.search_lanes == 8) ? qo.search_lanes : k.lanes;
+        policy = (qo.load_policy >= 0 ? qo.load_policy : k.policy) == 1 ? 1 : 0;
+        schedule = qo.length_schedule >= 0 ? (qo.length_schedule != 0) : k.schedule;
+        defer_after = c.d_step_stats != nullptr ? 0u : static_cast<uint32_t>(qo.search_defer_after >= 0 ? qo.search_defer_after : k.defer);
+        const int f = k.fast >= 0 ? k.fast : qo.search_fast;
+        fast = f == 0 ? 0 : (f == 2 ? 2 : 1);
+        exact = k.exact >= 0 ? k.exact != 0 : qo.search_exact != 0;
+        seed = k.seed >= 0 ? k.seed != 0 : qo.search_seed != 0;
+        perm = ix.perm_ok && !k.no_perm;
+        xlate = c.packed ? 2 : (perm ? 1 : 0);
+        text_route = ix.jump == nullptr && ix.sa_full != nullptr && ix.isa != nullptr && ix.text_units != nullptr && k.text != 0;
+    }
+};
+
+struct ListGrid { unsigned blocks; uint32_t range; };  // range: queries per block and range
+// blocks for ranges of `range` queries, at most `cap`
+static unsigned range_blocks(uint64_t nq, uint32_t range, uint64_t cap)
+{
+    const uint64_t ranges = (nq + range - 1) / range;
+    return static_cast<unsigned>(ranges < cap ? ranges : cap);
+}
+// Every block searches contiguous ranges of `range` queries (a multiple of 64, at most range_cap): about 48 rounds per
+// group at large batches, 1792+ blocks at small ones; grid_override (GDX_SEARCH_GRID) = number of blocks.
+static ListGrid range_grid(uint64_t nq, uint32_t range_cap, long grid_override)
+{
+    uint64_t per_block = (nq + 1791) / 1792;
+    per_block = (per_block + 63) / 64 * 64;
+    const uint32_t range = static_cast<uint32_t>(per_block > range_cap ? range_cap : per_block);
+    return {grid_override > 0 ? static_cast<unsigned>(grid_override) : range_blocks(nq, range, 1u << 20), range};
+}
+// A list left over by another kernel of the call: short, and its length is only known on the device -- small ranges spread it
+// over the chip, a capped grid strides over whatever there is
+static ListGrid short_list_grid(uint64_t nq, unsigned cap = 8192) { return {range_blocks(nq, 256, cap), 256}; }
+// Launch geometry of the group kernels (measured on MI355X, hg38-scale index, 100 M reads,
+// profiles/r01/search_variants.md): many short-lived blocks beat a resident grid -- 65536 blocks: 78 ms,
+// 1792 (7 per CU): 89 ms, 2048 (8 per CU, all resident, lock-step): 112 ms.  So: about 48 queries per
+// group, at most 65536 blocks, never fewer blocks than groups need.
+// Experiments: GDX_SEARCH_GRID = absolute number of blocks, GDX_SEARCH_PAD = dynamic LDS bytes per block.
+static unsigned group_grid(uint64_t nq, uint64_t groups_per_block, long grid_override)
+{
+    const uint64_t needed = (nq + groups_per_block - 1) / groups_per_block;
+    uint64_t blocks = (nq + groups_per_block * 48 - 1) / (groups_per_block * 48);
+    if (blocks < 1792) blocks = 1792;
+    if (blocks > 65536) blocks = 65536;
+    if (blocks > needed) blocks = needed;
+    if (grid_override > 0) blocks = static_cast<uint64_t>(grid_override);
+    return static_cast<unsigned>(blocks);
+}
+
+// the kernels' views of the index
+static SeedView seed_view(const IndexView &ix, const uint32_t *isa)
+{
+    return SeedView{ix.seed, ix.text_units, isa, ix.io_to_dense, ix.seed_buckets, ix.seed_k, ix.seed_tag_bits,
+                    ix.perm_code_lo, ix.perm_code_hi, ix.perm_exp_lo, ix.perm_exp_hi, ix.perm_mask};
+}
+static VerifyView verify_view(const IndexView &ix)
+{
+    // rows a verify round takes: four when SA[row] is one fetch away, one when it costs a locate walk
+    const bool entry_sa = ix.jump != nullptr && ix.jump_bytes == 32;
+    const uint32_t max_rows = (ix.sa_full != nullptr || entry_sa) ? 4u : 1u;
+    return VerifyView{ix.top, ix.text_units, ix.sa_full, entry_sa ? ix.jump : nullptr, ix.lines, ix.sb_offsets, ix.count,
+                      ix.sa_samples, ix.border_keys, ix.border_vals, ix.io_to_dense, ix.top_depth, ix.n, ix.n_texts,
+                      ix.sa_inv, ix.sa_rot, ix.sa_limit, max_rows, ix.perm_code_lo, ix.perm_code_hi, ix.perm_exp_lo,
+                      ix.perm_exp_hi, ix.perm_mask, ix.seed, ix.seed_buckets, ix.seed_k, ix.seed_tag_bits, ix.seed_pairs, ix.seed_quads};
+}
+static ExactView exact_view(const IndexView &ix, bool with_seed)
+{
+    return ExactView{ix.top, ix.jump, ix.pair_lines, ix.io_to_dense, ix.top_depth, ix.n, static_cast<uint32_t>(ix.depth),
+                     ix.perm_code_lo, ix.perm_code_hi, ix.perm_exp_lo, ix.perm_exp_hi, ix.perm_mask, ix.sa_full, ix.isa,
+                     ix.text_units, with_seed ? ix.seed : nullptr, ix.seed_buckets, ix.seed_k, ix.seed_tag_bits};
+}
+static FastView fast_view(const IndexView &ix)
+{
+    return FastView{ix.top, ix.jump, ix.io_to_dense, ix.top_depth, ix.sa_inv, ix.sa_rot, ix.sa_limit,
+                    ix.perm_code_lo, ix.perm_code_hi, ix.perm_exp_lo, ix.perm_exp_hi, ix.perm_mask};
+}
+
+// What a seed kernel (search_seed_kernel4, search_seed_lane_kernel) and seed_text_kernel4 behind it share
+struct SeedLaunch {
+    SeedView sv;
+    ListGrid grid;                              // of the seed kernel
+    unsigned lds = 0;                           // its dynamic LDS bytes
+    uint4 *rec = nullptr;                       // count / locate: the call's records ...
+    uint32_t *start = nullptr, *end = nullptr;  // ... exact intervals: the call's intervals
+    uint32_t *first = nullptr, *lng = nullptr;  // counted lists: reads left to the next kernel, reads for seed_text_kernel4
+    uint4 *state = nullptr;                     // where a listed read stands (null: the next kernel starts it over)
+    uint32_t *compact = nullptr;
+    uint2 *long_state = nullptr;
+    uint32_t long_stride = 0, state_packed = 0;
+};
+
+// What one stage of a call leaves for the next
+struct SearchChain {
     // the call's counters (and what the caller wants zeroed with them) are zeroed by one launch before its first kernel
     ZeroSet zs;
-    if (c.also_zero != nullptr) zs = *c.also_zero;
-    // Launch geometry of the group kernels (measured on MI355X, hg38-scale index, 100 M reads,
-    // profiles/r01/search_variants.md): many short-lived blocks beat a resident grid -- 65536 blocks: 78 ms,
-    // 1792 (7 per CU): 89 ms, 2048 (8 per CU, all resident, lock-step): 112 ms.  So: about 48 queries per
-    // group, at most 65536 blocks, never fewer blocks than groups need.
-    // Experiments: GDX_SEARCH_GRID = absolute number of blocks, GDX_SEARCH_PAD = dynamic LDS bytes per block.
-    static const long grid_override = [] { const char *e = getenv("GDX_SEARCH_GRID"); return e ? atol(e) : 0L; }();
-    static const long pad_override = [] { const char *e = getenv("GDX_SEARCH_PAD"); return e ? atol(e) : 0L; }();
-    const unsigned lds_pad = static_cast<unsigned>(pad_override);
-    auto group_grid = [&](uint64_t groups_per_block) {
-        const uint64_t needed = (nq + groups_per_block - 1) / groups_per_block;
-        uint64_t blocks = (nq + groups_per_block * 48 - 1) / (groups_per_block * 48);
-        if (blocks < 1792) blocks = 1792;
-        if (blocks > 65536) blocks = 65536;
-        if (blocks > needed) blocks = needed;
-        if (grid_override > 0) blocks = static_cast<uint64_t>(grid_override);
-        return static_cast<unsigned>(blocks);
-    };
-    // lanes per query of the pair-line kernels: 8 (one 16-byte chunk per lane) or 4 (two chunks per lane, twice the queries
-    // in flight); QueryOptions::search_lanes, else GDX_SEARCH_LANES, else 4
-    static const int env_lanes = [] {
-        const char *e = getenv("GDX_SEARCH_LANES");
-        return (e && atoi(e) == 8) ? 8 : 4;
-    }();
-    const int lanes = (qo.search_lanes == 4 || qo.search_lanes == 8) ? qo.search_lanes : env_lanes;
-    // cache policy of their line / entry loads (see below): QueryOptions::load_policy / GDX_LOAD_POLICY=0|1
-    static const int env_policy = [] {
-        const char *e = getenv("GDX_LOAD_POLICY");
-        return e ? atoi(e) : 0;
-    }();
-    const int policy = (qo.load_policy >= 0 ? qo.load_policy : env_policy) == 1 ? 1 : 0;
-    CursorArgs ca = c.cursors;
-    bool leftover_list = false;  // ca.active_in is the (short) list another kernel of this call left over
-    uint32_t *seed_list = nullptr;  // ... the seed kernel's, with each read's state in its record slot: search_fast_kernel4 next
+    CursorArgs ca;                   // the call's cursors; behind the front (a): its list and resume states
+    bool leftover_list = false;      // ca.active_in is the (short) list another kernel of this call left over
+    uint32_t *seed_list = nullptr;   // ... the seed kernel's, with each read's state in its record slot: search_fast_kernel4 next
     uint32_t seed_state_packed = 0;  // ... in the packed form (kStatePacked)
-    bool compact_by_seed = false;   // c.d_compact has been filled by the seed kernel
+    bool compact_by_seed = false;    // c.d_compact has been filled by the seed kernel
     uint32_t *fold_left = nullptr, *fold_long = nullptr;  // the lane kernel's lists when it counts the hit totals (d_tile_sums)
-    if (c.tile_sums_done != nullptr) *c.tile_sums_done = false;
-    if (c.d_compact != nullptr && (c.mode != 1 || c.d_rec == nullptr))
-        fail(GDX_ERR_INVALID_ARGUMENT, "internal: compact results go with the records of a count / locate search");
-    // Count / locate searches on an index with text units and no jump table: top table, then the rest of the query against
-    // the text at SA[row] (search_verify_kernel4); what it cannot finish is listed for the general kernel of the index
-    // (pair lines or rank lines) below.  QueryOptions::search_fast = 0 switches it off like the other fast path.
+    uint64_t *d_uniform_off = nullptr;  // (b) offsets of a uniform batch in scratch ...
+    bool sparse_offsets = false;        // ... of the listed queries only, written before each kernel that takes a list
+    // (c) grid and range over all queries, of the exact kernel and of the general kernel, and the lists the latter two take
+    ListGrid all{}, exact{}, general{};
+    CursorArgs ca_exact, ca_general;
+};
+
+// One call on its way through the stages (a) .. (e) of launch_search_call
+struct SearchLauncher {
+    const IndexView &ix;
+    SearchCall c;  // (a uniform batch in front of offset-reading kernels: d_qbeg / d_qend / uniform_len are rewritten, stage b)
+    hipStream_t stream;
+    const SearchKnobs &k;
+    const SearchSettings s;
+    const uint64_t nq;
+    const bool seed_pairs;       // per call: GDX_SEARCH_SEED_PAIRS is not 0 (the A/B of the two-copy repeat records)
+    const long lane_blocks_cap;  // per call: GDX_SEED_LANE_BLOCKS; <= 0: none
+    uint32_t ulen = 0;           // the uniform length for the kernels that compute where a query lies (0: they read offsets)
+    SearchChain st;
+
+    // A list whose length only the device knows, in stream scratch: word 0 counts its entries, which start at word 4 (nq + 4
+    // words in all).  The counter is zeroed by the call's ZeroSet launch (zs) or, without one, by a memset of its own here.
+    uint32_t *counted_list(int slot, ZeroSet *zs)
     {
-        static const int env_fast_v = [] { const char *e = getenv("GDX_SEARCH_FAST"); return e ? atoi(e) : -1; }();
-        static const int env_seed = [] { const char *e = getenv("GDX_SEARCH_SEED"); return e ? atoi(e) : -1; }();
+        uint32_t *list = static_cast<uint32_t *>(stream_scratch(stream, slot, (nq + 4) * sizeof(uint32_t)));
+        if (zs != nullptr) zs->add(list, sizeof(uint32_t));
+        else GDX_HIP(hipMemsetAsync(list, 0, sizeof(uint32_t), stream));
+        return list;
+    }
+    void print_left(const char *path, const uint32_t *n_list, const char *next)  // GDX_SEARCH_FAST_STATS
+    {
+        uint32_t n_left = 0;
+        GDX_HIP(hipMemcpyAsync(&n_left, n_list, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        GDX_HIP(hipStreamSynchronize(stream));
+        fprintf(stderr, "gdx: %s path left %u of %llu queries to the %s kernel\n", path, n_left, static_cast<unsigned long long>(nq), next);
+    }
+    template <int kXlate, bool kExact>
+    void launch_seed_text(const SeedLaunch &a)
+    {
+        hipLaunchKernelGGL((seed_text_kernel4<kXlate, kExact>), dim3(range_blocks(nq, kBlock / 4, 8192)), dim3(kBlock), 0, stream, a.sv,
+                           c.d_qbuf, c.d_qbeg, a.lng + 4, a.lng, a.long_state, a.long_stride, c.d_count, c.d_status, a.rec, a.start,
+                           a.end, a.compact, a.state, a.first + 4, a.first, ulen);
+    }
+    // the four-lane seed kernel and seed_text_kernel4 over its list of long reads
+    template <int kXlate, bool kExact>
+    void launch_seed_and_text(const SeedLaunch &a)
+    {
+        hipLaunchKernelGGL((search_seed_kernel4<kXlate, kExact>), dim3(a.grid.blocks), dim3(kBlock), a.lds, stream, a.sv, c.d_qbuf,
+                           c.d_qbeg, c.d_qend, nq, c.d_count, c.d_status, a.rec, a.start, a.end, a.grid.range, a.first + 4, a.first,
+                           a.state, a.compact, a.lng + 4, a.lng, a.long_state, a.long_stride, a.state_packed, ulen, CursorArgs());
+        launch_seed_text<kXlate, kExact>(a);
+    }
+    // search_verify_kernel4 over all queries (list == null) or over the seed kernel's list; what it leaves goes to `left`
+    template <bool kSeed>
+    void launch_verify(ListGrid grid, uint32_t *left, uint32_t *list, const uint4 *state, uint32_t wide)
+    {
+        const VerifyView vv = verify_view(ix);
+        with_xlate(s.xlate, [&](auto X) {
+            hipLaunchKernelGGL((search_verify_kernel4<decltype(X)::value, kSeed>), dim3(grid.blocks), dim3(kBlock), 0, stream, vv,
+                               c.d_qbuf, c.d_qbeg, c.d_qend, nq, c.d_count, c.d_status, c.d_rec, grid.range, left + 4, left,
+                               list ? list + 4 : nullptr, list, ulen, state, wide, state != nullptr ? st.seed_state_packed : 0u);
+        });
+    }
+
+    // (a), on an index with seed table: the seed table's own kernel first (absent k-mers and k-mers that occur once); what it
+    // lists -- k-mers on several rows, reads shorter than the seed, other symbols -- goes on in search_fast_kernel4 from the
+    // entry's interval when the index has top and jump tables (one jump round for the rest of a read from a repeat), else
+    // through the seed-aware verify kernel; their leftovers go to the general kernel.  The lists' lengths are only known on the
+    // device: small ranges, a capped grid that strides over whatever there is.
+    void seed_front(ListGrid v_grid, uint32_t *d_left)
+    {
+        const bool pair_general = s.variant == 2 && ix.pair_lines != nullptr;
+        // (to_fast implies every condition of `fast` in pair_lines)
+        const bool to_fast = k.seed_lean != 0 && k.seed_chain != 0 && pair_general && ix.top != nullptr && ix.top_depth >= 1u &&
+                             ix.jump != nullptr && ix.top_depth >= static_cast<uint32_t>(ix.depth) && s.lanes == 4 && s.policy == 0 &&
+                             s.fast != 0;
+        // (... or the verify kernel's, which hands the plain form on to the general kernel: to_verify_with_state below)
+        const bool to_verify_packed = !to_fast && pair_general && k.seed_lean != 0;
+        st.seed_state_packed = (to_fast || to_verify_packed) && c.d_rec != nullptr && k.seed_packed != 0 ? 1u : 0u;
+        // (2: states of two-copy repeats name their record in IndexView::seed_pairs -- only the verify kernel reads those)
+        if (st.seed_state_packed != 0u && !to_fast && (ix.seed_pairs != nullptr || ix.seed_quads != nullptr) && seed_pairs)
+            st.seed_state_packed = 2u;
+        if (k.seed_lean == 0) {
+            st.zs.flush(stream);
+            return launch_verify<true>(v_grid, d_left, nullptr, nullptr, 0u);
+        }
+        SeedLaunch a{seed_view(ix, nullptr), v_grid, k.seed_pad, c.d_rec};
+        a.first = counted_list(12, &st.zs);
+        // (the pair-line general kernel resumes listed reads from their k-mer's interval as well: the verify kernel in
+        // between takes the narrow ones and leaves the wide ones to it)
+        const bool to_verify_with_state = !to_fast && pair_general && c.d_rec != nullptr;
+        a.state = (to_fast || to_verify_with_state) ? c.d_rec : nullptr;
+        a.compact = c.d_compact;
+        // reads longer than a seed entry covers: listed with {position, symbols in front} in the first half of their
+        // record slot (an array of its own when the call has no records) for seed_text_kernel4, whose own
+        // leftovers (a symbol outside A C G T further front) join the seed kernel's list
+        a.lng = counted_list(13, &st.zs);
+        a.long_state = c.d_rec != nullptr ? reinterpret_cast<uint2 *>(c.d_rec) : static_cast<uint2 *>(stream_scratch(stream, 14, nq * sizeof(uint2)));
+        a.long_stride = c.d_rec != nullptr ? 2u : 1u;
+        a.state_packed = st.seed_state_packed;
+        // one lane per read (search_seed_lane_kernel) where its loads apply: 2-bit codes or v_perm tables, k <= 24, a
+        // dword-aligned buffer; GDX_SEED_LANE=0: the four-lane kernel
+        const bool lane_kernel = k.seed_lane != 0 && s.xlate != 0 && ix.seed_k <= 24u && ix.seed_k >= 8u &&
+                                 (reinterpret_cast<uintptr_t>(c.d_qbuf) & 3u) == 0;
+        // the locate's hit totals folded into this call (SearchCall::d_tile_sums): the lane kernel counts what it
+        // answers, tile_sums_lists_kernel adds its two lists once the whole chain has run (finish_fold)
+        unsigned long long *fold = nullptr;
+        if (lane_kernel && c.d_tile_sums != nullptr && c.d_tile_rest != nullptr && c.d_compact != nullptr) {
+            fold = c.d_tile_sums;
+            st.zs.add(fold, ((nq + kSumTile - 1) / kSumTile) * sizeof(unsigned long long));
+            st.fold_left = a.first;
+            st.fold_long = a.lng;
+        }
+        // (its ranges: at most kLaneRange reads, the capacity of its lists in LDS)
+        const uint32_t lane_range = k.seed_lane_range >= 64u && k.seed_lane_range <= kLaneRange ? k.seed_lane_range / 64u * 64u
+                                    : (v_grid.range < kLaneRange ? v_grid.range : kLaneRange);
+        if (lane_range % 64u != 0u) fail(GDX_ERR_INVALID_ARGUMENT, "internal: the lane kernel's ranges are multiples of 64");
+        unsigned lane_blocks = range_blocks(nq, lane_range, 1u << 20);
+        // (tests: GDX_SEED_LANE_BLOCKS caps the grid, so that a block takes several ranges -- its parked queue and
+        // its tile sums then cross range borders, which a grid of one block per range never shows)
+        if (lane_blocks_cap > 0 && static_cast<unsigned long>(lane_blocks_cap) < lane_blocks) lane_blocks = static_cast<unsigned>(lane_blocks_cap);
+        st.zs.flush(stream);
+        if (lane_kernel) {
+            with_int<2, 1>(s.xlate, [&](auto X) {
+                constexpr int kX = decltype(X)::value;
+                with_bool(ulen != 0u, [&](auto U) {
+                    hipLaunchKernelGGL((search_seed_lane_kernel<kX, decltype(U)::value>), dim3(lane_blocks), dim3(kBlock), a.lds, stream,
+                                       a.sv, c.d_qbuf, c.d_qbeg, c.d_qend, nq, c.d_count, c.d_status, c.d_rec, lane_range, a.first + 4,
+                                       a.first, a.state, a.compact, a.lng + 4, a.lng, a.long_state, a.long_stride, a.state_packed, ulen, fold);
+                });
+                launch_seed_text<kX, false>(a);
+            });
+        } else {
+            with_xlate(s.xlate, [&](auto X) { launch_seed_and_text<decltype(X)::value, false>(a); });
+        }
+        st.compact_by_seed = true;
+        if (to_fast) {
+            st.seed_list = a.first;
+            return;
+        }
+        // (the list's length is only known on the device: a grid the chip holds at once strides over whatever
+        // there is; 8192 blocks of this kernel's 12 KB of LDS took 13 us to dispatch and leave when the list
+        // was empty -- on a text without repeats it nearly is)
+        if (to_verify_with_state) st.ca.resume_state = a.state;  // (the seed kernel's states for the verify kernel over its list)
+        launch_verify<true>(short_list_grid(nq, k.seed_list_blocks), d_left, a.first, to_verify_with_state ? a.state : nullptr,
+                            to_verify_with_state ? 1u : 0u);
+    }
+
+    // (a) Count / locate searches on an index with text units: the seed chain above, or -- no seed table, no jump table -- top
+    // table, then the rest of the query against the text at SA[row] (search_verify_kernel4); what they cannot finish is listed
+    // for the general kernel of the index (pair lines or rank lines).  QueryOptions::search_fast = 0 switches the verify kernel
+    // off like the other fast path.
+    void front()
+    {
         const bool clean_call = c.mode == 1 && ix.layout == 0 && ix.text_units != nullptr && ix.n_searchable >= 4 &&
                                 c.d_step_stats == nullptr && c.d_hint == nullptr && c.d_start == nullptr &&
-                                c.d_end == nullptr && ca.active_in == nullptr && nq < 0xffffffffull;
+                                c.d_end == nullptr && st.ca.active_in == nullptr && nq < 0xffffffffull;
         // (a configured lookup table deeper than the seed keeps its own check of the symbols between the two depths, as
         // with the top table below)
-        const bool seed = clean_call && ix.seed != nullptr && ix.seed_k >= static_cast<uint32_t>(ix.depth) &&
-                          (env_seed >= 0 ? env_seed != 0 : qo.search_seed != 0);
+        const bool seed = clean_call && ix.seed != nullptr && ix.seed_k >= static_cast<uint32_t>(ix.depth) && s.seed;
         const bool verify = !seed && clean_call && ix.top != nullptr && ix.top_depth >= 1u && ix.jump == nullptr &&
-                            ix.top_depth >= static_cast<uint32_t>(ix.depth) &&
-                            (env_fast_v >= 0 ? env_fast_v != 0 : qo.search_fast != 0);
-        if (seed || verify) {
-            uint64_t per_block = (nq + 1791) / 1792;
-            per_block = (per_block + 63) / 64 * 64;
-            const uint32_t v_range = static_cast<uint32_t>(per_block > kMaxRange ? kMaxRange : per_block);
-            const uint64_t v_ranges = (nq + v_range - 1) / v_range;
-            const unsigned v_blocks = static_cast<unsigned>(v_ranges < (1u << 20) ? v_ranges : (1u << 20));
-            uint32_t *d_left = static_cast<uint32_t *>(stream_scratch(stream, 11, (nq + 4) * sizeof(uint32_t)));
-            zs.add(d_left, sizeof(uint32_t));
-            // rows a verify round takes: four when SA[row] is one fetch away, one when it costs a locate walk
-            const bool entry_sa = ix.jump != nullptr && ix.jump_bytes == 32;
-            const uint32_t max_rows = (ix.sa_full != nullptr || entry_sa) ? 4u : 1u;
-            const VerifyView vv{ix.top, ix.text_units, ix.sa_full, entry_sa ? ix.jump : nullptr, ix.lines, ix.sb_offsets, ix.count,
-                                ix.sa_samples, ix.border_keys, ix.border_vals, ix.io_to_dense, ix.top_depth, ix.n, ix.n_texts,
-                                ix.sa_inv, ix.sa_rot, ix.sa_limit, max_rows, ix.perm_code_lo, ix.perm_code_hi, ix.perm_exp_lo,
-                                ix.perm_exp_hi, ix.perm_mask, ix.seed, ix.seed_buckets, ix.seed_k, ix.seed_tag_bits, ix.seed_pairs, ix.seed_quads};
-            static const bool env_no_perm_v = getenv("GDX_SEARCH_NO_PERM") != nullptr;
-            // how the kernels get 2-bit codes: 2 = the buffer holds them (packed queries), 1 = v_perm tables, 0 = the table in LDS
-            const int xlate = c.packed ? 2 : ((ix.perm_ok && !env_no_perm_v) ? 1 : 0);
-#define GDX_VERIFY_LAUNCH_X(XLATE, SEED, BLOCKS, RANGE, LEFT, LIST)                                                           \
-    hipLaunchKernelGGL((search_verify_kernel4<XLATE, SEED>), dim3(BLOCKS), dim3(kBlock), 0, stream, vv, c.d_qbuf, c.d_qbeg,    \
-                       c.d_qend, nq, c.d_count, c.d_status, c.d_rec, RANGE, (LEFT) + 4, LEFT, (LIST) ? (LIST) + 4 : nullptr, LIST, ulen, \
-                       verify_state, verify_wide, verify_state != nullptr ? seed_state_packed : 0u)
-#define GDX_VERIFY_LAUNCH(SEED, BLOCKS, RANGE, LEFT, LIST)                             \
-    do {                                                                               \
-        if (xlate == 2) GDX_VERIFY_LAUNCH_X(2, SEED, BLOCKS, RANGE, LEFT, LIST);       \
-        else if (xlate == 1) GDX_VERIFY_LAUNCH_X(1, SEED, BLOCKS, RANGE, LEFT, LIST);  \
-        else GDX_VERIFY_LAUNCH_X(0, SEED, BLOCKS, RANGE, LEFT, LIST);                  \
-    } while (0)
-            uint32_t *const no_list = nullptr;
-            const uint4 *verify_state = nullptr;  // (set below: the seed kernel's states for the verify kernel over its list)
-            uint32_t verify_wide = 0;
-            if (seed) {
-                // the seed table's own kernel first (absent k-mers and k-mers that occur once); what it lists -- k-mers on
-                // several rows, reads shorter than the seed, other symbols -- goes on in search_fast_kernel4 from the entry's
-                // interval when the index has top and jump tables (one jump round for the rest of a read from a repeat),
-                // else through the seed-aware verify kernel; their leftovers go to the general kernel.  The lists' lengths
-                // are only known on the device: small ranges, a capped grid that strides over whatever there is.
-                static const int env_lean = [] { const char *e = getenv("GDX_SEARCH_SEED_LEAN"); return e ? atoi(e) : 1; }();
-                static const int env_chain = [] { const char *e = getenv("GDX_SEARCH_SEED_CHAIN"); return e ? atoi(e) : 1; }();
-                // (to_fast implies every condition of `fast` below)
-                const bool to_fast = env_lean != 0 && env_chain != 0 && variant == 2 && ix.pair_lines != nullptr && ix.top != nullptr &&
-                                     ix.top_depth >= 1u && ix.jump != nullptr && ix.top_depth >= static_cast<uint32_t>(ix.depth) &&
-                                     lanes == 4 && policy == 0 && (env_fast_v >= 0 ? env_fast_v != 0 : qo.search_fast != 0);
-                static const int env_packed = [] { const char *e = getenv("GDX_SEARCH_SEED_PACKED"); return e ? atoi(e) : 1; }();
-                // (... or the verify kernel's, which hands the plain form on to the general kernel: to_verify_with_state below)
-                const bool to_verify_packed = !to_fast && variant == 2 && ix.pair_lines != nullptr && env_lean != 0;
-                seed_state_packed = (to_fast || to_verify_packed) && c.d_rec != nullptr && env_packed != 0 ? 1u : 0u;
-                // (2: states of two-copy repeats name their record in IndexView::seed_pairs -- only the verify kernel reads those)
-                const char *env_pairs = getenv("GDX_SEARCH_SEED_PAIRS");  // (0: the A/B; read per call, a test switches it)
-                if (seed_state_packed != 0u && !to_fast && (ix.seed_pairs != nullptr || ix.seed_quads != nullptr) && !(env_pairs != nullptr && atoi(env_pairs) == 0))
-                    seed_state_packed = 2u;
-                if (env_lean != 0) {
-                    uint32_t *d_first = static_cast<uint32_t *>(stream_scratch(stream, 12, (nq + 4) * sizeof(uint32_t)));
-                    zs.add(d_first, sizeof(uint32_t));
-                    const SeedView sv{ix.seed, ix.text_units, nullptr, ix.io_to_dense, ix.seed_buckets, ix.seed_k, ix.seed_tag_bits,
-                                      ix.perm_code_lo, ix.perm_code_hi, ix.perm_exp_lo, ix.perm_exp_hi, ix.perm_mask};
-                    // (the pair-line general kernel resumes listed reads from their k-mer's interval as well: the verify kernel in
-                    // between takes the narrow ones and leaves the wide ones to it)
-                    const bool to_verify_with_state = !to_fast && variant == 2 && ix.pair_lines != nullptr && c.d_rec != nullptr;
-                    uint4 *d_seed_state = (to_fast || to_verify_with_state) ? c.d_rec : nullptr;
-                    uint32_t *const none = nullptr;
-                    // reads longer than a seed entry covers: listed with {position, symbols in front} in the first half of their
-                    // record slot (an array of its own when the call has no records) for seed_text_kernel4, whose own
-                    // leftovers (a symbol outside A C G T further front) join the seed kernel's list
-                    uint32_t *d_long = static_cast<uint32_t *>(stream_scratch(stream, 13, (nq + 4) * sizeof(uint32_t)));
-                    zs.add(d_long, sizeof(uint32_t));
-                    uint2 *d_long_state = c.d_rec != nullptr ? reinterpret_cast<uint2 *>(c.d_rec)
-                                                             : static_cast<uint2 *>(stream_scratch(stream, 14, nq * sizeof(uint2)));
-                    const uint32_t long_stride = c.d_rec != nullptr ? 2u : 1u;
-                    const uint64_t t_groups = (nq + kBlock / 4 - 1) / (kBlock / 4);
-                    const unsigned t_blocks = static_cast<unsigned>(t_groups < 8192 ? t_groups : 8192);
-                    // (experiments: GDX_SEED_PAD = dynamic LDS bytes per block, which caps the resident blocks per CU)
-                    static const unsigned seed_pad = [] { const char *e = getenv("GDX_SEED_PAD"); return e ? static_cast<unsigned>(atol(e)) : 0u; }();
-#define GDX_SEED_LAUNCH(XLATE)                                                                                                  \
-    do {                                                                                                                       \
-        hipLaunchKernelGGL((search_seed_kernel4<XLATE, false>), dim3(v_blocks), dim3(kBlock), seed_pad, stream, sv, c.d_qbuf,  \
-                           c.d_qbeg, c.d_qend, nq, c.d_count, c.d_status, c.d_rec, none, none, v_range, d_first + 4,          \
-                           d_first, d_seed_state, c.d_compact, d_long + 4, d_long, d_long_state, long_stride,                 \
-                           seed_state_packed, ulen, CursorArgs());                                                             \
-        hipLaunchKernelGGL((seed_text_kernel4<XLATE, false>), dim3(t_blocks), dim3(kBlock), 0, stream, sv, c.d_qbuf, c.d_qbeg, \
-                           d_long + 4, d_long, d_long_state, long_stride, c.d_count, c.d_status, c.d_rec, none, none,         \
-                           c.d_compact, d_seed_state, d_first + 4, d_first, ulen);                                            \
-    } while (0)
-                    // one lane per read (search_seed_lane_kernel) where its loads apply: 2-bit codes or v_perm tables, k <= 24, a
-                    // dword-aligned buffer; GDX_SEED_LANE=0: the four-lane kernel
-                    static const int env_lane = [] { const char *e = getenv("GDX_SEED_LANE"); return e ? atoi(e) : 1; }();
-                    const bool lane_kernel = env_lane != 0 && xlate != 0 && ix.seed_k <= 24u && ix.seed_k >= 8u &&
-                                             (reinterpret_cast<uintptr_t>(c.d_qbuf) & 3u) == 0;
-                    // the locate's hit totals folded into this call (SearchCall::d_tile_sums): the lane kernel counts what it
-                    // answers, tile_sums_lists_kernel adds its two lists once the whole chain has run (finish_fold below)
-                    unsigned long long *fold = nullptr;
-                    if (lane_kernel && c.d_tile_sums != nullptr && c.d_tile_rest != nullptr && c.d_compact != nullptr) {
-                        fold = c.d_tile_sums;
-                        zs.add(fold, ((nq + kSumTile - 1) / kSumTile) * sizeof(unsigned long long));
-                        fold_left = d_first;
-                        fold_long = d_long;
-                    }
-                    // (its ranges: at most kLaneRange reads, the capacity of its lists in LDS)
-                    // (experiments: GDX_SEED_LANE_RANGE = reads per range, a multiple of 64 up to kLaneRange)
-                    static const uint32_t env_lane_range = [] { const char *e = getenv("GDX_SEED_LANE_RANGE"); return e ? static_cast<uint32_t>(atol(e)) : 0u; }();
-                    const uint32_t lane_range = env_lane_range >= 64u && env_lane_range <= kLaneRange ? env_lane_range / 64u * 64u
-                                                : (v_range < kLaneRange ? v_range : kLaneRange);
-                    if (lane_range % 64u != 0u) fail(GDX_ERR_INVALID_ARGUMENT, "internal: the lane kernel's ranges are multiples of 64");
-                    const uint64_t lane_ranges = (nq + lane_range - 1) / lane_range;
-                    unsigned lane_blocks = static_cast<unsigned>(lane_ranges < (1u << 20) ? lane_ranges : (1u << 20));
-                    // (tests: GDX_SEED_LANE_BLOCKS caps the grid, so that a block takes several ranges -- its parked queue and
-                    // its tile sums then cross range borders, which a grid of one block per range never shows; read per call)
-                    if (const char *e = getenv("GDX_SEED_LANE_BLOCKS")) {
-                        const long cap = atol(e);
-                        if (cap > 0 && static_cast<unsigned long>(cap) < lane_blocks) lane_blocks = static_cast<unsigned>(cap);
-                    }
-#define GDX_SEED_LANE_LAUNCH(XLATE, UNIFORM)                                                                                    \
-    do {                                                                                                                       \
-        hipLaunchKernelGGL((search_seed_lane_kernel<XLATE, UNIFORM>), dim3(lane_blocks), dim3(kBlock), seed_pad, stream, sv,   \
-                           c.d_qbuf, c.d_qbeg, c.d_qend, nq, c.d_count, c.d_status, c.d_rec, lane_range, d_first + 4, d_first, \
-                           d_seed_state, c.d_compact, d_long + 4, d_long, d_long_state, long_stride, seed_state_packed, ulen,   \
-                           fold);                                                                                              \
-        hipLaunchKernelGGL((seed_text_kernel4<XLATE, false>), dim3(t_blocks), dim3(kBlock), 0, stream, sv, c.d_qbuf, c.d_qbeg, \
-                           d_long + 4, d_long, d_long_state, long_stride, c.d_count, c.d_status, c.d_rec, none, none,         \
-                           c.d_compact, d_seed_state, d_first + 4, d_first, ulen);                                            \
-    } while (0)
-                    zs.flush(stream);
-                    if (lane_kernel && xlate == 2 && ulen != 0u) GDX_SEED_LANE_LAUNCH(2, true);
-                    else if (lane_kernel && xlate == 2) GDX_SEED_LANE_LAUNCH(2, false);
-                    else if (lane_kernel && ulen != 0u) GDX_SEED_LANE_LAUNCH(1, true);
-                    else if (lane_kernel) GDX_SEED_LANE_LAUNCH(1, false);
-                    else if (xlate == 2) GDX_SEED_LAUNCH(2);
-                    else if (xlate == 1) GDX_SEED_LAUNCH(1);
-                    else GDX_SEED_LAUNCH(0);
-#undef GDX_SEED_LANE_LAUNCH
-#undef GDX_SEED_LAUNCH
-                    compact_by_seed = true;
-                    if (to_fast) {
-                        seed_list = d_first;
-                    } else {
-                        // (the list's length is only known on the device: a grid the chip holds at once strides over whatever
-                        // there is; 8192 blocks of this kernel's 12 KB of LDS took 13 us to dispatch and leave when the list
-                        // was empty -- on a text without repeats it nearly is)
-                        const uint32_t l_range = 256;
-                        const uint64_t l_ranges = (nq + l_range - 1) / l_range;
-                        static const unsigned l_cap = [] { const char *e = getenv("GDX_SEED_LIST_BLOCKS"); return e ? static_cast<unsigned>(atol(e)) : 1792u; }();
-                        const unsigned l_blocks = static_cast<unsigned>(l_ranges < l_cap ? l_ranges : l_cap);
-                        if (to_verify_with_state) {
-                            verify_state = d_seed_state;
-                            verify_wide = 1u;
-                            ca.resume_state = d_seed_state;
-                        }
-                        GDX_VERIFY_LAUNCH(true, l_blocks, l_range, d_left, d_first);
-                    }
-                } else {
-                    zs.flush(stream);
-                    GDX_VERIFY_LAUNCH(true, v_blocks, v_range, d_left, no_list);
-                }
-            } else {
-                zs.flush(stream);
-                GDX_VERIFY_LAUNCH(false, v_blocks, v_range, d_left, no_list);
-            }
-#undef GDX_VERIFY_LAUNCH
-#undef GDX_VERIFY_LAUNCH_X
-            static const bool env_stats_v = getenv("GDX_SEARCH_FAST_STATS") != nullptr;  // debug: size of the leftover list
-            if (env_stats_v) {
-                uint32_t n_left = 0;
-                GDX_HIP(hipMemcpyAsync(&n_left, seed_list ? seed_list : d_left, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-                GDX_HIP(hipStreamSynchronize(stream));
-                fprintf(stderr, "gdx: %s path left %u of %llu queries to the next kernel\n", seed ? "seed" : "verify", n_left,
-                        static_cast<unsigned long long>(nq));
-            }
-            ca.active_in = (seed_list ? seed_list : d_left) + 4;
-            ca.n_active_in = seed_list ? seed_list : d_left;
-            leftover_list = true;
-        }
-    }
-    zs.flush(stream);  // (a call that took none of the paths above: what the caller wanted zeroed)
-    // a uniform batch in front of the pair-line kernels, which read offsets: those of the whole batch (8 bytes per query, one
-    // streaming pass), or -- behind the seed chain -- of the listed queries only, written before each kernel that takes a list
-    bool sparse_offsets = false;
-    if (pair_offsets && c.mode == 1) {
-        if (leftover_list) {
-            d_uniform_off = static_cast<uint64_t *>(stream_scratch(stream, 15, (nq + 1) * sizeof(uint64_t)));
-            c.d_qbeg = d_uniform_off;
-            c.d_qend = d_uniform_off + 1;
-            c.uniform_len = 0;
-            sparse_offsets = true;
+                            ix.top_depth >= static_cast<uint32_t>(ix.depth) && s.fast != 0;
+        if (!seed && !verify) return;
+        const ListGrid v_grid = range_grid(nq, kMaxRange, 0);
+        uint32_t *d_left = counted_list(11, &st.zs);
+        if (seed) {
+            seed_front(v_grid, d_left);
         } else {
-            dense_uniform_offsets();
+            st.zs.flush(stream);
+            launch_verify<false>(v_grid, d_left, nullptr, nullptr, 0u);
         }
+        uint32_t *next = st.seed_list ? st.seed_list : d_left;
+        if (k.fast_stats) print_left(seed ? "seed" : "verify", next, "next");
+        st.ca.active_in = next + 4;
+        st.ca.n_active_in = next;
+        st.leftover_list = true;
     }
-    auto offsets_for_list = [&](const uint32_t *list, const uint32_t *n_list) {
-        if (sparse_offsets && list != nullptr)
-            hipLaunchKernelGGL(fill_uniform_offsets_list_kernel, dim3(1024), dim3(kBlock), 0, stream, d_uniform_off, list, n_list, ulen);
-    };
-    auto finish_fold = [&] {
-        if (fold_left == nullptr) return;
-        // (the lists' lengths are only known on the device: a capped grid that strides over whatever there is)
-        hipLaunchKernelGGL(tile_sums_lists_kernel, dim3(4096), dim3(kBlock), 0, stream, c.d_rec, c.d_compact, c.tile_max_hits,
-                           fold_left + 4, fold_left, fold_long + 4, fold_long, c.d_tile_sums, c.d_tile_rest);
-        if (c.tile_sums_done != nullptr) *c.tile_sums_done = true;
-    };
-    // compact results without the seed kernel: every query says "see the record"
-    if (c.d_compact != nullptr && !compact_by_seed) GDX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.d_compact), static_cast<int>(kCompactSee), nq, stream));
-    if (ix.layout == 0 && variant == 2 && ix.pair_lines != nullptr) {
-        // Every block searches contiguous ranges of `range` queries (a multiple of 64, at most kMaxRange): about
-        // 48 rounds per group at large batches, 1792+ blocks at small ones; GDX_SEARCH_GRID = number of blocks.
-        uint64_t per_block = (nq + 1791) / 1792;
-        per_block = (per_block + 63) / 64 * 64;
-        const uint32_t range_cap = c.mode == 2 ? kCursorRange : kMaxRange;
-        const uint32_t range = static_cast<uint32_t>(per_block > range_cap ? range_cap : per_block);
-        const uint64_t n_ranges = (nq + range - 1) / range;
-        const unsigned blocks = grid_override > 0 ? static_cast<unsigned>(grid_override)
-                                                  : static_cast<unsigned>(n_ranges < (1u << 20) ? n_ranges : (1u << 20));
+
+    // (b) Uniform batches (SearchCall::uniform_len): the seed chain and the rank-line kernels compute where a query lies; the
+    // pair-line kernels read offsets, which are then written once into scratch (8 bytes per query, one streaming pass) or --
+    // sparse: behind the seed chain -- of the listed queries only, before each kernel that takes a list (offsets_for_list)
+    void uniform_offsets(bool sparse)
+    {
+        st.d_uniform_off = static_cast<uint64_t *>(stream_scratch(stream, 15, (nq + 1) * sizeof(uint64_t)));
+        if (!sparse)
+            hipLaunchKernelGGL(fill_uniform_offsets_kernel, dim3(grid_for_items(nq + 1)), dim3(kBlock), 0, stream, st.d_uniform_off,
+                               nq + 1, c.uniform_len);
+        c.d_qbeg = st.d_uniform_off;
+        c.d_qend = st.d_uniform_off + 1;
+        c.uniform_len = 0;
+        st.sparse_offsets = sparse;
+    }
+    void offsets_for_list(const uint32_t *list, const uint32_t *n_list)
+    {
+        if (st.sparse_offsets && list != nullptr)
+            hipLaunchKernelGGL(fill_uniform_offsets_list_kernel, dim3(1024), dim3(kBlock), 0, stream, st.d_uniform_off, list, n_list, ulen);
+    }
+
+    // (c) Exact intervals on an index with seed table and inverse suffix array: the seed kernel answers the reads that occur
+    // exactly once through their seed (interval = the row ISA[position]); the exact kernel then goes over its list.
+    void pair_seed_exact()
+    {
+        SeedLaunch a{seed_view(ix, ix.isa), st.all};
+        a.first = counted_list(12, nullptr);
+        a.start = c.d_start;
+        a.end = c.d_end;
+        a.lng = counted_list(13, nullptr);
+        with_xlate(s.xlate, [&](auto X) { launch_seed_and_text<decltype(X)::value, true>(a); });
+        st.ca_exact.active_in = a.first + 4;
+        st.ca_exact.n_active_in = a.first;
+        st.exact = short_list_grid(nq);
+    }
+    // (c) The first chunk of a batch of cursors on an index with seed table and text route: the seed kernel's pipeline serves the
+    // cursors that are still cursor_empty and lists the others for the exact kernel (search_seed_kernel4<., true, true>).
+    void pair_seed_cursor()
+    {
+        uint32_t *d_first = counted_list(12, nullptr);
+        SeedView sv = seed_view(ix, ix.isa);
+        sv.n = ix.n;
+        with_int<1, 0>(s.perm ? 1 : 0, [&](auto X) {
+            hipLaunchKernelGGL((search_seed_kernel4<decltype(X)::value, true, true>), dim3(st.all.blocks), dim3(kBlock), 0, stream, sv,
+                               c.d_qbuf, c.d_qbeg, c.d_qend, nq, c.d_count, c.d_status, nullptr, c.d_start, c.d_end, st.all.range,
+                               d_first + 4, d_first, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u, 0u, st.ca);
+        });
+        st.ca_exact.active_in = d_first + 4;
+        st.ca_exact.n_active_in = d_first;
+        st.exact = short_list_grid(nq);
+    }
+    // (c) Exact intervals and cursor extension on clean input (search_exact_kernel4): what it cannot finish is listed for
+    // the general kernel.
+    // (2-bit reads: exact intervals through the text route's kernel and the seed kernel in front of it -- round 6; the
+    // general packed kernel steps every symbol on the pair lines of an index without jump table: 4.5 ms per 10 M reads
+    // against 0.8)
+    void pair_exact(bool seed_in_kernel)
+    {
+        uint32_t *d_left = counted_list(11, nullptr);
+        const ExactView ev = exact_view(ix, seed_in_kernel);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(st.exact.blocks), dim3(kBlock), 0, stream, ev, c.d_qbuf, c.d_qbeg, c.d_qend, nq, c.d_start,
+                               c.d_end, c.d_count, c.d_status, st.exact.range, s.schedule, d_left + 4, d_left, st.ca_exact);
+        };
+        if (s.text_route && c.packed) launch(search_exact_kernel4<0, 2, false, true>);
+        else
+            with_bool(c.mode == 2, [&](auto C) {
+                constexpr bool kCursor = decltype(C)::value;
+                with_int<1, 0>(s.perm ? 1 : 0, [&](auto X) {
+                    constexpr int kX = decltype(X)::value;
+                    if (s.text_route) launch(search_exact_kernel4<0, kX, kCursor, true>);
+                    else if (ix.jump == nullptr) launch(search_exact_kernel4<0, kX, kCursor>);
+                    else with_jump_bytes(ix.jump_bytes, [&](auto J) { launch(search_exact_kernel4<decltype(J)::value, kX, kCursor>); });
+                });
+            });
+        st.general = short_list_grid(nq);
+        st.ca_general.active_in = d_left + 4;  // the general kernel goes over the leftover list
+        st.ca_general.n_active_in = d_left;
+    }
+    // (c) Fast path (search_fast_kernel4): count / locate mode on an index with top and jump tables.  It finishes
+    // what needs no pair line (intervals of up to sixteen rows) and lists the rest, which the general kernel --
+    // with the straggler pass when the index asks for it -- takes up from the list where the fast path stopped.
+    void pair_fast()
+    {
+        // the leftover list is short (0.3 % of the reads of a non-repetitive text) and its length is only known on
+        // the device: small ranges spread it over the chip, a capped grid strides over whatever there is
+        st.general = short_list_grid(nq);
+        uint32_t *d_left = counted_list(11, nullptr);
+        // where a leftover query stands is kept in its record slot; a call without records (counts only) lets the
+        // general kernel start its few leftovers over rather than allocate 16 bytes per query for them
+        uint4 *d_state = c.d_rec;
+        const FastView fv = fast_view(ix);
+        // (after the seed kernel: over its list -- small ranges, a capped grid, as for the general kernel's lists)
+        uint32_t *seed_list = st.seed_list;
+        const ListGrid f_grid = seed_list ? st.general : st.all;
+        const uint32_t *f_list = seed_list ? seed_list + 4 : nullptr;
+        if (seed_list != nullptr) offsets_for_list(seed_list + 4, seed_list);
+        with_jump_bytes(ix.jump_bytes, [&](auto J) {
+            constexpr int kJ = decltype(J)::value;
+            with_xlate(s.xlate, [&](auto X) {
+                constexpr int kX = decltype(X)::value;
+                with_bool(s.fast == 2, [&](auto W) {  // sixteen-row rounds where reads from repeats are common
+                    hipLaunchKernelGGL((search_fast_kernel4<kJ, kX, decltype(W)::value>), dim3(f_grid.blocks), dim3(kBlock), 0, stream, fv,
+                                       c.d_qbuf, c.d_qbeg, c.d_qend, nq, c.d_count, c.d_status, c.d_rec, f_grid.range, d_left + 4, d_left,
+                                       d_state, f_list, seed_list, seed_list ? st.seed_state_packed : 0u);
+                });
+            });
+        });
+        if (k.fast_stats) print_left("fast", d_left, "general");
+        st.ca_general.active_in = d_left + 4;  // the general kernel searches the leftover list
+        st.ca_general.n_active_in = d_left;
+        st.ca_general.resume_state = d_state;
+    }
+    // (c) the general pair-line kernel of the call: packed, accounting, with the straggler pass, or plain
+    void pair_general()
+    {
+        const bool lanes8 = s.lanes == 8;
+        auto launch = [&](void (*kernel)(GDX_SEARCH_ARGS)) {
+            hipLaunchKernelGGL(kernel, dim3(st.general.blocks), dim3(kBlock), k.pad, stream, ix, c.d_qbuf, c.d_qbeg, c.d_qend, nq,
+                               c.d_start, c.d_end, c.d_count, c.d_status, c.d_step_stats, st.general.range, s.schedule, c.d_hint,
+                               c.d_rec, st.ca_general, s.defer_after);
+        };
+        with_jump_bytes(ix.jump_bytes, [&](auto J) {
+            constexpr int kJ = decltype(J)::value;
+            if (c.packed) {
+                with_int<0, 1>(c.mode, [&](auto M) { launch(search_pair_packed_kernel4<kJ, decltype(M)::value>); });
+            } else if (c.d_step_stats != nullptr) {  // accounting: always the exact mode (the reference's LF steps)
+                launch(lanes8 ? search_pair_stats_kernel8<0, kJ, 0> : search_pair_stats_kernel4<0, kJ, 0>);
+            } else if (s.defer_after != 0u && c.mode != 2) {
+                // (6 waves per SIMD / 80 VGPRs halve its 14 spills and change nothing: 14.25 vs 14.36 ms)
+                with_int<0, 1>(c.mode, [&](auto M) {
+                    constexpr int kM = decltype(M)::value;
+                    launch(lanes8 ? search_pair_defer_kernel8<0, kJ, kM> : search_pair_defer_kernel4<0, kJ, kM>);
+                });
+            } else {
+                with_int<0, 1>(s.policy, [&](auto P) {
+                    constexpr int kP = decltype(P)::value;
+                    with_int<0, 1, 2>(c.mode, [&](auto M) {
+                        constexpr int kM = decltype(M)::value;
+                        launch(lanes8 ? search_pair_kernel8<kP, kJ, kM> : search_pair_kernel4<kP, kJ, kM>);
+                    });
+                });
+            }
+        });
+    }
+    // (c) the pair-line path: seed-exact, seed-cursor, exact, fast, then the general kernel over what they left
+    void pair_lines()
+    {
+        const CursorArgs &ca = st.ca;
         // Cache policy of the line / entry loads: plain by default.  sc1 (no allocation in the CU's L1) was worth
         // +5 % while the first levels of the search were cache-resident pair lines; with the top table every load
         // is a DRAM miss and plain loads measure 3 % faster.  QueryOptions::load_policy / GDX_LOAD_POLICY=0|1.
-        // (resolved above the seed block)
-        // Ranges whose query lengths are spread out are searched in length order (order_range_by_length);
-        // QueryOptions::length_schedule / GDX_SEARCH_SCHEDULE=0 keeps the query order.
-        static const int env_schedule = [] {
-            const char *e = getenv("GDX_SEARCH_SCHEDULE");
-            return (e && e[0] == '0') ? 0 : 1;
-        }();
-        const int schedule = qo.length_schedule >= 0 ? (qo.length_schedule != 0) : env_schedule;
-        // Stragglers are parked after their allowance + defer_after load rounds and finished together
-        // (search_pair_body); QueryOptions::search_defer_after (resolved per index by FmIndex::query_options: on when
-        // the text is repetitive) / GDX_SEARCH_DEFER; 0 = never.  The accounting kernels never park (their per-query
-        // round counts describe the plain lock-step schedule).
-        static const int env_defer = [] {
-            const char *e = getenv("GDX_SEARCH_DEFER");
-            return e ? atoi(e) : 0;
-        }();
-        const uint32_t defer_after = c.d_step_stats != nullptr ? 0u
-                                     : static_cast<uint32_t>(qo.search_defer_after >= 0 ? qo.search_defer_after : env_defer);
-#define GDX_PAIR_LAUNCH(KERNEL)                                                                                     \
-    hipLaunchKernelGGL(KERNEL, dim3(g_blocks), dim3(kBlock), lds_pad, stream, ix, c.d_qbuf, c.d_qbeg, c.d_qend, nq, \
-                       c.d_start, c.d_end, c.d_count, c.d_status, c.d_step_stats, g_range, schedule, c.d_hint,      \
-                       c.d_rec, ca_general, defer_after)
-#define GDX_PAIR_LAUNCH_W(KERNEL, P, M)                                    \
-    do {                                                                   \
-        if (ix.jump_bytes == 32) GDX_PAIR_LAUNCH((KERNEL<P, 32, M>));      \
-        else if (ix.jump_bytes == 16) GDX_PAIR_LAUNCH((KERNEL<P, 16, M>)); \
-        else GDX_PAIR_LAUNCH((KERNEL<P, 8, M>));                           \
-    } while (0)
-#define GDX_PAIR_LAUNCH_M(KERNEL, P)                      \
-    do {                                                  \
-        if (c.mode == 0) GDX_PAIR_LAUNCH_W(KERNEL, P, 0); \
-        else if (c.mode == 1) GDX_PAIR_LAUNCH_W(KERNEL, P, 1); \
-        else GDX_PAIR_LAUNCH_W(KERNEL, P, 2);             \
-    } while (0)
-        // Fast path (search_fast_kernel4): count / locate mode on an index with top and jump tables.  It finishes
-        // what needs no pair line (intervals of up to sixteen rows) and lists the rest, which the general kernel --
-        // with the straggler pass when the index asks for it -- takes up from the list where the fast path stopped.
-        // QueryOptions::search_fast / GDX_SEARCH_FAST=0 switch it off.
-        // (qo.search_fast arrives resolved by FmIndex::query_options; the environment variable is a debug override)
-        static const int env_fast = [] { const char *e = getenv("GDX_SEARCH_FAST"); return e ? atoi(e) : -1; }();
-        const bool fast = c.mode == 1 && c.d_step_stats == nullptr && lanes == 4 && policy == 0 &&
+        const bool lanes4_plain = s.lanes == 4 && s.policy == 0;
+        st.all = range_grid(nq, c.mode == 2 ? kCursorRange : kMaxRange, k.grid);
+        // QueryOptions::search_fast / GDX_SEARCH_FAST=0 switch the fast path off.
+        const bool fast = c.mode == 1 && c.d_step_stats == nullptr && lanes4_plain &&
                           ix.top != nullptr && ix.top_depth >= 1u && ix.jump != nullptr &&
                           // the guards of the general kernel's top-table step (search_pair_body): dense 1..4 must all be
                           // searchable, and a configured lookup table deeper than the top table keeps its own check of
                           // the symbols between the two depths (a valid but unsearchable symbol there is an error, not a
                           // step) -- a leftover resumed after the top table would skip it
                           ix.n_searchable >= 4 && ix.top_depth >= static_cast<uint32_t>(ix.depth) &&
-                          (ca.active_in == nullptr || seed_list != nullptr) && c.d_hint == nullptr && c.d_start == nullptr &&
-                          c.d_end == nullptr && (env_fast >= 0 ? env_fast != 0 : qo.search_fast != 0) && nq < 0xffffffffull;
-        CursorArgs ca_general = ca;
-        if (seed_list != nullptr && !fast) fail(GDX_ERR_INVALID_ARGUMENT, "internal: the seed kernel's list without the fast kernel");
-        unsigned g_blocks = blocks;  // grid and range size of the general kernel
-        uint32_t g_range = range;
-        if (leftover_list) {  // short, and its length is only known on the device: small ranges, a capped grid
-            g_range = 256;
-            const uint64_t g_ranges = (nq + g_range - 1) / g_range;
-            g_blocks = static_cast<unsigned>(g_ranges < 8192 ? g_ranges : 8192);
-        }
-        // Exact intervals and cursor extension on clean input (search_exact_kernel4): what it cannot finish is listed for
-        // the general kernel below.  QueryOptions::search_exact / GDX_SEARCH_EXACT=0 switch it off.
-        static const int env_exact = [] { const char *e = getenv("GDX_SEARCH_EXACT"); return e ? atoi(e) : -1; }();
-        // (2-bit reads: exact intervals through the text route's kernel and the seed kernel in front of it -- round 6; the
-        // general packed kernel steps every symbol on the pair lines of an index without jump table: 4.5 ms per 10 M reads
-        // against 0.8)
-        // the text route in the jump table's place (search_exact_kernel4<0, ., ., true>); GDX_SEARCH_TEXT=0: pair lines only
-        static const int env_text = [] { const char *e = getenv("GDX_SEARCH_TEXT"); return e ? atoi(e) : 1; }();
-        const bool text_route = ix.jump == nullptr && ix.sa_full != nullptr && ix.isa != nullptr && ix.text_units != nullptr &&
-                                env_text != 0;
-        const bool exact = (c.mode == 0 || c.mode == 2) && c.d_step_stats == nullptr && lanes == 4 && policy == 0 &&
-                           (!c.packed || (c.mode == 0 && text_route)) &&
+                          (ca.active_in == nullptr || st.seed_list != nullptr) && c.d_hint == nullptr && c.d_start == nullptr &&
+                          c.d_end == nullptr && s.fast != 0 && nq < 0xffffffffull;
+        if (st.seed_list != nullptr && !fast) fail(GDX_ERR_INVALID_ARGUMENT, "internal: the seed kernel's list without the fast kernel");
+        st.ca_general = ca;
+        st.general = st.leftover_list ? short_list_grid(nq) : st.all;  // grid and range size of the general kernel
+        // QueryOptions::search_exact / GDX_SEARCH_EXACT=0 switch the exact kernel off.
+        const bool exact = (c.mode == 0 || c.mode == 2) && c.d_step_stats == nullptr && lanes4_plain &&
+                           (!c.packed || (c.mode == 0 && s.text_route)) &&
                            c.d_hint == nullptr && c.d_rec == nullptr && c.d_start != nullptr && c.d_end != nullptr &&
                            ix.n_searchable >= 4 && ix.sigma >= 5 && ca.resume_state == nullptr &&
                            (ix.top == nullptr || ix.top_depth >= static_cast<uint32_t>(ix.depth)) &&
-                           (env_exact >= 0 ? env_exact != 0 : qo.search_exact != 0) && (defer_after == 0u || c.mode == 2) &&
-                           nq < 0xffffffffull;
-        // Exact intervals on an index with seed table and inverse suffix array: the seed kernel answers the reads that occur
-        // exactly once through their seed (interval = the row ISA[position]); the exact kernel then goes over its list.
-        static const int env_seed_x = [] { const char *e = getenv("GDX_SEARCH_SEED"); return e ? atoi(e) : -1; }();
+                           s.exact && (s.defer_after == 0u || c.mode == 2) && nq < 0xffffffffull;
+        st.ca_exact = ca;
+        st.exact = st.all;
         const bool seed_exact = exact && c.mode == 0 && ix.seed != nullptr && ix.isa != nullptr && ix.text_units != nullptr &&
-                                ix.seed_k >= static_cast<uint32_t>(ix.depth) && ca.active_in == nullptr &&
-                                (env_seed_x >= 0 ? env_seed_x != 0 : qo.search_seed != 0);
-        CursorArgs ca_exact = ca;
-        unsigned x_blocks = blocks;
-        uint32_t x_range = range;
-        if (seed_exact) {
-            uint32_t *d_first = static_cast<uint32_t *>(stream_scratch(stream, 12, (nq + 4) * sizeof(uint32_t)));
-            GDX_HIP(hipMemsetAsync(d_first, 0, sizeof(uint32_t), stream));
-            const SeedView sv{ix.seed, ix.text_units, ix.isa, ix.io_to_dense, ix.seed_buckets, ix.seed_k, ix.seed_tag_bits,
-                              ix.perm_code_lo, ix.perm_code_hi, ix.perm_exp_lo, ix.perm_exp_hi, ix.perm_mask};
-            static const bool env_no_perm_s = getenv("GDX_SEARCH_NO_PERM") != nullptr;
-            uint4 *const no_rec = nullptr;
-            uint32_t *const none_u32 = nullptr;
-            uint32_t *d_long = static_cast<uint32_t *>(stream_scratch(stream, 13, (nq + 4) * sizeof(uint32_t)));
-            GDX_HIP(hipMemsetAsync(d_long, 0, sizeof(uint32_t), stream));
-            uint2 *const no_state = nullptr;
-            const uint64_t t_groups = (nq + kBlock / 4 - 1) / (kBlock / 4);
-            const unsigned t_blocks = static_cast<unsigned>(t_groups < 8192 ? t_groups : 8192);
-            if (c.packed) {
-                hipLaunchKernelGGL((search_seed_kernel4<2, true>), dim3(blocks), dim3(kBlock), 0, stream, sv, c.d_qbuf, c.d_qbeg,
-                                   c.d_qend, nq, c.d_count, c.d_status, no_rec, c.d_start, c.d_end, range, d_first + 4, d_first, no_rec,
-                                   none_u32, d_long + 4, d_long, no_state, 0u, 0u, ulen, CursorArgs());
-                hipLaunchKernelGGL((seed_text_kernel4<2, true>), dim3(t_blocks), dim3(kBlock), 0, stream, sv, c.d_qbuf, c.d_qbeg,
-                                   d_long + 4, d_long, no_state, 0u, c.d_count, c.d_status, no_rec, c.d_start, c.d_end, none_u32, no_rec,
-                                   d_first + 4, d_first, ulen);
-            } else if (ix.perm_ok && !env_no_perm_s) {
-                hipLaunchKernelGGL((search_seed_kernel4<1, true>), dim3(blocks), dim3(kBlock), 0, stream, sv, c.d_qbuf, c.d_qbeg,
-                                   c.d_qend, nq, c.d_count, c.d_status, no_rec, c.d_start, c.d_end, range, d_first + 4, d_first, no_rec,
-                                   none_u32, d_long + 4, d_long, no_state, 0u, 0u, ulen, CursorArgs());
-                hipLaunchKernelGGL((seed_text_kernel4<1, true>), dim3(t_blocks), dim3(kBlock), 0, stream, sv, c.d_qbuf, c.d_qbeg,
-                                   d_long + 4, d_long, no_state, 0u, c.d_count, c.d_status, no_rec, c.d_start, c.d_end, none_u32, no_rec,
-                                   d_first + 4, d_first, ulen);
-            } else {
-                hipLaunchKernelGGL((search_seed_kernel4<0, true>), dim3(blocks), dim3(kBlock), 0, stream, sv, c.d_qbuf, c.d_qbeg,
-                                   c.d_qend, nq, c.d_count, c.d_status, no_rec, c.d_start, c.d_end, range, d_first + 4, d_first, no_rec,
-                                   none_u32, d_long + 4, d_long, no_state, 0u, 0u, ulen, CursorArgs());
-                hipLaunchKernelGGL((seed_text_kernel4<0, true>), dim3(t_blocks), dim3(kBlock), 0, stream, sv, c.d_qbuf, c.d_qbeg,
-                                   d_long + 4, d_long, no_state, 0u, c.d_count, c.d_status, no_rec, c.d_start, c.d_end, none_u32, no_rec,
-                                   d_first + 4, d_first, ulen);
-            }
-            ca_exact.active_in = d_first + 4;
-            ca_exact.n_active_in = d_first;
-            x_range = 256;
-            const uint64_t x_ranges = (nq + x_range - 1) / x_range;
-            x_blocks = static_cast<unsigned>(x_ranges < 8192 ? x_ranges : 8192);
-        }
+                                ix.seed_k >= static_cast<uint32_t>(ix.depth) && ca.active_in == nullptr && s.seed;
+        if (seed_exact) pair_seed_exact();
         const bool seed_usable = ix.seed != nullptr && ix.seed_k >= static_cast<uint32_t>(ix.depth) && ix.seed_k <= 24u;
-        // The first chunk of a batch of cursors on such an index: the seed kernel's pipeline serves the cursors that are still
-        // cursor_empty and lists the others for the exact kernel (search_seed_kernel4<., true, true>).  "First" is a guess -- a
-        // chunk call with index 0, or a call without a live list: a wrong guess costs a pass, never a result.
-        // GDX_SEARCH_SEED_CURSOR=0: the exact kernel alone.
-        static const int env_seed_cursor = [] { const char *e = getenv("GDX_SEARCH_SEED_CURSOR"); return e ? atoi(e) : 1; }();
-        const bool seed_cursor = exact && c.mode == 2 && text_route && seed_usable && env_seed_cursor != 0 &&
-                                 (env_seed_x >= 0 ? env_seed_x != 0 : qo.search_seed != 0) &&
+        // "First" chunk is a guess -- a chunk call with index 0, or a call without a live list: a wrong guess costs a pass,
+        // never a result.  GDX_SEARCH_SEED_CURSOR=0: the exact kernel alone.
+        const bool seed_cursor = exact && c.mode == 2 && s.text_route && seed_usable && k.seed_cursor != 0 && s.seed &&
                                  // (chunks longer than an entry covers all go the exact kernel's way: its seed route, then the text)
                                  (ca.chunk_symbols != 0u ? (ca.chunk_index == 0u && ca.chunk_symbols >= ix.seed_k && ca.chunk_symbols <= ix.seed_k + 32u)
                                                          : ca.active_in == nullptr);
-        if (seed_cursor) {
-            uint32_t *d_first = static_cast<uint32_t *>(stream_scratch(stream, 12, (nq + 4) * sizeof(uint32_t)));
-            GDX_HIP(hipMemsetAsync(d_first, 0, sizeof(uint32_t), stream));
-            SeedView sv{ix.seed, ix.text_units, ix.isa, ix.io_to_dense, ix.seed_buckets, ix.seed_k, ix.seed_tag_bits,
-                        ix.perm_code_lo, ix.perm_code_hi, ix.perm_exp_lo, ix.perm_exp_hi, ix.perm_mask};
-            sv.n = ix.n;
-            static const bool env_no_perm_c = getenv("GDX_SEARCH_NO_PERM") != nullptr;
-            uint4 *const no_rec = nullptr;
-            uint32_t *const none_u32 = nullptr;
-            uint2 *const no_state = nullptr;
-            if (ix.perm_ok && !env_no_perm_c)
-                hipLaunchKernelGGL((search_seed_kernel4<1, true, true>), dim3(blocks), dim3(kBlock), 0, stream, sv, c.d_qbuf, c.d_qbeg,
-                                   c.d_qend, nq, c.d_count, c.d_status, no_rec, c.d_start, c.d_end, range, d_first + 4, d_first, no_rec,
-                                   none_u32, none_u32, none_u32, no_state, 0u, 0u, 0u, ca);
-            else
-                hipLaunchKernelGGL((search_seed_kernel4<0, true, true>), dim3(blocks), dim3(kBlock), 0, stream, sv, c.d_qbuf, c.d_qbeg,
-                                   c.d_qend, nq, c.d_count, c.d_status, no_rec, c.d_start, c.d_end, range, d_first + 4, d_first, no_rec,
-                                   none_u32, none_u32, none_u32, no_state, 0u, 0u, 0u, ca);
-            ca_exact.active_in = d_first + 4;
-            ca_exact.n_active_in = d_first;
-            x_range = 256;
-            const uint64_t x_ranges = (nq + x_range - 1) / x_range;
-            x_blocks = static_cast<unsigned>(x_ranges < 8192 ? x_ranges : 8192);
-        }
-        if (exact) {
-            uint32_t *d_left = static_cast<uint32_t *>(stream_scratch(stream, 11, (nq + 4) * sizeof(uint32_t)));
-            GDX_HIP(hipMemsetAsync(d_left, 0, sizeof(uint32_t), stream));
-            // (behind the seed kernel's cursor pass the exact kernel does not look into the seed table again)
-            const ExactView ev{ix.top, ix.jump, ix.pair_lines, ix.io_to_dense, ix.top_depth, ix.n, static_cast<uint32_t>(ix.depth),
-                               ix.perm_code_lo, ix.perm_code_hi, ix.perm_exp_lo, ix.perm_exp_hi, ix.perm_mask,
-                               ix.sa_full, ix.isa, ix.text_units, (seed_usable && !seed_cursor) ? ix.seed : nullptr, ix.seed_buckets,
-                               ix.seed_k, ix.seed_tag_bits};
-            static const bool env_no_perm = getenv("GDX_SEARCH_NO_PERM") != nullptr;  // debug: translate through LDS
-            const bool perm = ix.perm_ok && !env_no_perm;
-#define GDX_EXACT_LAUNCH(J, XLATE, CURSOR)                                                                                  \
-    hipLaunchKernelGGL((search_exact_kernel4<J, XLATE, CURSOR>), dim3(x_blocks), dim3(kBlock), 0, stream, ev, c.d_qbuf,     \
-                       c.d_qbeg, c.d_qend, nq, c.d_start, c.d_end, c.d_count, c.d_status, x_range, schedule, d_left + 4, d_left, ca_exact)
-#define GDX_EXACT_LAUNCH_X(J, CURSOR)                    \
-    do {                                                 \
-        if (perm) GDX_EXACT_LAUNCH(J, 1, CURSOR);        \
-        else GDX_EXACT_LAUNCH(J, 0, CURSOR);             \
-    } while (0)
-#define GDX_EXACT_LAUNCH_T(XLATE, CURSOR)                                                                                    \
-    hipLaunchKernelGGL((search_exact_kernel4<0, XLATE, CURSOR, true>), dim3(x_blocks), dim3(kBlock), 0, stream, ev, c.d_qbuf, \
-                       c.d_qbeg, c.d_qend, nq, c.d_start, c.d_end, c.d_count, c.d_status, x_range, schedule, d_left + 4, d_left, ca_exact)
-#define GDX_EXACT_LAUNCH_J(CURSOR)                                                 \
-    do {                                                                           \
-        if (text_route && c.packed) GDX_EXACT_LAUNCH_T(2, false);                  \
-        else if (text_route && perm) GDX_EXACT_LAUNCH_T(1, CURSOR);                \
-        else if (text_route) GDX_EXACT_LAUNCH_T(0, CURSOR);                        \
-        else if (ix.jump == nullptr) GDX_EXACT_LAUNCH_X(0, CURSOR);                \
-        else if (ix.jump_bytes == 32) GDX_EXACT_LAUNCH_X(32, CURSOR);              \
-        else if (ix.jump_bytes == 16) GDX_EXACT_LAUNCH_X(16, CURSOR);              \
-        else GDX_EXACT_LAUNCH_X(8, CURSOR);                                        \
-    } while (0)
-            if (c.mode == 2) GDX_EXACT_LAUNCH_J(true);
-            else GDX_EXACT_LAUNCH_J(false);
-#undef GDX_EXACT_LAUNCH_J
-#undef GDX_EXACT_LAUNCH_T
-#undef GDX_EXACT_LAUNCH_X
-#undef GDX_EXACT_LAUNCH
-            g_range = 256;
-            const uint64_t g_ranges = (nq + g_range - 1) / g_range;
-            g_blocks = static_cast<unsigned>(g_ranges < 8192 ? g_ranges : 8192);
-            ca_general.active_in = d_left + 4;  // the general kernel below goes over the leftover list
-            ca_general.n_active_in = d_left;
-        }
-        if (fast) {
-            // the leftover list is short (0.3 % of the reads of a non-repetitive text) and its length is only known on
-            // the device: small ranges spread it over the chip, a capped grid strides over whatever there is
-            g_range = 256;
-            const uint64_t g_ranges = (nq + g_range - 1) / g_range;
-            g_blocks = static_cast<unsigned>(g_ranges < 8192 ? g_ranges : 8192);
-            uint32_t *d_left = static_cast<uint32_t *>(stream_scratch(stream, 11, (nq + 4) * sizeof(uint32_t)));
-            GDX_HIP(hipMemsetAsync(d_left, 0, sizeof(uint32_t), stream));
-            // where a leftover query stands is kept in its record slot; a call without records (counts only) lets the
-            // general kernel start its few leftovers over rather than allocate 16 bytes per query for them
-            uint4 *d_state = c.d_rec;
-            const FastView fv{ix.top, ix.jump, ix.io_to_dense, ix.top_depth, ix.sa_inv, ix.sa_rot, ix.sa_limit,
-                              ix.perm_code_lo, ix.perm_code_hi, ix.perm_exp_lo, ix.perm_exp_hi, ix.perm_mask};
-            static const bool env_no_perm = getenv("GDX_SEARCH_NO_PERM") != nullptr;  // debug: translate through LDS
-            // sixteen-row rounds where reads from repeats are common (QueryOptions::search_fast == 2)
-            const bool wide_rounds = (env_fast >= 0 ? env_fast : qo.search_fast) == 2;
-            // (after the seed kernel: over its list -- small ranges, a capped grid, as for the general kernel's lists)
-            const unsigned f_blocks = seed_list ? g_blocks : blocks;
-            const uint32_t f_range = seed_list ? g_range : range;
-            const uint32_t *f_list = seed_list ? seed_list + 4 : nullptr;
-#define GDX_FAST_LAUNCH(J, XLATE)                                                                                             \
-    do {                                                                                                                      \
-        if (wide_rounds)                                                                                                      \
-            hipLaunchKernelGGL((search_fast_kernel4<J, XLATE, true>), dim3(f_blocks), dim3(kBlock), 0, stream, fv, c.d_qbuf,  \
-                               c.d_qbeg, c.d_qend, nq, c.d_count, c.d_status, c.d_rec, f_range, d_left + 4, d_left, d_state,  \
-                               f_list, seed_list, seed_list ? seed_state_packed : 0u); \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((search_fast_kernel4<J, XLATE, false>), dim3(f_blocks), dim3(kBlock), 0, stream, fv, c.d_qbuf, \
-                               c.d_qbeg, c.d_qend, nq, c.d_count, c.d_status, c.d_rec, f_range, d_left + 4, d_left, d_state,  \
-                               f_list, seed_list, seed_list ? seed_state_packed : 0u); \
-    } while (0)
-#define GDX_FAST_LAUNCH_P(XLATE)                                  \
-    do {                                                          \
-        if (ix.jump_bytes == 32) GDX_FAST_LAUNCH(32, XLATE);      \
-        else if (ix.jump_bytes == 16) GDX_FAST_LAUNCH(16, XLATE); \
-        else GDX_FAST_LAUNCH(8, XLATE);                           \
-    } while (0)
-            if (seed_list != nullptr) offsets_for_list(seed_list + 4, seed_list);
-            if (c.packed) GDX_FAST_LAUNCH_P(2);
-            else if (ix.perm_ok && !env_no_perm) GDX_FAST_LAUNCH_P(1);
-            else GDX_FAST_LAUNCH_P(0);
-#undef GDX_FAST_LAUNCH_P
-#undef GDX_FAST_LAUNCH
-            static const bool env_stats = getenv("GDX_SEARCH_FAST_STATS") != nullptr;  // debug: size of the leftover list
-            if (env_stats) {
-                uint32_t n_left = 0;
-                GDX_HIP(hipMemcpyAsync(&n_left, d_left, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-                GDX_HIP(hipStreamSynchronize(stream));
-                fprintf(stderr, "gdx: fast path left %u of %llu queries to the general kernel\n", n_left,
-                        static_cast<unsigned long long>(nq));
-            }
-            ca_general.active_in = d_left + 4;  // the general kernel below searches the leftover list
-            ca_general.n_active_in = d_left;
-            ca_general.resume_state = d_state;
-        }
-        offsets_for_list(ca_general.active_in, ca_general.n_active_in);
-        if (c.packed) {
-#define GDX_PACKED_W(M)                                                                    \
-    do {                                                                                   \
-        if (ix.jump_bytes == 32) GDX_PAIR_LAUNCH((search_pair_packed_kernel4<32, M>));     \
-        else if (ix.jump_bytes == 16) GDX_PAIR_LAUNCH((search_pair_packed_kernel4<16, M>)); \
-        else GDX_PAIR_LAUNCH((search_pair_packed_kernel4<8, M>));                          \
-    } while (0)
-            if (c.mode == 0) GDX_PACKED_W(0);
-            else GDX_PACKED_W(1);
-#undef GDX_PACKED_W
-        } else if (c.d_step_stats != nullptr) {  // accounting: always the exact mode (the reference's LF steps)
-            if (lanes == 8) GDX_PAIR_LAUNCH_W(search_pair_stats_kernel8, 0, 0);
-            else GDX_PAIR_LAUNCH_W(search_pair_stats_kernel4, 0, 0);
-        } else if (defer_after != 0u && c.mode != 2) {
-#define GDX_PAIR_LAUNCH_D(KERNEL)                          \
-    do {                                                  \
-        if (c.mode == 0) GDX_PAIR_LAUNCH_W(KERNEL, 0, 0); \
-        else GDX_PAIR_LAUNCH_W(KERNEL, 0, 1);             \
-    } while (0)
-            // (6 waves per SIMD / 80 VGPRs halve its 14 spills and change nothing: 14.25 vs 14.36 ms)
-            if (lanes == 8) GDX_PAIR_LAUNCH_D(search_pair_defer_kernel8);
-            else GDX_PAIR_LAUNCH_D(search_pair_defer_kernel4);
-#undef GDX_PAIR_LAUNCH_D
-        } else if (lanes == 8) {
-            if (policy == 1) GDX_PAIR_LAUNCH_M(search_pair_kernel8, 1);
-            else GDX_PAIR_LAUNCH_M(search_pair_kernel8, 0);
-        } else {
-            if (policy == 0) GDX_PAIR_LAUNCH_M(search_pair_kernel4, 0);
-            else GDX_PAIR_LAUNCH_M(search_pair_kernel4, 1);
-        }
-#undef GDX_PAIR_LAUNCH_M
-#undef GDX_PAIR_LAUNCH_W
-#undef GDX_PAIR_LAUNCH
-        finish_fold();
-        return;
+        if (seed_cursor) pair_seed_cursor();
+        // (behind the seed kernel's cursor pass the exact kernel does not look into the seed table again)
+        if (exact) pair_exact(seed_usable && !seed_cursor);
+        if (fast) pair_fast();
+        offsets_for_list(st.ca_general.active_in, st.ca_general.n_active_in);
+        pair_general();
     }
-    // rank-line and generic kernels: no hints (locate then walks from the interval itself)
-    if (c.d_hint) GDX_HIP(hipMemsetAsync(c.d_hint, 0xff, nq * sizeof(uint2), stream));
-#define GDX_PLAIN_LAUNCH(TABLE, GROUP, GRID)                                                                        \
-    do {                                                                                                            \
-        if (c.mode == 2)                                                                                            \
-            hipLaunchKernelGGL((search_kernel<TABLE, GROUP, true>), dim3(GRID), dim3(kBlock), lds_pad, stream, ix,  \
-                               c.d_qbuf, c.d_qbeg, c.d_qend, nq, c.d_start, c.d_end, c.d_count, c.d_status,         \
-                               c.d_step_stats, c.d_rec, ca, ulen);                                                  \
-        else if (c.packed)                                                                                          \
-            hipLaunchKernelGGL((search_kernel<TABLE, GROUP, false, true>), dim3(GRID), dim3(kBlock), lds_pad, stream, ix, \
-                               c.d_qbuf, c.d_qbeg, c.d_qend, nq, c.d_start, c.d_end, c.d_count, c.d_status,         \
-                               c.d_step_stats, c.d_rec, ca, ulen);                                                  \
-        else                                                                                                        \
-            hipLaunchKernelGGL((search_kernel<TABLE, GROUP, false>), dim3(GRID), dim3(kBlock), lds_pad, stream, ix, \
-                               c.d_qbuf, c.d_qbeg, c.d_qend, nq, c.d_start, c.d_end, c.d_count, c.d_status,         \
-                               c.d_step_stats, c.d_rec, ca, ulen);                                                  \
-    } while (0)
-    if (ix.layout == 0 && variant != 1) GDX_PLAIN_LAUNCH(QuadLineTable, 4, group_grid(kBlock / 4));
-    else if (ix.layout == 0) GDX_PLAIN_LAUNCH(LineTable, 1, grid_for_items(nq));
-    else GDX_PLAIN_LAUNCH(GenericTable, 1, grid_for_items(nq));
-#undef GDX_PLAIN_LAUNCH
-    finish_fold();
+
+    // (d) rank-line and generic kernels
+    template <class Table, int kGroup>
+    void launch_plain(unsigned grid)
+    {
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), k.pad, stream, ix, c.d_qbuf, c.d_qbeg, c.d_qend, nq, c.d_start, c.d_end,
+                               c.d_count, c.d_status, c.d_step_stats, c.d_rec, st.ca, ulen);
+        };
+        if (c.mode == 2) launch(search_kernel<Table, kGroup, true>);
+        else if (c.packed) launch(search_kernel<Table, kGroup, false, true>);
+        else launch(search_kernel<Table, kGroup, false>);
+    }
+    // (e) the tile sums of a locate that the lane kernel began: its two lists, once every kernel of the call has written its results
+    void finish_fold()
+    {
+        if (st.fold_left == nullptr) return;
+        // (the lists' lengths are only known on the device: a capped grid that strides over whatever there is)
+        hipLaunchKernelGGL(tile_sums_lists_kernel, dim3(4096), dim3(kBlock), 0, stream, c.d_rec, c.d_compact, c.tile_max_hits,
+                           st.fold_left + 4, st.fold_left, st.fold_long + 4, st.fold_long, c.d_tile_sums, c.d_tile_rest);
+        if (c.tile_sums_done != nullptr) *c.tile_sums_done = true;
+    }
+};
+
+void launch_search_call(const IndexView &ix, const SearchCall &call, hipStream_t stream, const QueryOptions &qo)
+{
+    if (call.nq == 0) return;
+    if (call.mode < 0 || call.mode > 2) fail(GDX_ERR_INVALID_ARGUMENT, "internal: search mode %d", call.mode);
+    const SearchKnobs &knobs = search_knobs();
+    // the two knobs that are read on every call: tests switch them between the calls of one process
+    const char *env_pairs = getenv("GDX_SEARCH_SEED_PAIRS");
+    const char *env_lane_blocks = getenv("GDX_SEED_LANE_BLOCKS");
+    SearchLauncher l{ix, call, stream, knobs, SearchSettings(ix, qo, knobs, call), call.nq,
+                     !(env_pairs != nullptr && atoi(env_pairs) == 0), env_lane_blocks != nullptr ? atol(env_lane_blocks) : 0L};
+    SearchCall &c = l.c;
+    if (c.packed && (ix.layout != 0 || ix.n_searchable < 4))
+        fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
+    if (c.packed && (c.mode == 2 || c.d_step_stats != nullptr)) fail(GDX_ERR_UNSUPPORTED, "packed queries: search and count / locate only");
+    const bool pair_lines = ix.layout == 0 && l.s.variant == 2 && ix.pair_lines != nullptr;
+    // (b, early) a uniform batch in front of the pair-line kernels, which read offsets; a count / locate call may leave all but
+    // a short list to the seed chain, which computes too: decided behind the front
+    const bool pair_offsets = c.uniform_len != 0u && pair_lines;
+    if (pair_offsets && c.mode != 1) l.uniform_offsets(false);
+    l.ulen = c.uniform_len;
+    if (c.also_zero != nullptr) l.st.zs = *c.also_zero;
+    l.st.ca = c.cursors;
+    if (c.tile_sums_done != nullptr) *c.tile_sums_done = false;
+    if (c.d_compact != nullptr && (c.mode != 1 || c.d_rec == nullptr))
+        fail(GDX_ERR_INVALID_ARGUMENT, "internal: compact results go with the records of a count / locate search");
+    l.front();            // (a)
+    l.st.zs.flush(stream);  // (a call that took none of the paths above: what the caller wanted zeroed)
+    if (pair_offsets && c.mode == 1) l.uniform_offsets(l.st.leftover_list);  // (b)
+    // compact results without the seed kernel: every query says "see the record"
+    if (c.d_compact != nullptr && !l.st.compact_by_seed)
+        GDX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.d_compact), static_cast<int>(kCompactSee), l.nq, stream));
+    if (pair_lines) {
+        l.pair_lines();  // (c)
+    } else {             // (d)
+        // rank-line and generic kernels: no hints (locate then walks from the interval itself)
+        if (c.d_hint) GDX_HIP(hipMemsetAsync(c.d_hint, 0xff, l.nq * sizeof(uint2), stream));
+        if (ix.layout == 0 && l.s.variant != 1) l.launch_plain<QuadLineTable, 4>(group_grid(l.nq, kBlock / 4, knobs.grid));
+        else if (ix.layout == 0) l.launch_plain<LineTable, 1>(grid_for_items(l.nq));
+        else l.launch_plain<GenericTable, 1>(grid_for_items(l.nq));
+    }
+    l.finish_fold();  // (e)
 }
 
 // ASCII -> 2-bit: packed byte b holds the codes of bytes 4 b .. 4 b + 3 of the query buffer; *bad_symbols counts the
