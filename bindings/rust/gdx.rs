@@ -227,6 +227,18 @@ extern "C" {
         d_n_segments: *mut c_void, d_remaining: *mut c_void, d_length: *mut c_void, d_start: *mut c_void,
         d_end: *mut c_void, d_status: *mut c_void, stream: *mut c_void,
     ) -> c_int;
+    /// per query its super-maximal exact matches, rightmost first (include/gdx.h "super-maximal exact matches");
+    /// ix_reversed: an index of the same texts, each reversed
+    pub fn gdx_smems_many(
+        ix: *const gdx_index_t, ix_reversed: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, max_smems: u32,
+        min_length: u32, out_n_smems: *mut u32, out_remaining: *mut u32, out_begin: *mut u32, out_length: *mut u32,
+        out_start: *mut u64, out_end: *mut u64, out_status: *mut u8,
+    ) -> c_int;
+    pub fn gdx_smems_many_dev(
+        ix: *const gdx_index_t, ix_reversed: *const gdx_index_t, d_qbuf: *const c_void, d_qoff: *const c_void, nq: u64,
+        max_smems: u32, min_length: u32, d_n_smems: *mut c_void, d_remaining: *mut c_void, d_begin: *mut c_void,
+        d_length: *mut c_void, d_start: *mut c_void, d_end: *mut c_void, d_status: *mut c_void, stream: *mut c_void,
+    ) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
     ) -> c_int;
@@ -608,6 +620,37 @@ impl GpuFmIndex {
                         let seg = (end_at, length[k] as usize, GpuCursor { index: self, start: s[k], end: e[k] });
                         end_at -= std::cmp::max(length[k] as usize, 1);
                         seg
+                    })
+                    .collect()
+            })
+            .collect()
+    }
+
+    /// Per query its super-maximal exact matches as (query_begin, query_end, cursor), by descending end: the matches
+    /// query[query_begin .. query_end] that no other match of the query contains, those shorter than `min_length` left
+    /// out, at most `max_smems` per query.  `reversed` is an index of the same texts, each reversed; the cursors are
+    /// intervals of `self`.
+    pub fn smems_many<'a, Q: AsRef<[u8]>>(
+        &'a self, reversed: &GpuFmIndex, queries: impl IntoIterator<Item = Q>, max_smems: u32, min_length: u32,
+    ) -> Vec<Vec<(usize, usize, GpuCursor<'a>)>> {
+        let (buf, off) = pack(queries);
+        let nq = off.len() - 1;
+        let slots = nq * max_smems as usize;
+        let (mut n_smems, mut remaining) = (vec![0u32; nq], vec![0u32; nq]);
+        let (mut begin, mut length) = (vec![0u32; slots], vec![0u32; slots]);
+        let (mut s, mut e) = (vec![0u64; slots], vec![0u64; slots]);
+        check(unsafe {
+            gdx_smems_many(self.raw, reversed.raw, buf.as_ptr(), off.as_ptr(), nq as u64, max_smems, min_length,
+                           n_smems.as_mut_ptr(), remaining.as_mut_ptr(), begin.as_mut_ptr(), length.as_mut_ptr(),
+                           s.as_mut_ptr(), e.as_mut_ptr(), std::ptr::null_mut())
+        });
+        (0..nq)
+            .map(|i| {
+                (0..n_smems[i] as usize)
+                    .map(|j| {
+                        let k = i * max_smems as usize + j;
+                        let b = begin[k] as usize;
+                        (b, b + length[k] as usize, GpuCursor { index: self, start: s[k], end: e[k] })
                     })
                     .collect()
             })

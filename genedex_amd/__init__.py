@@ -7,12 +7,18 @@ include/gdx.h, built into libgdx.so), and the host-side mirror of the reference'
 from . import alphabet
 from .alphabet import Alphabet
 
-__all__ = ["alphabet", "Alphabet", "FmIndexConfig", "FmIndex", "PartitionedFmIndex", "Cursor", "Hit", "GdxError"]
+__all__ = ["alphabet", "Alphabet", "FmIndexConfig", "FmIndex", "PartitionedFmIndex", "Cursor", "Hit", "Smem", "GdxError",
+           "reversed_texts"]
+
+
+def reversed_texts(texts):
+    """Every text read backwards, in the same order: what the companion index of FmIndex.smems_many is built from."""
+    return [bytes(t)[::-1] for t in texts]
 
 
 def __getattr__(name):
     # the query API needs libgdx.so; importing the alphabet tables alone does not
-    if name in ("FmIndexConfig", "FmIndex", "PartitionedFmIndex", "Cursor", "Hit", "pack_queries"):
+    if name in ("FmIndexConfig", "FmIndex", "PartitionedFmIndex", "Cursor", "Hit", "Smem", "pack_queries"):
         from . import index
 
         return getattr(index, name)

@@ -221,6 +221,8 @@ SIGNATURES = {
     "gdx_cursor_extend_front_strings": [vp, u64p, u64p, u8p, u64p, C.c_uint64, u8p],
     "gdx_suffix_segments_many": [vp, u8p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u64p, u64p, u8p],
     "gdx_suffix_segments_many_dev": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp],
+    "gdx_smems_many": [vp, vp, u8p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u64p, u64p, u8p],
+    "gdx_smems_many_dev": [vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp],
     # gdx_bench.h
     "gdx_index_build_stats": [vp, C.POINTER(BuildStats)],
     "gdx_synth_text_dev": [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp],

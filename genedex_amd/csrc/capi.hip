@@ -1640,6 +1640,41 @@ int gdx_suffix_segments_many_dev(const gdx_index_t *ix, const void *d_qbuf, cons
     });
 }
 
+int gdx_smems_many(const gdx_index_t *ix, const gdx_index_t *ix_reversed, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq,
+                   uint32_t max_smems, uint32_t min_length, uint32_t *out_n_smems, uint32_t *out_remaining, uint32_t *out_begin,
+                   uint32_t *out_length, uint64_t *out_start, uint64_t *out_end, uint8_t *out_status)
+{
+    return guarded([&] {
+        const gdx::FmIndex &f = deref(ix);
+        return f.smems_many(deref(ix_reversed), qbuf, qoff, nq, max_smems, min_length, out_n_smems, out_remaining, out_begin,
+                            out_length, out_start, out_end, out_status);
+    });
+}
+
+int gdx_smems_many_dev(const gdx_index_t *ix, const gdx_index_t *ix_reversed, const void *d_qbuf, const void *d_qoff, uint64_t nq,
+                       uint32_t max_smems, uint32_t min_length, void *d_n_smems, void *d_remaining, void *d_begin, void *d_length,
+                       void *d_start, void *d_end, void *d_status, void *stream)
+{
+    return guarded([&] {
+        const gdx::FmIndex &f = deref(ix);
+        const gdx::FmIndex &r = deref(ix_reversed);
+        if (max_smems == 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "max_smems must be at least 1");
+        if (min_length == 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "min_length must be at least 1");
+        f.check_companion(r);
+        if (nq == 0) return (int)GDX_OK;
+        if ((reinterpret_cast<uintptr_t>(d_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf must be 8-byte aligned");
+        if (!d_qbuf || !d_qoff || !d_n_smems || !d_remaining || !d_begin || !d_length || !d_start || !d_end)
+            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+        DeviceGuard guard(f.config().device_id);
+        gdx::launch_smems(f.view(), r.view(), static_cast<const uint8_t *>(d_qbuf), static_cast<const uint64_t *>(d_qoff), nq,
+                          max_smems, min_length, static_cast<uint32_t *>(d_n_smems), static_cast<uint32_t *>(d_remaining),
+                          static_cast<uint32_t *>(d_begin), static_cast<uint32_t *>(d_length), static_cast<uint32_t *>(d_start),
+                          static_cast<uint32_t *>(d_end), static_cast<uint8_t *>(d_status), as_stream(stream), f.query_options());
+        GDX_HIP(hipGetLastError());
+        return (int)GDX_OK;
+    });
+}
+
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {

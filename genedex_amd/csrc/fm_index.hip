@@ -2169,6 +2169,56 @@ int FmIndex::suffix_segments_many(const uint8_t *qbuf, const uint64_t *qoff, uin
     return any_status(st.data(), nq);
 }
 
+void FmIndex::check_companion(const FmIndex &r) const
+{
+    if (r.cfg_.device_id != cfg_.device_id) fail(GDX_ERR_INVALID_ARGUMENT, "the reversed index lives on another device");
+    if (r.n_ != n_ || r.n_texts_ != n_texts_)
+        fail(GDX_ERR_INVALID_ARGUMENT, "the reversed index holds %llu symbols in %llu texts, the index %llu in %llu",
+             (unsigned long long)r.n_, (unsigned long long)r.n_texts_, (unsigned long long)n_, (unsigned long long)n_texts_);
+    if (r.cfg_.sigma != cfg_.sigma || r.cfg_.n_searchable != cfg_.n_searchable ||
+        std::memcmp(r.cfg_.io_to_dense, cfg_.io_to_dense, 256) != 0)
+        fail(GDX_ERR_INVALID_ARGUMENT, "the reversed index was built with another alphabet");
+    if (r.count_host_ != count_host_)
+        fail(GDX_ERR_INVALID_ARGUMENT, "the reversed index counts other symbols: it was not built from the same texts, reversed");
+    if (r.view_.layout != view_.layout)
+        fail(GDX_ERR_UNSUPPORTED, "the reversed index has another occurrence-table layout (reference_table_layout)");
+}
+
+int FmIndex::smems_many(const FmIndex &reversed, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint32_t max_smems,
+                        uint32_t min_length, uint32_t *out_n_smems, uint32_t *out_remaining, uint32_t *out_begin,
+                        uint32_t *out_length, uint64_t *out_start, uint64_t *out_end, uint8_t *out_status) const
+{
+    if (max_smems == 0) fail(GDX_ERR_INVALID_ARGUMENT, "max_smems must be at least 1");
+    if (min_length == 0) fail(GDX_ERR_INVALID_ARGUMENT, "min_length must be at least 1");
+    check_companion(reversed);
+    check_queries(qbuf, qoff, nq);
+    if (nq == 0) return GDX_OK;
+    if (!out_n_smems || !out_remaining || !out_begin || !out_length || !out_start || !out_end)
+        fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+    for (uint64_t i = 0; i < nq; i++)
+        if (qoff[i + 1] - qoff[i] > 0xffffffffull)
+            fail(GDX_ERR_INVALID_ARGUMENT, "query %llu is longer than 2^32 - 1 symbols", (unsigned long long)i);
+    make_current();
+    hipStream_t stream = hipStreamPerThread;
+    DeviceQueries dq(qbuf, qoff, nq, stream);
+    const uint64_t slots = nq * max_smems;
+    DeviceBuffer<uint32_t> d_n(nq), d_rem(nq), d_begin(slots), d_len(slots), d_start(slots), d_end(slots);
+    DeviceBuffer<uint8_t> d_status(nq);
+    launch_smems(view_, reversed.view_, dq.qbuf.get(), dq.qoff.get(), nq, max_smems, min_length, d_n.get(), d_rem.get(),
+                 d_begin.get(), d_len.get(), d_start.get(), d_end.get(), d_status.get(), stream, query_options());
+    GDX_HIP(hipGetLastError());
+    GDX_HIP(hipMemcpyAsync(out_n_smems, d_n.get(), nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_remaining, d_rem.get(), nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_begin, d_begin.get(), slots * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_length, d_len.get(), slots * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    download_widened(d_start.get(), out_start, slots, stream);
+    download_widened(d_end.get(), out_end, slots, stream);
+    std::vector<uint8_t> st(nq);
+    GDX_HIP(hipMemcpy(st.data(), d_status.get(), nq, hipMemcpyDeviceToHost));
+    if (out_status) std::memcpy(out_status, st.data(), nq);
+    return any_status(st.data(), nq);
+}
+
 int FmIndex::rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const
 {
     if (m == 0) return GDX_OK;

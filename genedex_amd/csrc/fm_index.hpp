@@ -129,6 +129,14 @@ public:
     int suffix_segments_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint32_t max_segments, uint32_t flags,
                              uint32_t *out_n_segments, uint32_t *out_remaining, uint32_t *out_length, uint64_t *out_start,
                              uint64_t *out_end, uint8_t *out_status) const;
+    // gdx_smems_many[_dev]: fails with GDX_ERR_INVALID_ARGUMENT unless `reversed` can be the index of this one's texts, each
+    // reversed (device, n, number of texts, alphabet and count array agree), with GDX_ERR_UNSUPPORTED when the two have
+    // different occurrence-table layouts
+    void check_companion(const FmIndex &reversed) const;
+    // gdx_smems_many: the whole batch staged (copy in, one launch, copy out)
+    int smems_many(const FmIndex &reversed, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint32_t max_smems,
+                   uint32_t min_length, uint32_t *out_n_smems, uint32_t *out_remaining, uint32_t *out_begin, uint32_t *out_length,
+                   uint64_t *out_start, uint64_t *out_end, uint8_t *out_status) const;
     int rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const;
     int symbol_at_many(const uint64_t *idx, uint64_t m, uint8_t *out) const;
 

@@ -134,6 +134,14 @@ void launch_suffix_segments(const IndexView &ix, const uint8_t *d_qbuf, const ui
                             uint32_t max_segments, bool lf_only, uint32_t *d_n_segments, uint32_t *d_remaining,
                             uint32_t *d_length, uint32_t *d_start, uint32_t *d_end, uint8_t *d_status, hipStream_t stream,
                             const QueryOptions &qo = QueryOptions());
+// gdx_smems_many[_dev]: per query its super-maximal exact matches, rightmost first, one launch that alternates between
+// fx (the index of the texts) and rx (the index of the same texts, each reversed; same table layout, alphabet and count
+// array as fx).  SMEM j of query i in slot i * max_smems + j of d_begin / d_length / d_start / d_end (start / end: rows of
+// fx), unused slots zeroed.  The kernel variant comes from qo (the options of fx).  d_status may be null.
+void launch_smems(const IndexView &fx, const IndexView &rx, const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq,
+                  uint32_t max_smems, uint32_t min_length, uint32_t *d_n_smems, uint32_t *d_remaining, uint32_t *d_begin,
+                  uint32_t *d_length, uint32_t *d_start, uint32_t *d_end, uint8_t *d_status, hipStream_t stream,
+                  const QueryOptions &qo = QueryOptions());
 // d_error (u32, pre-zeroed) is set to 1 when an argument is out of range
 void launch_rank_many(const IndexView &ix, const uint8_t *d_symbols, const uint32_t *d_idx, uint64_t m,
                       uint32_t *d_out, uint32_t *d_error, hipStream_t stream);

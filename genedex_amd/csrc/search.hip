@@ -3691,6 +3691,187 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((kText &
     }
 }
 
+// gdx_smems_many[_dev]: the super-maximal exact matches of every read (include/gdx.h has the definition), found by a walk
+// that alternates between two one-directional indexes: fx over the texts, rx over the same texts each reversed.  From
+// position p a FORWARD pass on rx consumes q[p], q[p + 1], ... (extending in front of the reversed match) and gives the
+// longest e with q[p, e) occurring; a BACKWARD pass on fx from e, the pass of suffix_segments_kernel, gives the longest
+// match [s, e) that ends there and its interval in fx; [s, e) is an SMEM and the walk goes on at p = s - 1.  All in one
+// launch; kGroup lanes per read, control flow uniform inside a group, its first lane writes.  Both passes step as the
+// segments kernel does (PairTable::lf1 for symbols 1..4 on pair lines -- kPair: BOTH views hold them -- else Table::rank2
+// plus count) and enter through their own index's top table when the pass has top_depth symbols 1..4 ahead of it; the
+// entry of an absent D-mer only says that the pass is shorter, which is then found step by step.  io_to_dense and count
+// are the same in both indexes (the host checks it), so the block keeps one copy.
+struct SmemsOut {
+    uint32_t *n_smems, *remaining, *begin, *length, *start, *end;
+    uint8_t *status;
+};
+
+// The query's symbols left to right through aligned 8-byte windows, the next one requested a window ahead: QueryWindow
+// for the forward pass.  Bytes [pos, end) with pos < end; get() must walk upwards from pos.
+struct ForwardQueryWindow {
+    const uint64_t *words;
+    uint64_t cur, next, cur_word, last_word;
+
+    __device__ __forceinline__ void init(const uint8_t *qbuf, uint64_t pos, uint64_t end)
+    {
+        words = reinterpret_cast<const uint64_t *>(qbuf);
+        last_word = (end - 1) >> 3;
+        cur_word = pos >> 3;
+        cur = words[cur_word];
+        next = cur_word < last_word ? words[cur_word + 1] : 0ull;
+    }
+    __device__ __forceinline__ uint32_t get(uint64_t at)
+    {
+        const uint64_t w = at >> 3;
+        if (w != cur_word) {
+            cur_word = w;
+            cur = next;
+            next = w < last_word ? words[w + 1] : 0ull;
+        }
+        return static_cast<uint32_t>(cur >> ((at & 7u) * 8u)) & 0xffu;
+    }
+};
+
+// one cursor step of either pass with dense symbol c >= 1
+template <class Table, int kGroup, bool kPair>
+__device__ __forceinline__ void smems_step(const IndexView &ix, const uint32_t *s_count, uint32_t c, uint32_t lo, uint32_t hi,
+                                           uint32_t &nlo, uint32_t &nhi)
+{
+    if (kPair && c <= 4u) {
+        PairTable::lf1<0, kGroup>(ix, c, lo, hi, nlo, nhi);
+    } else {
+        Table::rank2(ix, c, lo, hi, nlo, nhi);
+        const uint32_t cc = s_count[c];
+        nlo += cc;
+        nhi += cc;
+    }
+}
+
+// The top-table entry of a pass: its first `depth` symbols sit at first[0], first[dir], first[2 dir], ... (first consumed
+// symbol in the highest bits, as top_lookup takes them).  False, lo / hi untouched: a symbol outside 1..4 or a D-mer that
+// does not occur -- the pass then runs step by step from its start.
+__device__ __forceinline__ bool smems_top(const IndexView &ix, uint32_t depth, const uint8_t *s_dense, const uint8_t *first, int dir,
+                                          uint32_t &lo, uint32_t &hi)
+{
+    uint32_t a = 0, b = 0;
+    for (uint32_t s = 0; s < depth; s++) {
+        const uint32_t c = s_dense[first[static_cast<int64_t>(dir) * static_cast<int64_t>(s)]];
+        if (s < 8u) a |= c << (4u * (7u - s));
+        else b |= c << (4u * (15u - s));
+    }
+    uint32_t tlo, thi;
+    if (!top_lookup(ix, a, b, tlo, thi) || tlo == thi) return false;
+    lo = tlo;
+    hi = thi;
+    return true;
+}
+
+// Like the segments kernel this one lives on reads in flight (a dependent, latency-bound fetch chain per read).  Waves per
+// SIMD from the registers the compiler reports (-Rpass-analysis=kernel-resource-usage, gfx950): pair lines 77 VGPRs and
+// one lane per read on rank lines 75 VGPRs = 6 waves; four lanes on rank lines 57 and the generic table 61: 7 asked for,
+// 8 reported; no scratch in any instance (profiles/r09/smems.md).
+template <class Table, int kGroup, bool kPair>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((kPair || std::is_same<Table, LineTable>::value) ? 6 : 7))) void smems_kernel(
+    IndexView fx, IndexView rx, const uint8_t *__restrict__ qbuf, const uint64_t *__restrict__ qoff, uint64_t nq,
+    uint32_t max_smems, uint32_t min_length, SmemsOut out)
+{
+    __shared__ uint8_t s_dense[256];
+    __shared__ uint32_t s_count[257];
+    for (int i = threadIdx.x; i < 256; i += kBlock) s_dense[i] = fx.io_to_dense[i];
+    for (int i = threadIdx.x; i <= fx.sigma; i += kBlock) s_count[i] = fx.count[i];
+    __syncthreads();
+
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * (kBlock / kGroup);
+    const bool writer = (threadIdx.x % kGroup) == 0;
+    const uint32_t fdepth = (fx.top != nullptr && fx.layout == 0) ? fx.top_depth : 0u;
+    const uint32_t rdepth = (rx.top != nullptr && rx.layout == 0) ? rx.top_depth : 0u;
+    for (uint64_t q = static_cast<uint64_t>(blockIdx.x) * (kBlock / kGroup) + threadIdx.x / kGroup; q < nq; q += stride) {
+        const uint64_t begin = qoff[q];
+        const uint32_t m = static_cast<uint32_t>(qoff[q + 1] - begin);
+        const uint64_t slot0 = q * max_smems;
+        uint32_t pe = m, n_smems = 0, status = GDX_Q_OK;  // pe = p + 1: the walk stands at p, 0 = it is through
+        while (pe > 0u && n_smems < max_smems) {
+            const uint32_t p = pe - 1u;
+            // forward pass on rx: the longest e with q[p, e) occurring
+            uint32_t lo = 0, hi = rx.n, e = p;
+            if (rdepth != 0u && m - p >= rdepth && smems_top(rx, rdepth, s_dense, qbuf + begin + p, 1, lo, hi)) e = p + rdepth;
+            if (e < m) {
+                ForwardQueryWindow win;
+                win.init(qbuf, begin + e, begin + m);
+                while (e < m) {
+                    const uint32_t c = s_dense[win.get(begin + e)];
+                    if (c == 0u) {  // also as the symbol that blocks: translation comes before anything else
+                        status = GDX_Q_INVALID_SYMBOL;
+                        break;
+                    }
+                    if (lo == hi) break;  // (an index without rows: nothing occurs)
+                    uint32_t nlo, nhi;
+                    smems_step<Table, kGroup, kPair>(rx, s_count, c, lo, hi, nlo, nhi);
+                    if (nlo == nhi) break;
+                    lo = nlo;
+                    hi = nhi;
+                    e++;
+                }
+            }
+            if (status != GDX_Q_OK) break;
+            if (e == p) {  // q[p] occurs nowhere: no SMEM covers p
+                pe = p;
+                continue;
+            }
+            // backward pass on fx: the longest match that ends at e, with the interval from before the step that emptied it
+            uint32_t len = 0;
+            lo = 0;
+            hi = fx.n;
+            if (fdepth != 0u && e >= fdepth && smems_top(fx, fdepth, s_dense, qbuf + begin + e - 1u, -1, lo, hi)) len = fdepth;
+            QueryWindow win;
+            win.init(qbuf, begin, begin + (e - len));
+            while (len < e) {
+                const uint32_t c = s_dense[win.get(begin + (e - len) - 1u)];
+                if (c == 0u) {
+                    status = GDX_Q_INVALID_SYMBOL;
+                    break;
+                }
+                if (lo == hi) break;
+                uint32_t nlo, nhi;
+                smems_step<Table, kGroup, kPair>(fx, s_count, c, lo, hi, nlo, nhi);
+                if (nlo == nhi) break;
+                lo = nlo;
+                hi = nhi;
+                len++;
+            }
+            if (status != GDX_Q_OK) break;
+            const uint32_t s = e - len;
+            if (len >= min_length) {
+                if (writer) {
+                    out.begin[slot0 + n_smems] = s;
+                    out.length[slot0 + n_smems] = len;
+                    out.start[slot0 + n_smems] = lo;
+                    out.end[slot0 + n_smems] = hi;
+                }
+                n_smems++;
+            }
+            // s <= p when rx indexes the reversed texts of fx; with a companion built from other texts (the host cannot
+            // tell) the walk must still move left
+            pe = s < p ? s : p;
+        }
+        if (status != GDX_Q_OK) {
+            n_smems = 0;
+            pe = m;
+        }
+        if (writer) {
+            for (uint32_t j = n_smems; j < max_smems; j++) {
+                out.begin[slot0 + j] = 0u;
+                out.length[slot0 + j] = 0u;
+                out.start[slot0 + j] = 0u;
+                out.end[slot0 + j] = 0u;
+            }
+            out.n_smems[q] = n_smems;
+            out.remaining[q] = pe;
+            if (out.status != nullptr) out.status[q] = static_cast<uint8_t>(status);
+        }
+    }
+}
+
 template <class Table>
 __global__ __launch_bounds__(kBlock) void rank_many_kernel(IndexView ix, const uint8_t *__restrict__ symbols,
                                                            const uint32_t *__restrict__ idx, uint64_t m,
@@ -4658,6 +4839,25 @@ void launch_suffix_segments(const IndexView &ix, const uint8_t *d_qbuf, const ui
     else if (ix.layout == 0) GDX_SEGMENTS_LAUNCH(LineTable, 1, false);
     else GDX_SEGMENTS_LAUNCH(GenericTable, 1, false);
 #undef GDX_SEGMENTS_LAUNCH
+}
+
+void launch_smems(const IndexView &fx, const IndexView &rx, const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq,
+                  uint32_t max_smems, uint32_t min_length, uint32_t *d_n_smems, uint32_t *d_remaining, uint32_t *d_begin,
+                  uint32_t *d_length, uint32_t *d_start, uint32_t *d_end, uint8_t *d_status, hipStream_t stream,
+                  const QueryOptions &qo)
+{
+    if (nq == 0) return;
+    const int variant = qo.search_variant >= 0 ? qo.search_variant : search_variant();
+    const SmemsOut out = {d_n_smems, d_remaining, d_begin, d_length, d_start, d_end, d_status};
+#define GDX_SMEMS_LAUNCH(TABLE, GROUP, PAIR)                                                                                  \
+    hipLaunchKernelGGL((smems_kernel<TABLE, GROUP, PAIR>), dim3(grid_for_items(nq * GROUP)), dim3(kBlock), 0, stream, fx, rx, \
+                       d_qbuf, d_qoff, nq, max_smems, min_length, out)
+    // (the callers have checked that both views have the same table layout)
+    if (fx.layout == 0 && variant == 2 && fx.pair_lines != nullptr && rx.pair_lines != nullptr) GDX_SMEMS_LAUNCH(QuadLineTable, 4, true);
+    else if (fx.layout == 0 && variant != 1) GDX_SMEMS_LAUNCH(QuadLineTable, 4, false);
+    else if (fx.layout == 0) GDX_SMEMS_LAUNCH(LineTable, 1, false);
+    else GDX_SMEMS_LAUNCH(GenericTable, 1, false);
+#undef GDX_SMEMS_LAUNCH
 }
 
 void launch_rank_many(const IndexView &ix, const uint8_t *d_symbols, const uint32_t *d_idx, uint64_t m,

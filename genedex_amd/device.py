@@ -386,6 +386,27 @@ class DeviceEngine:
             _ptr(out["n_segments"]), _ptr(out["remaining"]), _ptr(out["length"]), _ptr(out["start"]), _ptr(out["end"]),
             _ptr(out["status"]) if out.get("status") is not None else None, _stream()))
 
+    # ---- super-maximal exact matches (gdx_smems_many_dev) ---------------------------------------------------
+    def alloc_smems(self, nq: int, max_smems: int):
+        d = self.dev
+        slots = max(nq * max_smems, 1)
+        out = {name: torch.empty(max(nq, 1), dtype=torch.int32, device=d) for name in ("n_smems", "remaining")}
+        out.update({name: torch.empty(slots, dtype=torch.int32, device=d) for name in ("begin", "length", "start", "end")})
+        out["status"] = torch.empty(max(nq, 1), dtype=torch.uint8, device=d)
+        return out
+
+    def smems(self, q: DeviceQueries, reversed_index, max_smems: int, min_length: int, out) -> None:
+        """One fused launch: per query its super-maximal exact matches into `out` (alloc_smems; u32 values in int32 tensors,
+        SMEM j of query i in slot i * max_smems + j).  reversed_index: the DeviceEngine or FmIndex of the same texts, each
+        reversed.  Plain batches only."""
+        if q.packed or q.uniform_len:
+            raise ValueError("smems(): plain batches only")
+        r = reversed_index.h if isinstance(reversed_index, DeviceEngine) else reversed_index._h
+        _lib.check(self.lib.gdx_smems_many_dev(
+            self.h, r, _ptr(q.qbuf), _ptr(q.qoff), q.nq, int(max_smems), int(min_length), _ptr(out["n_smems"]),
+            _ptr(out["remaining"]), _ptr(out["begin"]), _ptr(out["length"]), _ptr(out["start"]), _ptr(out["end"]),
+            _ptr(out["status"]) if out.get("status") is not None else None, _stream()))
+
     def search_step_stats(self, q: DeviceQueries):
         """(LF steps, line fetches of all queries, fetch slots their wavefronts spent)"""
         steps = torch.zeros(3, dtype=torch.int64, device=self.dev)

@@ -30,6 +30,13 @@ class Segment(NamedTuple):
     cursor: "Cursor"
 
 
+class Smem(NamedTuple):
+    """One super-maximal exact match of a query (FmIndex.smems_many): query[query_begin : query_end], cursor its interval"""
+    query_begin: int
+    query_end: int
+    cursor: "Cursor"
+
+
 def _p(a, t):
     return a.ctypes.data_as(t)
 
@@ -465,6 +472,40 @@ class FmIndex:
         symbol occurs nowhere, length 0 with cursor_empty() for the empty query"""
         segs = self.suffix_segments_many([query], 1)[0]
         return (segs[0].length, segs[0].cursor) if segs else (0, self.cursor_empty())
+
+    def smems_raw(self, reversed_index, qbuf, qoff, max_smems, min_length=1, strict=True):
+        """gdx_smems_many -> (n_smems u32[nq], remaining u32[nq], begin u32[nq * max_smems], length u32, start u64, end u64,
+        status u8[nq]): per query its super-maximal exact matches, rightmost first (include/gdx.h has the definition).
+        reversed_index: an FmIndex of the same texts, each reversed (genedex_amd.reversed_texts)."""
+        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
+        qoff = np.ascontiguousarray(qoff, dtype=np.uint64)
+        nq = qoff.size - 1
+        slots = max(nq * int(max_smems), 1)
+        n_smems = np.zeros(max(nq, 1), dtype=np.uint32)
+        remaining = np.zeros(max(nq, 1), dtype=np.uint32)
+        begin = np.zeros(slots, dtype=np.uint32)
+        length = np.zeros(slots, dtype=np.uint32)
+        start = np.zeros(slots, dtype=np.uint64)
+        end = np.zeros(slots, dtype=np.uint64)
+        status = np.zeros(max(nq, 1), dtype=np.uint8)
+        st = self._lib.gdx_smems_many(self._h, reversed_index._h, _p(qbuf, u8p), _p(qoff, u64p), nq, int(max_smems),
+                                      int(min_length), _p(n_smems, u32p), _p(remaining, u32p), _p(begin, u32p),
+                                      _p(length, u32p), _p(start, u64p), _p(end, u64p), _p(status, u8p))
+        _lib.check(st, allow=() if strict else (_lib.GDX_ERR_QUERY_STATUS,))
+        k = nq * int(max_smems)
+        return n_smems[:nq], remaining[:nq], begin[:k], length[:k], start[:k], end[:k], status[:nq]
+
+    def smems_many(self, queries, reversed_index, max_smems, min_length=1):
+        """Per query the list of its Smem(query_begin, query_end, cursor), by descending end: the matches of the query that no
+        other match contains, at most max_smems of them, those shorter than min_length left out; cursor is the interval of
+        query[query_begin:query_end] in this index (count() / locate())."""
+        qbuf, qoff = pack_queries(queries)
+        n_smems, _, begin, length, start, end, _ = self.smems_raw(reversed_index, qbuf, qoff, max_smems, min_length)
+        out = []
+        for i in range(qoff.size - 1):
+            ks = range(i * max_smems, i * max_smems + int(n_smems[i]))
+            out.append([Smem(int(begin[k]), int(begin[k]) + int(length[k]), Cursor(self, int(start[k]), int(end[k]))) for k in ks])
+        return out
 
     def rank_many(self, symbols, idx):
         """TextWithRankSupport::rank (text_with_rank_support/mod.rs:106-110), batched."""

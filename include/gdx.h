@@ -370,6 +370,49 @@ int gdx_suffix_segments_many(const gdx_index_t *ix, const uint8_t *qbuf, const u
                              uint32_t *out_length /*nq*max_segments*/, uint64_t *out_start, uint64_t *out_end,
                              uint8_t *out_status /*nq or NULL*/);
 
+/* Super-maximal exact matches (SMEMs): the seed set of a read that does not occur as a whole.  For a query q of m
+ * symbols a MATCH is a pair b < e such that q[b, e) occurs in some text, where "occurs" means that
+ * Cursor::extend_query_front, applied from [0, n) to q[e-1], ..., q[b], never empties the interval (so alphabets,
+ * sentinels and non-searchable symbols such as N mean what they mean there).  An SMEM is a match that is not properly
+ * contained in another match.  Unlike the greedy suffix segments the SMEMs do not depend on where a walk started: a
+ * mismatch near the read's right end does not hide the long match to its left.
+ * No bidirectional index is needed, two one-directional ones are: F = ix, the index of the texts, and R = ix_reversed,
+ * an index of the same texts, each reversed (text i of R is text i of F read backwards).  The walk that defines the
+ * outputs:
+ *     p = m - 1; n_smems = 0
+ *     while p >= 0 and n_smems < max_smems:
+ *         forward pass on R (the longest e with q[p, e) occurring): cursor = R's [0, n), e = p; while e < m: extend
+ *             the cursor in front by q[e]; if it empties: stop, else e += 1
+ *         if e == p: p -= 1; continue                      (q[p] occurs nowhere: no SMEM covers p)
+ *         backward pass on F (the longest match that ends at e): cursor = F's [0, n), s = e; while s > 0: extend in
+ *             front by q[s-1]; if it empties: stop and keep the previous interval, else s -= 1
+ *         (s <= p always; [s, e) is an SMEM, and every SMEM not yet seen begins left of s)
+ *         if e - s >= min_length: record (begin = s, length = e - s, F's interval [start, end)); n_smems += 1
+ *         p = s - 1
+ *     remaining = p + 1 if p >= 0 else 0
+ * Per query: out_n_smems; out_remaining -- 0 when the walk went through the whole read, otherwise max_smems cut it and
+ * SMEMs that begin left of `remaining`, if there are any, are not reported; and the SMEMs in the order found, by
+ * descending end: SMEM j of query i in slot i * max_smems + j of out_begin / out_length / out_start / out_end.  Unused
+ * slots are written as zeros.  Every recorded (start, end) is a cursor of F (ix) for gdx_cursor_locate_many.
+ * A symbol outside the alphabet that the walk REACHES, in either pass and also as the symbol that blocks it, gives the
+ * query GDX_Q_INVALID_SYMBOL, n_smems 0, remaining m and zeroed slots, and the host call GDX_ERR_QUERY_STATUS.
+ * GDX_ERR_INVALID_ARGUMENT: max_smems == 0, min_length == 0, (host form) a query of 2^32 symbols or more, and an
+ * ix_reversed that cannot be the companion of ix: another device, n, num_texts, sigma, n_searchable, io_to_dense table
+ * or count[] array.  A COMPANION THAT PASSES THESE CHECKS BUT WAS BUILT FROM OTHER TEXTS IS NOT DETECTED: the call then
+ * terminates with meaningless results.  GDX_ERR_UNSUPPORTED: either handle belongs to the 64-bit engine, or the two
+ * have different occurrence-table layouts (gdx_build_options_t.reference_table_layout).
+ * The companion is an ordinary gdx_index_t that the caller builds with gdx_index_build_ex from the reversed texts (no
+ * new handle type, no new build call).  The walk uses only its occurrence table, and profits from pair lines and a top
+ * table; recommended build options for it: seed_symbols = 0, text_units = 0, full_suffix_array = 0,
+ * inverse_suffix_array = 0, jump_entry_bytes = 0 (INTEGRATION.md has what it costs in HBM).  Queries are in the plain
+ * form only (IO symbols plus u64 offsets).  One fused kernel launch per call, with the kernel variant of ix's query
+ * options (pair lines are used when BOTH indexes hold them); the host form stages the whole batch (copy in, launch, copy
+ * out; no chunked pipeline).  gdx_parts_t and gdx_multi_t have no such call. */
+int gdx_smems_many(const gdx_index_t *ix, const gdx_index_t *ix_reversed, const uint8_t *qbuf, const uint64_t *qoff,
+                   uint64_t nq, uint32_t max_smems, uint32_t min_length,
+                   uint32_t *out_n_smems /*nq*/, uint32_t *out_remaining /*nq*/, uint32_t *out_begin /*nq*max_smems*/,
+                   uint32_t *out_length, uint64_t *out_start, uint64_t *out_end, uint8_t *out_status /*nq or NULL*/);
+
 /* ---------------------------------------------------------------------------------------
  * device-resident entry points: all pointers are DEVICE pointers on the handle's GPU, work
  * is enqueued on `stream` (hipStream_t) and the call returns without synchronising.
@@ -385,6 +428,13 @@ int gdx_suffix_segments_many_dev(const gdx_index_t *ix, const void *d_qbuf, cons
                                  uint32_t max_segments, uint32_t flags, void *d_n_segments, void *d_remaining,
                                  void *d_length, void *d_start /*u32*/, void *d_end /*u32*/, void *d_status,
                                  void *stream);
+/* gdx_smems_many on device pointers: d_qoff u64[nq + 1], d_n_smems / d_remaining u32[nq], d_begin / d_length / d_start /
+ * d_end u32[nq * max_smems], d_status u8[nq] or NULL (read it to learn of invalid symbols: the call itself does not
+ * synchronise and returns GDX_OK).  Queries must be shorter than 2^32 symbols. */
+int gdx_smems_many_dev(const gdx_index_t *ix, const gdx_index_t *ix_reversed, const void *d_qbuf, const void *d_qoff,
+                       uint64_t nq, uint32_t max_smems, uint32_t min_length, void *d_n_smems, void *d_remaining,
+                       void *d_begin, void *d_length, void *d_start /*u32*/, void *d_end /*u32*/, void *d_status,
+                       void *stream);
 /* locate for m intervals whose offsets were produced by gdx_hit_offsets_dev; total =
  * d_hit_offsets[m] (the caller reads it back to size d_hits and d_workspace:
  * gdx_locate_workspace_bytes(total)). */
