@@ -239,6 +239,23 @@ extern "C" {
         max_smems: u32, min_length: u32, d_n_smems: *mut c_void, d_remaining: *mut c_void, d_begin: *mut c_void,
         d_length: *mut c_void, d_start: *mut c_void, d_end: *mut c_void, d_status: *mut c_void, stream: *mut c_void,
     ) -> c_int;
+    /// both strands (include/gdx.h "both strands"): the stock complement table, the bytes of an expanded batch, the expand
+    /// of a device-resident batch, and count / locate of every read as given (row 2i) and reverse-complemented (row 2i + 1)
+    pub fn gdx_dna_complement_table(out: *mut u8);
+    pub fn gdx_strands_out_bytes(total_symbols: u64, packed: c_int, mode: u32) -> u64;
+    pub fn gdx_strands_expand_dev(
+        ix: *const gdx_index_t, d_qbuf: *const c_void, d_qoff: *const c_void, nq: u64, layout: *const QueryLayout,
+        total_symbols: u64, complement: *const u8, mode: u32, d_out_qbuf: *mut c_void, d_out_qoff: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
+    pub fn gdx_count_many_strands(
+        ix: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, complement: *const u8, out_counts: *mut u64,
+        out_status: *mut u8,
+    ) -> c_int;
+    pub fn gdx_locate_many_alloc_strands(
+        ix: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, complement: *const u8, out_hit_offsets: *mut u64,
+        out_hits: *mut *mut Hit, out_total: *mut u64, out_status: *mut u8,
+    ) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
     ) -> c_int;
@@ -529,6 +546,33 @@ impl GpuFmIndex {
         check(unsafe {
             gdx_locate_many_alloc(self.raw, buf.as_ptr(), off.as_ptr(), nq as u64, offsets.as_mut_ptr(), &mut ptr,
                                   &mut total, std::ptr::null_mut())
+        });
+        Hits { ptr, total: total as usize, offsets }
+    }
+
+    /// count_many on both strands: per read (occurrences as given, occurrences of its reverse complement under the stock
+    /// IUPAC complement table).  The reads cross PCIe once; the reverse complements are made on the device.
+    pub fn count_many_both_strands<Q: AsRef<[u8]>>(&self, queries: impl IntoIterator<Item = Q>) -> Vec<(usize, usize)> {
+        let (buf, off) = pack(queries);
+        let nq = off.len() - 1;
+        let mut counts = vec![0u64; 2 * nq];
+        check(unsafe {
+            gdx_count_many_strands(self.raw, buf.as_ptr(), off.as_ptr(), nq as u64, std::ptr::null(), counts.as_mut_ptr(),
+                                   std::ptr::null_mut())
+        });
+        counts.chunks(2).map(|c| (c[0] as usize, c[1] as usize)).collect()
+    }
+
+    /// locate_many on both strands: `of(2 * i)` are the hits of read i as given, `of(2 * i + 1)` those of its reverse
+    /// complement (the read maps to the reverse strand there; position = the leftmost text coordinate of the alignment)
+    pub fn locate_many_both_strands<Q: AsRef<[u8]>>(&self, queries: impl IntoIterator<Item = Q>) -> Hits {
+        let (buf, off) = pack(queries);
+        let nq = off.len() - 1;
+        let mut offsets = vec![0u64; 2 * nq + 1];
+        let (mut total, mut ptr) = (0u64, std::ptr::null_mut());
+        check(unsafe {
+            gdx_locate_many_alloc_strands(self.raw, buf.as_ptr(), off.as_ptr(), nq as u64, std::ptr::null(), offsets.as_mut_ptr(),
+                                          &mut ptr, &mut total, std::ptr::null_mut())
         });
         Hits { ptr, total: total as usize, offsets }
     }

@@ -28,6 +28,8 @@ GDX_ERR_QUERY_STATUS = 6
 GDX_ERR_UNSUPPORTED = 7
 
 GDX_SEGMENTS_LF_ONLY = 1  # flags of gdx_suffix_segments_many[_dev]
+GDX_STRANDS_REVERSE = 1   # modes of gdx_strands_expand_dev
+GDX_STRANDS_BOTH = 2
 GDX_Q_OK = 0
 GDX_Q_INVALID_SYMBOL = 1
 GDX_Q_UNSEARCHABLE_IN_LOOKUP = 2
@@ -223,6 +225,11 @@ SIGNATURES = {
     "gdx_suffix_segments_many_dev": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp],
     "gdx_smems_many": [vp, vp, u8p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u64p, u64p, u8p],
     "gdx_smems_many_dev": [vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "gdx_dna_complement_table": [u8p],
+    "gdx_strands_out_bytes": [C.c_uint64, C.c_int, C.c_uint32],
+    "gdx_strands_expand_dev": [vp, vp, vp, C.c_uint64, C.POINTER(QueryLayout), C.c_uint64, u8p, C.c_uint32, vp, vp, vp],
+    "gdx_count_many_strands": [vp, u8p, u64p, C.c_uint64, u8p, u64p, u8p],
+    "gdx_locate_many_alloc_strands": [vp, u8p, u64p, C.c_uint64, u8p, u64p, C.POINTER(C.POINTER(HitStruct)), u64p, u8p],
     # gdx_bench.h
     "gdx_index_build_stats": [vp, C.POINTER(BuildStats)],
     "gdx_synth_text_dev": [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp],
@@ -246,7 +253,8 @@ SIGNATURES = {
 _RESTYPES = {"gdx_locate_many_totals_workspace_bytes": C.c_uint64, "gdx_wire_bitmap_bytes": C.c_uint64,
              "gdx_wire_pack_workspace_bytes": C.c_uint64, "gdx_last_error": C.c_char_p, "gdx_index_free": None, "gdx_fastx_close": None,
              "gdx_build_options_init": None, "gdx_query_layout_init": None, "gdx_query_options_init": None, "gdx_free_hits": None, "gdx_free_hits32": None, "gdx_release_cached_hits": None, "gdx_multi_free": None, "gdx_parts_free": None,
-             "gdx_locate_workspace_bytes": C.c_uint64, "gdx_packed_bytes": C.c_uint64}
+             "gdx_locate_workspace_bytes": C.c_uint64, "gdx_packed_bytes": C.c_uint64, "gdx_strands_out_bytes": C.c_uint64,
+             "gdx_dna_complement_table": None}
 
 _lib = None
 

@@ -124,6 +124,21 @@ def ascii_amino_acid_iupac():
     return Alphabet.from_ambiguous_io_symbols(_ci(b"ABCDEFGHIJKLMNOPQRSTUVWXYZ") + [b"*"], 0)
 
 
+def dna_complement_table() -> np.ndarray:
+    """The stock complement table of the both-strand calls (gdx_dna_complement_table): IUPAC, case kept, every other byte
+    mapped to itself."""
+    table = np.arange(256, dtype=np.uint8)
+    for a, b in zip(b"ACGTRYKMBVDHSWN", b"TGCAYRMKVBHDSWN"):
+        table[a], table[a + 32] = b, b + 32
+    return table
+
+
+def reverse_complement(seq, table=None) -> bytes:
+    """r[j] = table[seq[m - 1 - j]]: the host-side definition of what gdx_strands_expand_dev makes on the device."""
+    table = dna_complement_table() if table is None else np.asarray(table, dtype=np.uint8)
+    return table[np.frombuffer(bytes(seq), dtype=np.uint8)[::-1]].tobytes()
+
+
 def u8_until(max_symbol):
     """src/alphabet.rs:339-341."""
     return Alphabet.from_io_symbols(bytes(range(max_symbol + 1)), 0)

@@ -1675,6 +1675,71 @@ int gdx_smems_many_dev(const gdx_index_t *ix, const gdx_index_t *ix_reversed, co
     });
 }
 
+// ---- both strands (strands.hip) ---------------------------------------------------------------------------------
+
+void gdx_dna_complement_table(uint8_t out[256])
+{
+    if (out) gdx::dna_complement_table(out);
+}
+
+uint64_t gdx_strands_out_bytes(uint64_t total_symbols, int packed, uint32_t mode)
+{
+    return gdx::strands_out_bytes(total_symbols, packed != 0, mode);
+}
+
+int gdx_strands_expand_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
+                           const gdx_query_layout_t *layout, uint64_t total_symbols, const uint8_t *complement, uint32_t mode,
+                           void *d_out_qbuf, void *d_out_qoff, void *stream)
+{
+    return guarded([&] {
+        const gdx::FmIndex &f = deref(ix);
+        if (mode != GDX_STRANDS_REVERSE && mode != GDX_STRANDS_BOTH)
+            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "mode must be GDX_STRANDS_REVERSE or GDX_STRANDS_BOTH");
+        gdx::SearchCall c;  // (the layout's checks: struct size, alignment of d_qbuf, offsets of a batch that is not uniform)
+        apply_layout(c, d_qbuf, d_qoff, nq, layout);
+        if (c.packed && (f.view().layout != 0 || f.view().n_searchable < 4))
+            gdx::fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
+        uint8_t stock[256];
+        if (!complement) {
+            gdx::dna_complement_table(stock);
+            complement = stock;
+        }
+        gdx::check_complement(f.config().io_to_dense, complement, c.packed);
+        const bool writes_offsets = mode == GDX_STRANDS_BOTH && c.uniform_len == 0;
+        if (!d_out_qbuf || (writes_offsets && !d_out_qoff)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null output");
+        if ((reinterpret_cast<uintptr_t>(d_out_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_out_qbuf must be 8-byte aligned");
+        if (nq != 0 && !d_qbuf) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf is null");
+        if (c.uniform_len != 0 && total_symbols != nq * c.uniform_len)
+            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "a uniform batch of %llu queries of %u symbols has %llu symbols, not %llu",
+                      (unsigned long long)nq, c.uniform_len, (unsigned long long)(nq * c.uniform_len), (unsigned long long)total_symbols);
+        const uint64_t out_bytes = gdx::strands_out_bytes(total_symbols, c.packed, mode);
+        const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_qbuf), out0 = reinterpret_cast<uintptr_t>(d_out_qbuf);
+        if (nq != 0 && in0 < out0 + out_bytes && out0 < in0 + gdx::strands_out_bytes(total_symbols, c.packed, 1))
+            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_out_qbuf overlaps d_qbuf");
+        DeviceGuard guard(f.config().device_id);
+        gdx::launch_strands_expand(c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, total_symbols, complement, mode, d_out_qbuf,
+                                   static_cast<uint64_t *>(d_out_qoff), as_stream(stream));
+        GDX_HIP(hipGetLastError());
+        return (int)GDX_OK;
+    });
+}
+
+int gdx_count_many_strands(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint8_t *complement,
+                           uint64_t *out_counts, uint8_t *out_status)
+{
+    return guarded([&] { return deref(ix).strands_many(qbuf, qoff, nq, complement, out_counts, nullptr, nullptr, nullptr, out_status); });
+}
+
+int gdx_locate_many_alloc_strands(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq,
+                                  const uint8_t *complement, uint64_t *out_hit_offsets, gdx_hit_t **out_hits, uint64_t *out_total,
+                                  uint8_t *out_status)
+{
+    return guarded([&] {
+        if (!out_hit_offsets) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "out_hit_offsets is null");
+        return deref(ix).strands_many(qbuf, qoff, nq, complement, nullptr, out_hit_offsets, out_hits, out_total, out_status);
+    });
+}
+
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {

@@ -1035,6 +1035,14 @@ __global__ __launch_bounds__(kBlock) void widen_u32_kernel(const uint32_t *in, u
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < m; i += stride) out[i] = in[i];
 }
 
+// max_hits_per_query of the staged host calls: an interval keeps its first max_hits rows (suffix-array order)
+__global__ __launch_bounds__(kBlock) void take_first_rows_kernel(const uint32_t *start, uint32_t *end, uint64_t m, uint32_t max_hits)
+{
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < m; i += stride)
+        if (end[i] > start[i] && end[i] - start[i] > max_hits) end[i] = start[i] + max_hits;
+}
+
 __global__ __launch_bounds__(kBlock) void narrow_u64_kernel(const uint64_t *in, uint32_t *out, uint64_t m,
                                                             uint64_t limit, uint32_t *error)
 {
@@ -2217,6 +2225,81 @@ int FmIndex::smems_many(const FmIndex &reversed, const uint8_t *qbuf, const uint
     GDX_HIP(hipMemcpy(st.data(), d_status.get(), nq, hipMemcpyDeviceToHost));
     if (out_status) std::memcpy(out_status, st.data(), nq);
     return any_status(st.data(), nq);
+}
+
+int FmIndex::strands_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint8_t *complement, uint64_t *out_counts,
+                          uint64_t *out_hit_offsets, gdx_hit_t **out_hits, uint64_t *out_total, uint8_t *out_status) const
+{
+    const bool locate = out_hit_offsets != nullptr;
+    if (locate) {
+        if (!out_hits) fail(GDX_ERR_INVALID_ARGUMENT, "out_hits is null");
+        *out_hits = nullptr;
+        if (out_total) *out_total = 0;
+        out_hit_offsets[0] = 0;
+    }
+    uint8_t stock[256];
+    if (!complement) {
+        dna_complement_table(stock);
+        complement = stock;
+    }
+    check_complement(cfg_.io_to_dense, complement, false);
+    check_queries(qbuf, qoff, nq);
+    if (2 * nq >= 0xffffffffull) fail(GDX_ERR_UNSUPPORTED, "more than 2^31-1 queries in one both-strand call");
+    if (nq == 0) return GDX_OK;
+    if (!locate && !out_counts) fail(GDX_ERR_INVALID_ARGUMENT, "out_counts is null");
+    make_current();
+    hipStream_t stream = hipStreamPerThread;
+    DeviceQueries dq(qbuf, qoff, nq, stream);  // the forward reads cross the link once
+    const uint64_t total = qoff[nq] - qoff[0], m = 2 * nq;
+    DeviceBuffer<uint8_t> d_both(strands_out_bytes(total, false, GDX_STRANDS_BOTH));
+    DeviceBuffer<uint64_t> d_both_off(m + 1);
+    launch_strands_expand(dq.qbuf.get(), dq.qoff.get(), nq, false, 0, total, complement, GDX_STRANDS_BOTH, d_both.get(),
+                          d_both_off.get(), stream);
+    DeviceBuffer<uint32_t> d_start(m), d_end(m);
+    DeviceBuffer<uint8_t> d_status(m);
+    SearchCall c;
+    c.d_qbuf = d_both.get();
+    c.d_qbeg = d_both_off.get();
+    c.d_qend = d_both_off.get() + 1;
+    c.nq = m;
+    c.d_start = d_start.get();
+    c.d_end = d_end.get();
+    c.d_status = d_status.get();
+    c.mode = 0;
+    launch_search_call(view_, c, stream, query_options());
+    GDX_HIP(hipGetLastError());
+    std::vector<uint8_t> st(m);
+    GDX_HIP(hipMemcpyAsync(st.data(), d_status.get(), m, hipMemcpyDeviceToHost, stream));
+    if (!locate) {
+        std::vector<uint64_t> s(m), e(m);
+        download_widened(d_start.get(), s.data(), m, stream);
+        download_widened(d_end.get(), e.data(), m, stream);
+        for (uint64_t i = 0; i < m; i++) out_counts[i] = e[i] > s[i] ? e[i] - s[i] : 0;
+    } else {
+        const uint32_t max_hits = query_options().max_hits_per_query;
+        if (max_hits != 0)
+            hipLaunchKernelGGL(take_first_rows_kernel, dim3(grid_for_items(m)), dim3(kBlock), 0, stream, d_start.get(), d_end.get(),
+                               m, max_hits);
+        uint64_t n_hits = 0;
+        int rc = GDX_OK;
+        locate_device(d_start.get(), d_end.get(), m, out_hit_offsets, nullptr, 0, &n_hits, &rc);  // offsets and the total
+        gdx_hit_t *hits = static_cast<gdx_hit_t *>(std::malloc((n_hits ? n_hits : 1) * sizeof(gdx_hit_t)));
+        if (!hits) fail(GDX_ERR_DEVICE, "out of host memory for %llu hits", static_cast<unsigned long long>(n_hits));
+        if (n_hits != 0) {
+            rc = GDX_OK;
+            try {
+                locate_device(d_start.get(), d_end.get(), m, nullptr, hits, n_hits, nullptr, &rc);
+            } catch (...) {
+                std::free(hits);
+                throw;
+            }
+        }
+        *out_hits = hits;
+        if (out_total) *out_total = n_hits;
+    }
+    GDX_HIP(hipStreamSynchronize(stream));
+    if (out_status) std::memcpy(out_status, st.data(), m);
+    return any_status(st.data(), m);
 }
 
 int FmIndex::rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const

@@ -137,6 +137,10 @@ public:
     int smems_many(const FmIndex &reversed, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint32_t max_smems,
                    uint32_t min_length, uint32_t *out_n_smems, uint32_t *out_remaining, uint32_t *out_begin, uint32_t *out_length,
                    uint64_t *out_start, uint64_t *out_end, uint8_t *out_status) const;
+    // gdx_count_many_strands / gdx_locate_many_alloc_strands: the whole batch staged (copy the forward reads in, expand them on
+    // the device, search 2 nq rows, copy out); complement: 256 bytes or null (the stock table).  out_hit_offsets == null: counts only
+    int strands_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint8_t *complement, uint64_t *out_counts,
+                     uint64_t *out_hit_offsets, gdx_hit_t **out_hits, uint64_t *out_total, uint8_t *out_status) const;
     int rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const;
     int symbol_at_many(const uint64_t *idx, uint64_t m, uint8_t *out) const;
 

@@ -157,6 +157,20 @@ void launch_fill_top(const IndexView &ix, uint2 *d_top, uint32_t depth, hipStrea
 // *d_sum (pre-zeroed) += widths of the top-table entries wider than `rows` rows
 void launch_top_wide(const uint2 *d_top, uint32_t depth, uint32_t rows, unsigned long long *d_sum, hipStream_t stream);
 
+// ---- strands.hip --------------------------------------------------------------------------
+// gdx_dna_complement_table: the stock IUPAC table
+void dna_complement_table(uint8_t out[256]);
+// the two rules of gdx.h that make a complement table usable with an index (GDX_ERR_INVALID_ARGUMENT otherwise): it keeps
+// validity, and -- packed -- the complement of a dense symbol d in 1..4 is 5 - d
+void check_complement(const uint8_t *io_to_dense, const uint8_t *complement, bool packed);
+uint64_t strands_out_bytes(uint64_t total_symbols, bool packed, uint32_t mode);
+// gdx_strands_expand_dev: the batch in any of the four layouts (uniform_len != 0: d_qoff unused) -> its reverse complement
+// (mode GDX_STRANDS_REVERSE) or both strands interleaved (GDX_STRANDS_BOTH; with offsets d_out_qoff = u64[2 nq + 1]) in the same
+// layout; every byte of strands_out_bytes is written.  complement: host, 256 bytes, checked by the caller.
+void launch_strands_expand(const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq, bool packed, uint32_t uniform_len,
+                           uint64_t total_symbols, const uint8_t *complement, uint32_t mode, void *d_out_qbuf,
+                           uint64_t *d_out_qoff, hipStream_t stream);
+
 // ---- locate.hip ---------------------------------------------------------------------------
 size_t hit_offsets_temp_bytes(uint64_t m);
 void launch_hit_offsets(const uint32_t *d_start, const uint32_t *d_end, uint64_t m, uint64_t *d_hit_offsets,

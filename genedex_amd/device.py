@@ -101,6 +101,41 @@ class DeviceQueries:
             raise ValueError(f"{int(bad.item())} symbols outside the four searchable ones: not expressible in 2 bits")
         return DeviceQueries(packed, self.qoff, self.nq, (n_sym + 3) // 4, True, self.uniform_len)
 
+    def with_strands(self, index: FmIndex, mode: str = "both", complement=None) -> "DeviceQueries":
+        """A new batch in the same form, made on the device (gdx_strands_expand_dev): mode "reverse" -- query i is the reverse
+        complement of query i; "both" -- 2 nq queries, query 2i as given and query 2i + 1 its reverse complement.  complement:
+        256 bytes, None = the stock table (alphabet.dna_complement_table)."""
+        lib = _lib.load()
+        m = {"reverse": _lib.GDX_STRANDS_REVERSE, "both": _lib.GDX_STRANDS_BOTH}[mode]
+        if self.uniform_len:
+            n_sym = self.nq * int(self.uniform_len)
+        else:
+            n_sym = int(self.qoff[self.nq].item()) if self.nq else 0
+        dev = self.qbuf.device
+        out = torch.empty(int(lib.gdx_strands_out_bytes(n_sym, 1 if self.packed else 0, m)), dtype=torch.uint8, device=dev)
+        lay, qoff = self.layout()
+        if self.uniform_len:
+            out_off = self.qoff
+        elif m == _lib.GDX_STRANDS_BOTH:
+            out_off = torch.empty(2 * self.nq + 1, dtype=torch.int64, device=dev)
+        else:
+            out_off = self.qoff
+        comp_arr = None if complement is None else np.ascontiguousarray(complement, dtype=np.uint8)  # (read during the call)
+        if comp_arr is not None and comp_arr.size != 256:
+            raise ValueError("a complement table has 256 entries")
+        comp = None if comp_arr is None else comp_arr.ctypes.data_as(u8p)
+        _lib.check(lib.gdx_strands_expand_dev(index._h, _ptr(self.qbuf), qoff, self.nq, C.byref(lay) if lay is not None else None,
+                                              n_sym, comp, m, _ptr(out), _ptr(out_off) if not self.uniform_len else C.c_void_p(0),
+                                              _stream()))
+        nq = self.nq * m
+        if self.uniform_len:
+            n_out = nq * int(self.uniform_len)
+        elif m == _lib.GDX_STRANDS_BOTH:
+            n_out = 2 * (n_sym - (int(self.qoff[0].item()) if self.nq else 0))
+        else:
+            n_out = n_sym
+        return DeviceQueries(out, out_off, nq, (n_out + 3) // 4 if self.packed else n_out, self.packed, self.uniform_len)
+
     @classmethod
     def synth(cls, io_text: torch.Tensor, text_lengths, nq: int, len_min: int, len_max: int,
               sampled_per_million: int, seed: int = 43) -> "DeviceQueries":

@@ -41,6 +41,13 @@ def _p(a, t):
     return a.ctypes.data_as(t)
 
 
+def _complement_table(table):
+    table = np.ascontiguousarray(table, dtype=np.uint8)
+    if table.size != 256:
+        raise ValueError("a complement table has 256 entries")
+    return table
+
+
 def pack_queries(queries):
     """list of bytes-like -> (qbuf u8[...], qoff u64[nq+1])"""
     queries = [bytes(q) for q in queries]
@@ -537,6 +544,50 @@ class FmIndex:
         off, t, p, _ = self.locate_raw(qbuf, qoff)
         t, p = t.tolist(), p.tolist()
         return [[Hit(t[h], p[h]) for h in range(int(off[q]), int(off[q + 1]))] for q in range(qoff.size - 1)]
+
+    # ---- both strands (gdx.h "both strands") ------------------------------------------------------
+    def count_strands_raw(self, qbuf, qoff, complement=None, strict=True):
+        """gdx_count_many_strands -> (counts u64[2 nq], status u8[2 nq]); row 2i = read i, row 2i + 1 = its reverse complement"""
+        nq = qoff.size - 1
+        counts = np.zeros(2 * nq, dtype=np.uint64)
+        status = np.zeros(2 * nq, dtype=np.uint8)
+        comp = None if complement is None else _p(_complement_table(complement), u8p)
+        st = self._lib.gdx_count_many_strands(self._h, _p(qbuf, u8p), _p(qoff, u64p), nq, comp, _p(counts, u64p), _p(status, u8p))
+        _lib.check(st, allow=() if strict else (_lib.GDX_ERR_QUERY_STATUS,))
+        return counts, status
+
+    def locate_strands_raw(self, qbuf, qoff, complement=None, strict=True):
+        """gdx_locate_many_alloc_strands -> (hit_offsets u64[2 nq + 1], text_ids u64[total], positions u64[total], status u8[2 nq])"""
+        nq = qoff.size - 1
+        off = np.zeros(2 * nq + 1, dtype=np.uint64)
+        status = np.zeros(2 * nq, dtype=np.uint8)
+        total = C.c_uint64(0)
+        hits = C.POINTER(_lib.HitStruct)()
+        comp = None if complement is None else _p(_complement_table(complement), u8p)
+        st = self._lib.gdx_locate_many_alloc_strands(self._h, _p(qbuf, u8p), _p(qoff, u64p), nq, comp, _p(off, u64p),
+                                                     C.byref(hits), C.byref(total), _p(status, u8p))
+        try:
+            _lib.check(st, allow=() if strict else (_lib.GDX_ERR_QUERY_STATUS,))
+            n = total.value
+            flat = np.ctypeslib.as_array(C.cast(hits, u64p), shape=(2 * n,)).reshape(n, 2).copy() if n else np.zeros((0, 2), np.uint64)
+        finally:
+            if hits:
+                self._lib.gdx_free_hits(hits)
+        return off, flat[:, 0].copy(), flat[:, 1].copy(), status
+
+    def count_many_strands(self, queries, complement=None):
+        """(nq, 2) array: occurrences of every read as given and of its reverse complement"""
+        qbuf, qoff = pack_queries(queries)
+        return self.count_strands_raw(qbuf, qoff, complement)[0].reshape(-1, 2)
+
+    def locate_many_strands(self, queries, complement=None):
+        """per read a pair of hit lists: (hits of the read as given, hits of its reverse complement -- the read maps to the
+        reverse strand there, position = the leftmost text coordinate of the alignment)"""
+        qbuf, qoff = pack_queries(queries)
+        off, t, p, _ = self.locate_strands_raw(qbuf, qoff, complement)
+        t, p = t.tolist(), p.tolist()
+        rows = [[Hit(t[h], p[h]) for h in range(int(off[r]), int(off[r + 1]))] for r in range(2 * (qoff.size - 1))]
+        return [(rows[2 * i], rows[2 * i + 1]) for i in range(qoff.size - 1)]
 
     def cursor_empty(self) -> "Cursor":
         s = C.c_uint64(0)

@@ -570,6 +570,61 @@ int gdx_locate_many_alloc_layout(const gdx_index_t *ix, const uint8_t *qbuf, con
                                  const gdx_query_layout_t *layout, uint64_t *out_hit_offsets, gdx_hit_t **out_hits,
                                  uint64_t *out_total, uint8_t *out_status);
 
+/* ---- both strands: reverse-complement batches made on the device ------------------------------------------------------
+ * A mapper's reads come from either strand of the DNA; the reference leaves the second strand to its callers.  The COMPLEMENT
+ * is a 256-entry table from IO symbol to IO symbol, the REVERSE COMPLEMENT of a query q of m symbols is r with
+ * r[j] = comp[q[m - 1 - j]].  A hit at position p of the reverse complement of a read means that the read maps to the reverse
+ * strand, with p as the leftmost text coordinate of the alignment.
+ *   gdx_dna_complement_table   the stock table (host only, no device needed): IUPAC -- A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H,
+ *       S, W and N map to themselves --, lower case to lower case, every other byte to itself.  It is an involution.
+ * A table is usable with an index only if it KEEPS VALIDITY: for every byte c, io_to_dense[c] == 0 exactly when
+ * io_to_dense[comp[c]] == 0 (the handle's own table).  Then a query with a symbol outside the alphabet gets GDX_Q_INVALID_SYMBOL
+ * on both strands, wherever the walk reaches it, and the status bytes mean what they mean everywhere.  The stock table passes
+ * for the four DNA alphabets of the reference and fails for ascii_amino_acid (V is valid, B is not).  PACKED batches are
+ * complemented as code ^ 3, which is right exactly when io_to_dense[comp[c]] == 5 - d for every byte c with dense code d in
+ * 1..4; the exceptions of the packed form stay the caller's business, as everywhere.  Both rules are checked on the host; a
+ * table that fails one is GDX_ERR_INVALID_ARGUMENT.
+ *
+ * gdx_strands_expand_dev turns a device-resident batch, in any of the four forms of gdx_query_layout_t (same alignment rules
+ * as the search calls), into a batch of the SAME form that every `_dev` call takes unchanged: count, locate, the one-call
+ * step, cursors, suffix segments, SMEMs.
+ *   GDX_STRANDS_REVERSE   nq queries out, query i = revcomp(q_i).  With offsets, output query i occupies the symbol range
+ *                         [qoff[i], qoff[i+1]) of the output buffer that q_i occupies in the input: the caller reuses its own
+ *                         offsets array and d_out_qoff may be NULL.
+ *   GDX_STRANDS_BOTH      2 nq queries out, query 2i = q_i as given, query 2i + 1 = revcomp(q_i).  With offsets, d_out_qoff is
+ *                         u64[2 nq + 1], written by the call and zero based: out[2i] = 2 (qoff[i] - qoff[0]), out[2i + 1] =
+ *                         out[2i] + len_i, out[2 nq] = 2 (qoff[nq] - qoff[0]); qoff[0] is read on the device.
+ * A uniform batch stays uniform with the same uniform_len (d_out_qoff is ignored and may be NULL).  total_symbols is the number
+ * of symbols of the input buffer up to the end of its last query (qoff[nq], or nq * uniform_len), which the host knows as it
+ * does for gdx_pack_queries_dev.  The caller allocates gdx_strands_out_bytes(total_symbols, packed, mode) bytes for d_out_qbuf
+ * (8-byte aligned, not overlapping d_qbuf) -- plain: mode * total_symbols rounded up to 8, plus 8; packed:
+ * gdx_packed_bytes(mode * total_symbols) -- and the call defines every byte of them: bits and bytes that belong to no query are
+ * zero.  complement: HOST pointer to 256 bytes, NULL = the stock table; it travels as a kernel argument.  The call enqueues on
+ * `stream` (two launches at most) without synchronising, allocating device memory or copying from pageable memory.
+ * GDX_ERR_INVALID_ARGUMENT: an unknown mode, a table that fails the rules above; GDX_ERR_UNSUPPORTED: the packed form on an
+ * index that does not take packed queries, and handles of the 64-bit engine.  nq == 0 is GDX_OK (and out_qoff[0] = 0).
+ * The expanded batch costs device memory beside the input: as much again (REVERSE) or twice as much (BOTH). */
+#define GDX_STRANDS_REVERSE 1u /* nq queries out: query i = revcomp(q_i)                                 */
+#define GDX_STRANDS_BOTH 2u    /* 2 nq queries out: query 2i = q_i as given, query 2i + 1 = revcomp(q_i) */
+void gdx_dna_complement_table(uint8_t out[256]);
+uint64_t gdx_strands_out_bytes(uint64_t total_symbols, int packed, uint32_t mode);
+int gdx_strands_expand_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
+                           const gdx_query_layout_t *layout, uint64_t total_symbols,
+                           const uint8_t *complement /* host, 256 bytes; NULL = the stock table */, uint32_t mode,
+                           void *d_out_qbuf, void *d_out_qoff, void *stream);
+/* gdx_count_many / gdx_locate_many_alloc on both strands of every read (plain form: IO symbols + u64 offsets): row 2i is read i
+ * as given, row 2i + 1 its reverse complement; out_counts / out_status have 2 nq entries, out_hit_offsets 2 nq + 1.  Hits are in
+ * suffix-array order within a row and are released with gdx_free_hits; gdx_query_options_t.max_hits_per_query applies per row.
+ * The forward reads cross PCIe ONCE and are expanded on the device.  The calls stage the whole batch (copy in, expand, search,
+ * locate, copy out; no chunked pipeline), like gdx_suffix_segments_many.  Argument errors and GDX_ERR_QUERY_STATUS as in
+ * gdx_count_many / gdx_locate_many_alloc, the complement table as above; handles of the 64-bit engine return
+ * GDX_ERR_UNSUPPORTED; gdx_parts_t and gdx_multi_t have no such call. */
+int gdx_count_many_strands(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq,
+                           const uint8_t *complement, uint64_t *out_counts /*2 nq*/, uint8_t *out_status /*2 nq or NULL*/);
+int gdx_locate_many_alloc_strands(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq,
+                                  const uint8_t *complement, uint64_t *out_hit_offsets /*2 nq + 1*/, gdx_hit_t **out_hits,
+                                  uint64_t *out_total, uint8_t *out_status /*2 nq or NULL*/);
+
 /* ---- batched cursor extension by strings (Cursor::extend_query_front, cursor.rs:34-51, applied to every symbol of
  * a string from its last to its first; ROADMAP.md:33 "API to use batched search with cursors") --------------------
  * Cursor i is extended by string i = d_qbuf[d_qbeg[i] .. d_qend[i]) (for a plain offsets array pass d_qoff and
