@@ -133,6 +133,7 @@ pub const GDX_OK: c_int = 0;
 pub const GDX_ERR_CAPACITY: c_int = 5;
 pub const GDX_ERR_QUERY_STATUS: c_int = 6;
 pub const GDX_SEGMENTS_LF_ONLY: u32 = 1;
+pub const GDX_HAMMING_INVALID: u32 = 0xFFFF_FFFF;
 
 /// gdx_query_layout_t
 #[repr(C)]
@@ -255,6 +256,17 @@ extern "C" {
     pub fn gdx_locate_many_alloc_strands(
         ix: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, complement: *const u8, out_hit_offsets: *mut u64,
         out_hits: *mut *mut Hit, out_total: *mut u64, out_status: *mut u8,
+    ) -> c_int;
+    /// Hamming verification of located seeds (include/gdx.h "Hamming verification"): per candidate (query, seed begin,
+    /// located hit) the mismatches of the whole read against its text on the seed's diagonal, capped at max_mismatches + 1
+    pub fn gdx_hamming_many_dev(
+        ix: *const gdx_index_t, d_qbuf: *const c_void, d_qoff: *const c_void, nq: u64, layout: *const QueryLayout,
+        d_cand_query: *const c_void, d_cand_begin: *const c_void, d_cand_hits: *const c_void, m: u64, max_mismatches: u32,
+        d_out: *mut c_void, stream: *mut c_void,
+    ) -> c_int;
+    pub fn gdx_hamming_many(
+        ix: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, cand_query: *const u32, cand_begin: *const u32,
+        cand_hits: *const Hit, m: u64, max_mismatches: u32, out: *mut u32,
     ) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
@@ -699,6 +711,24 @@ impl GpuFmIndex {
                     .collect()
             })
             .collect()
+    }
+
+    /// Seed and verify: candidate c says that the seed of `queries[cand_query[c]]` that begins at symbol `cand_begin[c]` was
+    /// located at `cand_hits[c]` (what `GpuCursor::locate` gives for an SMEM's cursor); entry c of the result is the number of
+    /// mismatches of the WHOLE query against that text on the seed's diagonal, min(dist, max_mismatches + 1).  Symbols that
+    /// hang over an end of the text, N and bytes outside the alphabet count as mismatches.  Panics on a candidate whose
+    /// query or text id is out of range and on an index without text units.
+    pub fn hamming_many<Q: AsRef<[u8]>>(
+        &self, queries: impl IntoIterator<Item = Q>, cand_query: &[u32], cand_begin: &[u32], cand_hits: &[Hit], max_mismatches: u32,
+    ) -> Vec<u32> {
+        assert!(cand_query.len() == cand_begin.len() && cand_query.len() == cand_hits.len());
+        let (buf, off) = pack(queries);
+        let mut out = vec![0u32; cand_query.len()];
+        check(unsafe {
+            gdx_hamming_many(self.raw, buf.as_ptr(), off.as_ptr(), (off.len() - 1) as u64, cand_query.as_ptr(), cand_begin.as_ptr(),
+                             cand_hits.as_ptr(), cand_query.len() as u64, max_mismatches, out.as_mut_ptr())
+        });
+        out
     }
 }
 

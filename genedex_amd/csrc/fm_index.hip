@@ -2302,6 +2302,59 @@ int FmIndex::strands_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq
     return any_status(st.data(), m);
 }
 
+void FmIndex::check_hamming(bool packed, uint32_t max_mismatches) const
+{
+    if (view_.text_units == nullptr)
+        fail(GDX_ERR_UNSUPPORTED, "the index holds no text units (gdx_build_options_t.text_units): there is no text to compare with");
+    if (packed && (view_.layout != 0 || view_.n_searchable < 4))
+        fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
+    if (max_mismatches > 0x80000000u) fail(GDX_ERR_INVALID_ARGUMENT, "max_mismatches must be at most 2^31");
+}
+
+int FmIndex::hamming_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint32_t *cand_query, const uint32_t *cand_begin,
+                          const gdx_hit_t *cand_hits, uint64_t m, uint32_t max_mismatches, uint32_t *out) const
+{
+    check_hamming(false, max_mismatches);
+    check_queries(qbuf, qoff, nq);
+    if (m == 0) return GDX_OK;
+    if (!cand_query || !cand_begin || !cand_hits || !out) fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+    if (nq == 0) {  // every candidate is out of range
+        for (uint64_t c = 0; c < m; c++) out[c] = GDX_HAMMING_INVALID;
+        return GDX_OK;
+    }
+    for (uint64_t i = 0; i < nq; i++)
+        if (qoff[i + 1] - qoff[i] > 0xffffffffull)
+            fail(GDX_ERR_INVALID_ARGUMENT, "query %llu is longer than 2^32 - 1 symbols", (unsigned long long)i);
+    std::vector<gdx_hit32_t> narrow(m);
+    for (uint64_t c = 0; c < m; c++) {
+        if (cand_query[c] >= nq)
+            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu belongs to query %u of %llu", (unsigned long long)c, cand_query[c],
+                 (unsigned long long)nq);
+        if (cand_hits[c].text_id >= n_texts_)
+            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu lies in text %llu of %llu", (unsigned long long)c,
+                 (unsigned long long)cand_hits[c].text_id, (unsigned long long)n_texts_);
+        if (cand_hits[c].position > 0xffffffffull)
+            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu: position %llu does not fit 32 bits", (unsigned long long)c,
+                 (unsigned long long)cand_hits[c].position);
+        narrow[c].text_id = static_cast<uint32_t>(cand_hits[c].text_id);
+        narrow[c].position = static_cast<uint32_t>(cand_hits[c].position);
+    }
+    make_current();
+    hipStream_t stream = hipStreamPerThread;
+    DeviceQueries dq(qbuf, qoff, nq, stream);
+    DeviceBuffer<uint32_t> d_query(m), d_begin(m), d_out(m);
+    DeviceBuffer<gdx_hit32_t> d_hits(m);
+    GDX_HIP(hipMemcpyAsync(d_query.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_begin.get(), cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
+    launch_hamming(view_, dq.qbuf.get(), dq.qoff.get(), nq, false, 0, d_query.get(), d_begin.get(), d_hits.get(), m, max_mismatches,
+                   d_out.get(), stream);
+    GDX_HIP(hipGetLastError());
+    GDX_HIP(hipMemcpyAsync(out, d_out.get(), m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipStreamSynchronize(stream));
+    return GDX_OK;
+}
+
 int FmIndex::rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const
 {
     if (m == 0) return GDX_OK;

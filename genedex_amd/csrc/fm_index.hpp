@@ -141,6 +141,11 @@ public:
     // the device, search 2 nq rows, copy out); complement: 256 bytes or null (the stock table).  out_hit_offsets == null: counts only
     int strands_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint8_t *complement, uint64_t *out_counts,
                      uint64_t *out_hit_offsets, gdx_hit_t **out_hits, uint64_t *out_total, uint8_t *out_status) const;
+    // gdx_hamming_many: the whole batch staged (copy queries and candidates in, one launch, copy out); hits narrowed to 32 bits
+    int hamming_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint32_t *cand_query, const uint32_t *cand_begin,
+                     const gdx_hit_t *cand_hits, uint64_t m, uint32_t max_mismatches, uint32_t *out) const;
+    // what both forms of gdx_hamming_many refuse before they look at the batch (text units, packed queries, the limit)
+    void check_hamming(bool packed, uint32_t max_mismatches) const;
     int rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const;
     int symbol_at_many(const uint64_t *idx, uint64_t m, uint8_t *out) const;
 

@@ -171,6 +171,14 @@ void launch_strands_expand(const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64
                            uint64_t total_symbols, const uint8_t *complement, uint32_t mode, void *d_out_qbuf,
                            uint64_t *d_out_qoff, hipStream_t stream);
 
+// ---- hamming.hip --------------------------------------------------------------------------
+// gdx_hamming_many_dev: per candidate (query, seed begin, located hit) the Hamming distance of the whole read against its
+// text on the seed's diagonal, capped at max_mismatches + 1; GDX_HAMMING_INVALID for a query or text id out of range.  The
+// batch in any of the four layouts (uniform_len != 0: d_qoff unused).  ix must hold text units.  One launch.
+void launch_hamming(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq, bool packed,
+                    uint32_t uniform_len, const uint32_t *d_cand_query, const uint32_t *d_cand_begin,
+                    const gdx_hit32_t *d_cand_hits, uint64_t m, uint32_t max_mismatches, uint32_t *d_out, hipStream_t stream);
+
 // ---- locate.hip ---------------------------------------------------------------------------
 size_t hit_offsets_temp_bytes(uint64_t m);
 void launch_hit_offsets(const uint32_t *d_start, const uint32_t *d_end, uint64_t m, uint64_t *d_hit_offsets,

@@ -442,6 +442,28 @@ class DeviceEngine:
             _ptr(out["remaining"]), _ptr(out["begin"]), _ptr(out["length"]), _ptr(out["start"]), _ptr(out["end"]),
             _ptr(out["status"]) if out.get("status") is not None else None, _stream()))
 
+    # ---- Hamming verification of located seeds (gdx_hamming_many_dev) ---------------------------------------
+    def hamming(self, q: DeviceQueries, cand_query: torch.Tensor, cand_begin: torch.Tensor, cand_hits: torch.Tensor,
+                max_mismatches: int, out: torch.Tensor = None) -> torch.Tensor:
+        """One launch: per candidate the mismatches of the whole query against its text on the seed's diagonal, capped at
+        max_mismatches + 1, into `out` (u32 values in an int32 tensor of m entries; made here when None).  q in any of the four
+        forms (a batch made by with_strands goes straight in); cand_query / cand_begin: int32[m] holding u32 values; cand_hits:
+        int32[m, 2] = (text_id, position), the hits tensor of locate().  A candidate whose query or text id is out of range
+        gets -1 (GDX_HAMMING_INVALID)."""
+        m = cand_query.numel()
+        if cand_begin.numel() != m or cand_hits.numel() != 2 * m:
+            raise ValueError("cand_query, cand_begin and cand_hits differ in length")
+        for t in (cand_query, cand_begin, cand_hits):
+            if t.element_size() != 4 or not t.is_contiguous():
+                raise ValueError("candidates are contiguous 32-bit tensors")
+        if out is None:
+            out = torch.empty(max(m, 1), dtype=torch.int32, device=self.dev)
+        lay, qoff = q.layout()
+        _lib.check(self.lib.gdx_hamming_many_dev(self.h, _ptr(q.qbuf), qoff, q.nq, C.byref(lay) if lay is not None else None,
+                                                 _ptr(cand_query), _ptr(cand_begin), _ptr(cand_hits), m, int(max_mismatches),
+                                                 _ptr(out), _stream()))
+        return out
+
     def search_step_stats(self, q: DeviceQueries):
         """(LF steps, line fetches of all queries, fetch slots their wavefronts spent)"""
         steps = torch.zeros(3, dtype=torch.int64, device=self.dev)

@@ -589,6 +589,36 @@ class FmIndex:
         rows = [[Hit(t[h], p[h]) for h in range(int(off[r]), int(off[r + 1]))] for r in range(2 * (qoff.size - 1))]
         return [(rows[2 * i], rows[2 * i + 1]) for i in range(qoff.size - 1)]
 
+    # ---- Hamming verification of located seeds (gdx.h "Hamming verification") ---------------------------
+    def hamming_raw(self, qbuf, qoff, cand_query, cand_begin, text_ids, positions, max_mismatches):
+        """gdx_hamming_many -> u32[m]: per candidate (query, where its seed begins in the query, the (text_id, position) the
+        seed was located at) the mismatches of the whole query against its text on that diagonal, capped at
+        max_mismatches + 1 (include/gdx.h has the definition)."""
+        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
+        qoff = np.ascontiguousarray(qoff, dtype=np.uint64)
+        cq = np.ascontiguousarray(cand_query, dtype=np.uint32)
+        cb = np.ascontiguousarray(cand_begin, dtype=np.uint32)
+        m = cq.size
+        hits = np.zeros((max(m, 1), 2), dtype=np.uint64)
+        hits[:m, 0] = text_ids
+        hits[:m, 1] = positions
+        if cb.size != m:
+            raise ValueError("cand_query and cand_begin differ in length")
+        out = np.zeros(max(m, 1), dtype=np.uint32)
+        _lib.check(self._lib.gdx_hamming_many(self._h, _p(qbuf, u8p), _p(qoff, u64p), qoff.size - 1, _p(cq, u32p), _p(cb, u32p),
+                                              hits.ctypes.data_as(C.POINTER(_lib.HitStruct)), m, int(max_mismatches), _p(out, u32p)))
+        return out[:m]
+
+    def hamming_many(self, queries, cand_query, cand_begin, hits, max_mismatches):
+        """uint32 array, one entry per candidate: candidate c says that the seed of queries[cand_query[c]] that begins at
+        symbol cand_begin[c] was located at hits[c] (a Hit, or any (text_id, position) pair -- what Cursor.locate() gives for
+        an Smem's or a Segment's cursor); the entry is the number of mismatches of the WHOLE query against that text on the
+        seed's diagonal, min(dist, max_mismatches + 1).  Symbols that hang over an end of the text, N and bytes outside the
+        alphabet count as mismatches."""
+        qbuf, qoff = pack_queries(queries)
+        h = np.asarray([tuple(x) for x in hits], dtype=np.uint64).reshape(-1, 2)
+        return self.hamming_raw(qbuf, qoff, cand_query, cand_begin, h[:, 0], h[:, 1], max_mismatches)
+
     def cursor_empty(self) -> "Cursor":
         s = C.c_uint64(0)
         e = C.c_uint64(0)

@@ -625,6 +625,50 @@ int gdx_locate_many_alloc_strands(const gdx_index_t *ix, const uint8_t *qbuf, co
                                   const uint8_t *complement, uint64_t *out_hit_offsets /*2 nq + 1*/, gdx_hit_t **out_hits,
                                   uint64_t *out_total, uint8_t *out_status /*2 nq or NULL*/);
 
+/* ---- Hamming verification of located seeds against the text (seed and verify) -----------------------------------------
+ * A seed q[b, b + len) of a read q -- an SMEM, a suffix segment -- was located at (text_id, position) by
+ * gdx_cursor_locate_many.  How many mismatches does the WHOLE read have against the text on that diagonal, i.e. against
+ * text[text_id][position - b, position - b + |q|)?  The call answers that from the text the index already holds
+ * (gdx_build_options_t.text_units, 4 bits per symbol; the default shape has them), so the caller needs no copy of the texts.
+ * Nothing here walks the index, backtracks or enumerates intervals: it is a gather and compare over candidates the caller
+ * already has.
+ * Inputs: a batch of nq queries in any of the four forms of gdx_query_layout_t (plain or packed, offsets or uniform; same
+ * alignment rules as the search calls) and m candidates; candidate c is cand_query[c] (u32: the query it belongs to),
+ * cand_begin[c] (u32: where the seed begins in the query) and cand_hits[c] ({text_id, position}: where that seed was
+ * located, exactly what gdx_cursor_locate_many returns for the seed's cursor).
+ * Let q be the query, L its length, T the text text_id of length |T| (sentinel excluded) and
+ * s = (int64) position - (int64) cand_begin.  Query symbol j, 0 <= j < L, MATCHES when all three hold:
+ *     0 <= s + j < |T|,
+ *     dense(q[j]) is one of the dense codes 1..4,
+ *     dense(T[s + j]) == dense(q[j]).
+ * Everything else is a mismatch: a read symbol that hangs over either end of its text (even where a neighbouring text
+ * would continue the match), N or any other symbol outside 1..4 on either side, a byte outside the alphabet.  This is the
+ * rule of the search, where a non-searchable symbol never matches, carried over to verification.  There is no per-query
+ * status and no GDX_Q_INVALID_SYMBOL: the output is a pure function of the bytes.
+ * dist = the number of mismatches; out[c] = min(dist, max_mismatches + 1), so a kernel may stop a candidate as soon as it
+ * exceeds the limit, and the output does not depend on where it stopped.  L == 0 gives 0.  cand_begin may exceed L and
+ * position may be any u32: only the arithmetic above applies.
+ * GDX_HAMMING_INVALID is written for a candidate with cand_query >= nq or text_id >= num_texts by the device form, which
+ * cannot report an argument error without synchronising and returns GDX_OK (as gdx_rank_many_dev does); the host form returns
+ * GDX_ERR_INVALID_ARGUMENT instead, also for a position of 2^32 or more.  Packed batches follow the usual rule: the
+ * exceptions of the packed form are the caller's business, and their results are meaningless.
+ * Host form: plain queries only (each shorter than 2^32 symbols); stages the whole batch (copy in, one launch, copy out; no
+ * chunked pipeline) like gdx_suffix_segments_many and narrows gdx_hit_t to 32 bits on the way in.  Device form: d_qoff
+ * u64[nq + 1] (unused for a uniform batch), queries shorter than 2^32 symbols; ONE launch, no synchronisation, no allocation,
+ * no copy from pageable memory.
+ * GDX_ERR_UNSUPPORTED: an index without text units, a handle of the 64-bit engine, the packed form on an index that does not
+ * take packed queries.  GDX_ERR_INVALID_ARGUMENT: max_mismatches > 2^31, an unknown layout.  m == 0 is GDX_OK; so is
+ * nq == 0, where every candidate is out of range: the device form writes GDX_HAMMING_INVALID m times and the host form does
+ * the same instead of failing.  gdx_parts_t and gdx_multi_t have no such call. */
+#define GDX_HAMMING_INVALID 0xFFFFFFFFu
+int gdx_hamming_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
+                         const gdx_query_layout_t *layout, const void *d_cand_query /*u32[m]*/,
+                         const void *d_cand_begin /*u32[m]*/, const void *d_cand_hits /*gdx_hit32_t[m]*/, uint64_t m,
+                         uint32_t max_mismatches, void *d_out /*u32[m]*/, void *stream);
+int gdx_hamming_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq,
+                     const uint32_t *cand_query, const uint32_t *cand_begin, const gdx_hit_t *cand_hits, uint64_t m,
+                     uint32_t max_mismatches, uint32_t *out);
+
 /* ---- batched cursor extension by strings (Cursor::extend_query_front, cursor.rs:34-51, applied to every symbol of
  * a string from its last to its first; ROADMAP.md:33 "API to use batched search with cursors") --------------------
  * Cursor i is extended by string i = d_qbuf[d_qbeg[i] .. d_qend[i]) (for a plain offsets array pass d_qoff and
