@@ -134,6 +134,10 @@ pub const GDX_ERR_CAPACITY: c_int = 5;
 pub const GDX_ERR_QUERY_STATUS: c_int = 6;
 pub const GDX_SEGMENTS_LF_ONLY: u32 = 1;
 pub const GDX_HAMMING_INVALID: u32 = 0xFFFF_FFFF;
+pub const GDX_EDIT_MAX_QUERY_LEN: u32 = 256;
+pub const GDX_EDIT_INVALID: u32 = 0xFFFF_FFFF;
+pub const GDX_EDIT_TOO_LONG: u32 = 0xFFFF_FFFE;
+pub const GDX_EDIT_NO_END: u32 = 0xFFFF_FFFF;
 
 /// gdx_query_layout_t
 #[repr(C)]
@@ -267,6 +271,18 @@ extern "C" {
     pub fn gdx_hamming_many(
         ix: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, cand_query: *const u32, cand_begin: *const u32,
         cand_hits: *const Hit, m: u64, max_mismatches: u32, out: *mut u32,
+    ) -> c_int;
+    /// Edit-distance verification of located seeds (include/gdx.h "edit-distance verification"): per candidate the infix
+    /// edit distance of the whole read against its text within max_edits of the seed's diagonal, capped at max_edits + 1, and
+    /// the exclusive end of the leftmost best alignment (d_out_end / out_end may be null)
+    pub fn gdx_edit_distance_many_dev(
+        ix: *const gdx_index_t, d_qbuf: *const c_void, d_qoff: *const c_void, nq: u64, layout: *const QueryLayout,
+        d_cand_query: *const c_void, d_cand_begin: *const c_void, d_cand_hits: *const c_void, m: u64, max_edits: u32,
+        d_out_dist: *mut c_void, d_out_end: *mut c_void, stream: *mut c_void,
+    ) -> c_int;
+    pub fn gdx_edit_distance_many(
+        ix: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, cand_query: *const u32, cand_begin: *const u32,
+        cand_hits: *const Hit, m: u64, max_edits: u32, out_dist: *mut u32, out_end: *mut u32,
     ) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
@@ -729,6 +745,26 @@ impl GpuFmIndex {
                              cand_hits.as_ptr(), cand_query.len() as u64, max_mismatches, out.as_mut_ptr())
         });
         out
+    }
+
+    /// Seed and verify with indels: for the candidates of `hamming_many`, (dist, end) per candidate.  dist is the least number
+    /// of substitutions, insertions and deletions that turn the WHOLE query (at most 256 symbols; longer ones get
+    /// GDX_EDIT_TOO_LONG) into a piece of its text within `max_edits` (at most 256) of the seed's diagonal,
+    /// min(dist, max_edits + 1); end is where the leftmost best such piece ends (exclusive), GDX_EDIT_NO_END when
+    /// dist > max_edits.  Panics like `hamming_many`.
+    pub fn edit_distance_many<Q: AsRef<[u8]>>(
+        &self, queries: impl IntoIterator<Item = Q>, cand_query: &[u32], cand_begin: &[u32], cand_hits: &[Hit], max_edits: u32,
+    ) -> (Vec<u32>, Vec<u32>) {
+        assert!(cand_query.len() == cand_begin.len() && cand_query.len() == cand_hits.len());
+        let (buf, off) = pack(queries);
+        let mut dist = vec![0u32; cand_query.len()];
+        let mut end = vec![0u32; cand_query.len()];
+        check(unsafe {
+            gdx_edit_distance_many(self.raw, buf.as_ptr(), off.as_ptr(), (off.len() - 1) as u64, cand_query.as_ptr(),
+                                   cand_begin.as_ptr(), cand_hits.as_ptr(), cand_query.len() as u64, max_edits, dist.as_mut_ptr(),
+                                   end.as_mut_ptr())
+        });
+        (dist, end)
     }
 }
 

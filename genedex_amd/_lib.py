@@ -31,6 +31,10 @@ GDX_SEGMENTS_LF_ONLY = 1  # flags of gdx_suffix_segments_many[_dev]
 GDX_STRANDS_REVERSE = 1   # modes of gdx_strands_expand_dev
 GDX_STRANDS_BOTH = 2
 GDX_HAMMING_INVALID = 0xFFFFFFFF  # gdx_hamming_many_dev: a candidate whose query or text id is out of range
+GDX_EDIT_MAX_QUERY_LEN = 256      # gdx_edit_distance_many[_dev]: longer queries get GDX_EDIT_TOO_LONG
+GDX_EDIT_INVALID = 0xFFFFFFFF     # dist: a candidate whose query or text id is out of range (device form)
+GDX_EDIT_TOO_LONG = 0xFFFFFFFE    # dist: the candidate's query has more than GDX_EDIT_MAX_QUERY_LEN symbols
+GDX_EDIT_NO_END = 0xFFFFFFFF      # end: whenever dist is not a distance <= max_edits
 GDX_Q_OK = 0
 GDX_Q_INVALID_SYMBOL = 1
 GDX_Q_UNSEARCHABLE_IN_LOOKUP = 2
@@ -233,6 +237,8 @@ SIGNATURES = {
     "gdx_locate_many_alloc_strands": [vp, u8p, u64p, C.c_uint64, u8p, u64p, C.POINTER(C.POINTER(HitStruct)), u64p, u8p],
     "gdx_hamming_many_dev": [vp, vp, vp, C.c_uint64, C.POINTER(QueryLayout), vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp],
     "gdx_hamming_many": [vp, u8p, u64p, C.c_uint64, u32p, u32p, C.POINTER(HitStruct), C.c_uint64, C.c_uint32, u32p],
+    "gdx_edit_distance_many_dev": [vp, vp, vp, C.c_uint64, C.POINTER(QueryLayout), vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp],
+    "gdx_edit_distance_many": [vp, u8p, u64p, C.c_uint64, u32p, u32p, C.POINTER(HitStruct), C.c_uint64, C.c_uint32, u32p, u32p],
     # gdx_bench.h
     "gdx_index_build_stats": [vp, C.POINTER(BuildStats)],
     "gdx_synth_text_dev": [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp],

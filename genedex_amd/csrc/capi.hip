@@ -1769,6 +1769,38 @@ int gdx_hamming_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t 
     return guarded([&] { return deref(ix).hamming_many(qbuf, qoff, nq, cand_query, cand_begin, cand_hits, m, max_mismatches, out); });
 }
 
+// ---- edit-distance verification of located seeds (edit_distance.hip) ---------------------------------------------
+
+int gdx_edit_distance_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
+                               const gdx_query_layout_t *layout, const void *d_cand_query, const void *d_cand_begin,
+                               const void *d_cand_hits, uint64_t m, uint32_t max_edits, void *d_out_dist, void *d_out_end, void *stream)
+{
+    return guarded([&] {
+        const gdx::FmIndex &f = deref(ix);
+        gdx::SearchCall c;  // (the layout's checks: struct size, alignment of d_qbuf, offsets of a batch that is not uniform)
+        apply_layout(c, d_qbuf, d_qoff, nq, layout);
+        f.check_edit_distance(c.packed, max_edits);
+        if (m == 0) return (int)GDX_OK;
+        if (!d_cand_query || !d_cand_begin || !d_cand_hits || !d_out_dist) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+        if (nq != 0 && !d_qbuf) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf is null");
+        DeviceGuard guard(f.config().device_id);
+        gdx::launch_edit_distance(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, static_cast<const uint32_t *>(d_cand_query),
+                                  static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits), m,
+                                  max_edits, static_cast<uint32_t *>(d_out_dist), static_cast<uint32_t *>(d_out_end), as_stream(stream));
+        GDX_HIP(hipGetLastError());
+        return (int)GDX_OK;
+    });
+}
+
+int gdx_edit_distance_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint32_t *cand_query,
+                           const uint32_t *cand_begin, const gdx_hit_t *cand_hits, uint64_t m, uint32_t max_edits, uint32_t *out_dist,
+                           uint32_t *out_end)
+{
+    return guarded([&] {
+        return deref(ix).edit_distance_many(qbuf, qoff, nq, cand_query, cand_begin, cand_hits, m, max_edits, out_dist, out_end);
+    });
+}
+
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {

@@ -2355,6 +2355,59 @@ int FmIndex::hamming_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq
     return GDX_OK;
 }
 
+void FmIndex::check_edit_distance(bool packed, uint32_t max_edits) const
+{
+    check_hamming(packed, 0);
+    if (max_edits > GDX_EDIT_MAX_QUERY_LEN)
+        fail(GDX_ERR_INVALID_ARGUMENT, "max_edits must be at most %u (no distance exceeds the longest query)", GDX_EDIT_MAX_QUERY_LEN);
+}
+
+int FmIndex::edit_distance_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint32_t *cand_query,
+                                const uint32_t *cand_begin, const gdx_hit_t *cand_hits, uint64_t m, uint32_t max_edits,
+                                uint32_t *out_dist, uint32_t *out_end) const
+{
+    check_edit_distance(false, max_edits);
+    check_queries(qbuf, qoff, nq);
+    if (m == 0) return GDX_OK;
+    if (!cand_query || !cand_begin || !cand_hits || !out_dist) fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+    if (nq == 0) {  // every candidate is out of range
+        for (uint64_t c = 0; c < m; c++) {
+            out_dist[c] = GDX_EDIT_INVALID;
+            if (out_end) out_end[c] = GDX_EDIT_NO_END;
+        }
+        return GDX_OK;
+    }
+    std::vector<gdx_hit32_t> narrow(m);
+    for (uint64_t c = 0; c < m; c++) {
+        if (cand_query[c] >= nq)
+            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu belongs to query %u of %llu", (unsigned long long)c, cand_query[c],
+                 (unsigned long long)nq);
+        if (cand_hits[c].text_id >= n_texts_)
+            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu lies in text %llu of %llu", (unsigned long long)c,
+                 (unsigned long long)cand_hits[c].text_id, (unsigned long long)n_texts_);
+        if (cand_hits[c].position > 0xffffffffull)
+            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu: position %llu does not fit 32 bits", (unsigned long long)c,
+                 (unsigned long long)cand_hits[c].position);
+        narrow[c].text_id = static_cast<uint32_t>(cand_hits[c].text_id);
+        narrow[c].position = static_cast<uint32_t>(cand_hits[c].position);
+    }
+    make_current();
+    hipStream_t stream = hipStreamPerThread;
+    DeviceQueries dq(qbuf, qoff, nq, stream);
+    DeviceBuffer<uint32_t> d_query(m), d_begin(m), d_dist(m), d_end(out_end ? m : 0);
+    DeviceBuffer<gdx_hit32_t> d_hits(m);
+    GDX_HIP(hipMemcpyAsync(d_query.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_begin.get(), cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
+    launch_edit_distance(view_, dq.qbuf.get(), dq.qoff.get(), nq, false, 0, d_query.get(), d_begin.get(), d_hits.get(), m, max_edits,
+                         d_dist.get(), out_end ? d_end.get() : nullptr, stream);
+    GDX_HIP(hipGetLastError());
+    GDX_HIP(hipMemcpyAsync(out_dist, d_dist.get(), m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (out_end) GDX_HIP(hipMemcpyAsync(out_end, d_end.get(), m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipStreamSynchronize(stream));
+    return GDX_OK;
+}
+
 int FmIndex::rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const
 {
     if (m == 0) return GDX_OK;

@@ -146,6 +146,12 @@ public:
                      const gdx_hit_t *cand_hits, uint64_t m, uint32_t max_mismatches, uint32_t *out) const;
     // what both forms of gdx_hamming_many refuse before they look at the batch (text units, packed queries, the limit)
     void check_hamming(bool packed, uint32_t max_mismatches) const;
+    // gdx_edit_distance_many: staged like hamming_many; out_end may be null
+    int edit_distance_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint32_t *cand_query,
+                           const uint32_t *cand_begin, const gdx_hit_t *cand_hits, uint64_t m, uint32_t max_edits, uint32_t *out_dist,
+                           uint32_t *out_end) const;
+    // what both forms of gdx_edit_distance_many refuse before they look at the batch (check_hamming's, and the limit)
+    void check_edit_distance(bool packed, uint32_t max_edits) const;
     int rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const;
     int symbol_at_many(const uint64_t *idx, uint64_t m, uint8_t *out) const;
 

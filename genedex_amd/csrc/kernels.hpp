@@ -179,6 +179,16 @@ void launch_hamming(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *
                     uint32_t uniform_len, const uint32_t *d_cand_query, const uint32_t *d_cand_begin,
                     const gdx_hit32_t *d_cand_hits, uint64_t m, uint32_t max_mismatches, uint32_t *d_out, hipStream_t stream);
 
+// ---- edit_distance.hip --------------------------------------------------------------------
+// gdx_edit_distance_many_dev: per candidate the infix edit distance of the whole read (at most GDX_EDIT_MAX_QUERY_LEN symbols)
+// against its text within max_edits (<= 256) of the seed's diagonal, capped at max_edits + 1, and where the best alignment ends
+// (d_out_end may be null); GDX_EDIT_INVALID for a query or text id out of range, GDX_EDIT_TOO_LONG for a longer read.  The batch
+// in any of the four layouts (uniform_len != 0: d_qoff unused).  ix must hold text units.  One launch.
+void launch_edit_distance(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq, bool packed,
+                          uint32_t uniform_len, const uint32_t *d_cand_query, const uint32_t *d_cand_begin,
+                          const gdx_hit32_t *d_cand_hits, uint64_t m, uint32_t max_edits, uint32_t *d_out_dist,
+                          uint32_t *d_out_end, hipStream_t stream);
+
 // ---- locate.hip ---------------------------------------------------------------------------
 size_t hit_offsets_temp_bytes(uint64_t m);
 void launch_hit_offsets(const uint32_t *d_start, const uint32_t *d_end, uint64_t m, uint64_t *d_hit_offsets,

@@ -464,6 +464,30 @@ class DeviceEngine:
                                                  _ptr(out), _stream()))
         return out
 
+    # ---- edit-distance verification of located seeds (gdx_edit_distance_many_dev) ----------------------------
+    def edit_distance(self, q: DeviceQueries, cand_query: torch.Tensor, cand_begin: torch.Tensor, cand_hits: torch.Tensor,
+                      max_edits: int, out_dist: torch.Tensor = None, out_end: torch.Tensor = None, want_end: bool = True):
+        """One launch: per candidate of hamming() the infix edit distance of the whole query (at most 256 symbols) against its
+        text within max_edits of the seed's diagonal, capped at max_edits + 1, into out_dist, and the exclusive end of the
+        leftmost best alignment into out_end (u32 values in int32 tensors of m entries; made here when None; want_end=False
+        with out_end None passes NULL).  -> (out_dist, out_end).  Out-of-range candidates get -1 (GDX_EDIT_INVALID), longer
+        queries -2 (GDX_EDIT_TOO_LONG); out_end is -1 (GDX_EDIT_NO_END) wherever out_dist is not a distance <= max_edits."""
+        m = cand_query.numel()
+        if cand_begin.numel() != m or cand_hits.numel() != 2 * m:
+            raise ValueError("cand_query, cand_begin and cand_hits differ in length")
+        for t in (cand_query, cand_begin, cand_hits):
+            if t.element_size() != 4 or not t.is_contiguous():
+                raise ValueError("candidates are contiguous 32-bit tensors")
+        if out_dist is None:
+            out_dist = torch.empty(max(m, 1), dtype=torch.int32, device=self.dev)
+        if out_end is None and want_end:
+            out_end = torch.empty(max(m, 1), dtype=torch.int32, device=self.dev)
+        lay, qoff = q.layout()
+        _lib.check(self.lib.gdx_edit_distance_many_dev(self.h, _ptr(q.qbuf), qoff, q.nq, C.byref(lay) if lay is not None else None,
+                                                       _ptr(cand_query), _ptr(cand_begin), _ptr(cand_hits), m, int(max_edits),
+                                                       _ptr(out_dist), _ptr(out_end) if out_end is not None else None, _stream()))
+        return out_dist, out_end
+
     def search_step_stats(self, q: DeviceQueries):
         """(LF steps, line fetches of all queries, fetch slots their wavefronts spent)"""
         steps = torch.zeros(3, dtype=torch.int64, device=self.dev)

@@ -619,6 +619,38 @@ class FmIndex:
         h = np.asarray([tuple(x) for x in hits], dtype=np.uint64).reshape(-1, 2)
         return self.hamming_raw(qbuf, qoff, cand_query, cand_begin, h[:, 0], h[:, 1], max_mismatches)
 
+    # ---- edit-distance verification of located seeds (gdx.h "edit-distance verification") ----------------
+    def edit_distance_raw(self, qbuf, qoff, cand_query, cand_begin, text_ids, positions, max_edits, want_end=True):
+        """gdx_edit_distance_many -> (dist u32[m], end u32[m] or None): per candidate of hamming_raw the infix edit distance of
+        the whole query against its text within max_edits of the seed's diagonal, capped at max_edits + 1, and the exclusive end
+        of the leftmost best alignment in that text (include/gdx.h has the definition)."""
+        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
+        qoff = np.ascontiguousarray(qoff, dtype=np.uint64)
+        cq = np.ascontiguousarray(cand_query, dtype=np.uint32)
+        cb = np.ascontiguousarray(cand_begin, dtype=np.uint32)
+        m = cq.size
+        hits = np.zeros((max(m, 1), 2), dtype=np.uint64)
+        hits[:m, 0] = text_ids
+        hits[:m, 1] = positions
+        if cb.size != m:
+            raise ValueError("cand_query and cand_begin differ in length")
+        dist = np.zeros(max(m, 1), dtype=np.uint32)
+        end = np.zeros(max(m, 1), dtype=np.uint32) if want_end else None
+        _lib.check(self._lib.gdx_edit_distance_many(self._h, _p(qbuf, u8p), _p(qoff, u64p), qoff.size - 1, _p(cq, u32p), _p(cb, u32p),
+                                                    hits.ctypes.data_as(C.POINTER(_lib.HitStruct)), m, int(max_edits), _p(dist, u32p),
+                                                    _p(end, u32p) if want_end else None))
+        return dist[:m], (end[:m] if want_end else None)
+
+    def edit_distance_many(self, queries, cand_query, cand_begin, hits, max_edits):
+        """(dist, end), two uint32 arrays with one entry per candidate of hamming_many: dist is the least number of
+        substitutions, insertions and deletions that turn the WHOLE query (at most 256 symbols) into a piece of its text that
+        lies within max_edits of the seed's diagonal, min(dist, max_edits + 1); end is where the leftmost best such piece ends
+        (exclusive, a position in the text), GDX_EDIT_NO_END when dist > max_edits.  A query that hangs over an end of its text
+        pays one edit per overhanging symbol; N and bytes outside the alphabet never match."""
+        qbuf, qoff = pack_queries(queries)
+        h = np.asarray([tuple(x) for x in hits], dtype=np.uint64).reshape(-1, 2)
+        return self.edit_distance_raw(qbuf, qoff, cand_query, cand_begin, h[:, 0], h[:, 1], max_edits)
+
     def cursor_empty(self) -> "Cursor":
         s = C.c_uint64(0)
         e = C.c_uint64(0)

@@ -669,6 +669,50 @@ int gdx_hamming_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t 
                      const uint32_t *cand_query, const uint32_t *cand_begin, const gdx_hit_t *cand_hits, uint64_t m,
                      uint32_t max_mismatches, uint32_t *out);
 
+/* ---- edit-distance verification of located seeds (seed and verify, with insertions and deletions) ---------------------
+ * gdx_hamming_many ends at substitutions: one inserted or deleted symbol shifts the rest of the read off the diagonal and
+ * the candidate looks hopeless.  This call is the same gather and compare -- the text the index already holds, candidates
+ * the caller already has, nothing walks the index -- with a compare that tolerates indels.
+ * Inputs and candidates are exactly those of gdx_hamming_many: any of the four query layouts, cand_query / cand_begin /
+ * cand_hits.  Let q be the query and L its length, T the text text_id and |T| its length (sentinel excluded),
+ * k = max_edits and s = (int64) position - (int64) cand_begin.  The WINDOW is T[x0, x1) with
+ *     x0 = clamp(s - k, 0, |T|),   x1 = clamp(s + L + k, 0, |T|)            (computed in int64).
+ * A read symbol and a text symbol MATCH when both have the same dense code and that code is one of 1..4 (the Hamming rule:
+ * N, the sentinel and bytes outside the alphabet never match, on either side).
+ *     dist = min over x0 <= x <= y <= x1 of the unit-cost edit distance between q and T[x, y)
+ * (substitution 1, insertion 1, deletion 1; a pair that matches 0, a pair that does not 1).  This is the infix
+ * ("semi-global") distance: text of the window left unaligned on either side of the read is free.
+ *     out_dist[c] = min(dist, k + 1)
+ *     out_end[c]  = the smallest y for which some x gives ed(q, T[x, y)) = dist, when dist <= k; else GDX_EDIT_NO_END
+ * out_end is a position in text text_id and an exclusive end; d_out_end / out_end may be NULL.  L == 0 gives dist 0 and end
+ * x0.  An empty window (an empty text, a diagonal far outside the text) gives dist L.  The window is clipped to the text's
+ * own bounds: a read that hangs over an end pays one insertion per overhanging symbol, and a neighbouring text never
+ * continues an alignment.  It follows that dist <= the Hamming distance of the same candidate, and that with k = 0
+ * out_dist = min(Hamming distance, 1).
+ * A query of more than GDX_EDIT_MAX_QUERY_LEN symbols gets GDX_EDIT_TOO_LONG and GDX_EDIT_NO_END in both forms and the call
+ * stays GDX_OK: it is a limit of the implementation, not an argument error, and one long read must not fail a batch.
+ * Candidates out of range follow gdx_hamming_many: the device form writes GDX_EDIT_INVALID and GDX_EDIT_NO_END for
+ * cand_query >= nq or text_id >= num_texts and returns GDX_OK; the host form returns GDX_ERR_INVALID_ARGUMENT, also for a
+ * position of 2^32 or more; with nq == 0 both forms write GDX_EDIT_INVALID (and GDX_EDIT_NO_END) m times.  m == 0 is GDX_OK.
+ * GDX_ERR_INVALID_ARGUMENT: max_edits > 256 (dist never exceeds L <= 256, so a larger limit says nothing), an unknown layout.
+ * GDX_ERR_UNSUPPORTED: an index without text units, a handle of the 64-bit engine, the packed form on an index that does
+ * not take packed queries.  A refused call writes nothing.
+ * Device form: ONE launch, no synchronisation, no allocation, no copy from pageable memory.  Host form: plain queries only;
+ * stages the whole batch (copy in, one launch, copy out) like gdx_hamming_many and narrows gdx_hit_t to 32 bits.
+ * Out of scope: where the alignment starts, CIGAR / traceback, affine gaps, reads of more than 256 symbols; gdx_parts_t and
+ * gdx_multi_t have no such call. */
+#define GDX_EDIT_MAX_QUERY_LEN 256u
+#define GDX_EDIT_INVALID  0xFFFFFFFFu   /* dist: cand_query >= nq or text_id >= num_texts (device form) */
+#define GDX_EDIT_TOO_LONG 0xFFFFFFFEu   /* dist: the candidate's query has more than 256 symbols        */
+#define GDX_EDIT_NO_END   0xFFFFFFFFu   /* end:  whenever dist is not a distance <= max_edits           */
+int gdx_edit_distance_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
+                               const gdx_query_layout_t *layout, const void *d_cand_query /*u32[m]*/,
+                               const void *d_cand_begin /*u32[m]*/, const void *d_cand_hits /*gdx_hit32_t[m]*/, uint64_t m,
+                               uint32_t max_edits, void *d_out_dist /*u32[m]*/, void *d_out_end /*u32[m] or NULL*/, void *stream);
+int gdx_edit_distance_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq,
+                           const uint32_t *cand_query, const uint32_t *cand_begin, const gdx_hit_t *cand_hits, uint64_t m,
+                           uint32_t max_edits, uint32_t *out_dist, uint32_t *out_end /*or NULL*/);
+
 /* ---- batched cursor extension by strings (Cursor::extend_query_front, cursor.rs:34-51, applied to every symbol of
  * a string from its last to its first; ROADMAP.md:33 "API to use batched search with cursors") --------------------
  * Cursor i is extended by string i = d_qbuf[d_qbeg[i] .. d_qend[i]) (for a plain offsets array pass d_qoff and
