@@ -138,6 +138,10 @@ pub const GDX_EDIT_MAX_QUERY_LEN: u32 = 256;
 pub const GDX_EDIT_INVALID: u32 = 0xFFFF_FFFF;
 pub const GDX_EDIT_TOO_LONG: u32 = 0xFFFF_FFFE;
 pub const GDX_EDIT_NO_END: u32 = 0xFFFF_FFFF;
+pub const GDX_CIGAR_INS: u32 = 1;
+pub const GDX_CIGAR_DEL: u32 = 2;
+pub const GDX_CIGAR_EQ: u32 = 7;
+pub const GDX_CIGAR_DIFF: u32 = 8;
 
 /// gdx_query_layout_t
 #[repr(C)]
@@ -283,6 +287,22 @@ extern "C" {
     pub fn gdx_edit_distance_many(
         ix: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, cand_query: *const u32, cand_begin: *const u32,
         cand_hits: *const Hit, m: u64, max_edits: u32, out_dist: *mut u32, out_end: *mut u32,
+    ) -> c_int;
+    /// Alignment traceback of verified seed hits (include/gdx.h "alignment traceback"): per candidate of
+    /// gdx_edit_distance_many its distance and end, where the canonical best alignment begins and its run-length CIGAR
+    /// (2 max_edits + 1 words per candidate, run_length << 4 | GDX_CIGAR_*).  d_workspace null: the size query, which
+    /// writes out_workspace_bytes[0..2] (least, best) and launches nothing
+    pub fn gdx_align_many_dev(
+        ix: *const gdx_index_t, d_qbuf: *const c_void, d_qoff: *const c_void, nq: u64, layout: *const QueryLayout,
+        d_cand_query: *const c_void, d_cand_begin: *const c_void, d_cand_hits: *const c_void, m: u64, max_edits: u32,
+        d_out_dist: *mut c_void, d_out_begin: *mut c_void, d_out_end: *mut c_void, d_out_n_cigar: *mut c_void,
+        d_out_cigar: *mut c_void, d_workspace: *mut c_void, workspace_bytes: u64, out_workspace_bytes: *mut u64,
+        stream: *mut c_void,
+    ) -> c_int;
+    pub fn gdx_align_many(
+        ix: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, cand_query: *const u32, cand_begin: *const u32,
+        cand_hits: *const Hit, m: u64, max_edits: u32, out_dist: *mut u32, out_begin: *mut u32, out_end: *mut u32,
+        out_n_cigar: *mut u32, out_cigar: *mut u32,
     ) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
@@ -434,6 +454,16 @@ fn pack<Q: AsRef<[u8]>>(queries: impl IntoIterator<Item = Q>) -> (Vec<u8>, Vec<u
         off.push(buf.len() as u64);
     }
     (buf, off)
+}
+
+/// One candidate's alignment (`GpuFmIndex::align_many`): `dist` edits; the query against text[span.0 .. span.1) with the
+/// runs `cigar`, each (length, GDX_CIGAR_*), first run of the query first.  `span` is None (and `cigar` empty) when dist is
+/// over the limit or a GDX_EDIT_* marker.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct Alignment {
+    pub dist: u32,
+    pub span: Option<(u32, u32)>,
+    pub cigar: Vec<(u32, u32)>,
 }
 
 /// Hits of one call, owned by the library's allocation; handed out per query without copying.
@@ -765,6 +795,34 @@ impl GpuFmIndex {
                                    end.as_mut_ptr())
         });
         (dist, end)
+    }
+
+    /// The last stage of seed and verify: for the candidates of `edit_distance_many`, one `Alignment` per candidate.  dist is
+    /// what `edit_distance_many` gives; when it is at most `max_edits` (at most 256), `span` is (begin, end) of the canonical
+    /// best alignment in the candidate's text and `cigar` its runs, first run of the query first, each (length, op) with op
+    /// one of GDX_CIGAR_INS / _DEL / _EQ / _DIFF; otherwise `span` is None and `cigar` empty.  Panics like `hamming_many`.
+    pub fn align_many<Q: AsRef<[u8]>>(
+        &self, queries: impl IntoIterator<Item = Q>, cand_query: &[u32], cand_begin: &[u32], cand_hits: &[Hit], max_edits: u32,
+    ) -> Vec<Alignment> {
+        assert!(cand_query.len() == cand_begin.len() && cand_query.len() == cand_hits.len());
+        assert!(max_edits <= GDX_EDIT_MAX_QUERY_LEN);
+        let (buf, off) = pack(queries);
+        let m = cand_query.len();
+        let stride = 2 * max_edits as usize + 1;
+        let (mut dist, mut begin, mut end, mut n_cigar) = (vec![0u32; m], vec![0u32; m], vec![0u32; m], vec![0u32; m]);
+        let mut cigar = vec![0u32; m * stride];
+        check(unsafe {
+            gdx_align_many(self.raw, buf.as_ptr(), off.as_ptr(), (off.len() - 1) as u64, cand_query.as_ptr(), cand_begin.as_ptr(),
+                           cand_hits.as_ptr(), m as u64, max_edits, dist.as_mut_ptr(), begin.as_mut_ptr(), end.as_mut_ptr(),
+                           n_cigar.as_mut_ptr(), cigar.as_mut_ptr())
+        });
+        (0..m)
+            .map(|c| Alignment {
+                dist: dist[c],
+                span: if end[c] == GDX_EDIT_NO_END { None } else { Some((begin[c], end[c])) },
+                cigar: cigar[c * stride..c * stride + n_cigar[c] as usize].iter().map(|w| (w >> 4, w & 15)).collect(),
+            })
+            .collect()
     }
 }
 

@@ -35,6 +35,10 @@ GDX_EDIT_MAX_QUERY_LEN = 256      # gdx_edit_distance_many[_dev]: longer queries
 GDX_EDIT_INVALID = 0xFFFFFFFF     # dist: a candidate whose query or text id is out of range (device form)
 GDX_EDIT_TOO_LONG = 0xFFFFFFFE    # dist: the candidate's query has more than GDX_EDIT_MAX_QUERY_LEN symbols
 GDX_EDIT_NO_END = 0xFFFFFFFF      # end: whenever dist is not a distance <= max_edits
+GDX_CIGAR_INS = 1                 # gdx_align_many[_dev]: the op in the low four bits of a cigar word (BAM's codes)
+GDX_CIGAR_DEL = 2
+GDX_CIGAR_EQ = 7
+GDX_CIGAR_DIFF = 8
 GDX_Q_OK = 0
 GDX_Q_INVALID_SYMBOL = 1
 GDX_Q_UNSEARCHABLE_IN_LOOKUP = 2
@@ -239,6 +243,10 @@ SIGNATURES = {
     "gdx_hamming_many": [vp, u8p, u64p, C.c_uint64, u32p, u32p, C.POINTER(HitStruct), C.c_uint64, C.c_uint32, u32p],
     "gdx_edit_distance_many_dev": [vp, vp, vp, C.c_uint64, C.POINTER(QueryLayout), vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp],
     "gdx_edit_distance_many": [vp, u8p, u64p, C.c_uint64, u32p, u32p, C.POINTER(HitStruct), C.c_uint64, C.c_uint32, u32p, u32p],
+    "gdx_align_many_dev": [vp, vp, vp, C.c_uint64, C.POINTER(QueryLayout), vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp,
+                           vp, C.c_uint64, u64p, vp],
+    "gdx_align_many": [vp, u8p, u64p, C.c_uint64, u32p, u32p, C.POINTER(HitStruct), C.c_uint64, C.c_uint32, u32p, u32p, u32p,
+                       u32p, u32p],
     # gdx_bench.h
     "gdx_index_build_stats": [vp, C.POINTER(BuildStats)],
     "gdx_synth_text_dev": [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp],

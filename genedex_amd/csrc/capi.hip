@@ -1801,6 +1801,55 @@ int gdx_edit_distance_many(const gdx_index_t *ix, const uint8_t *qbuf, const uin
     });
 }
 
+// ---- alignment traceback of verified seed hits (align.hip) -------------------------------------------------------
+
+int gdx_align_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq, const gdx_query_layout_t *layout,
+                       const void *d_cand_query, const void *d_cand_begin, const void *d_cand_hits, uint64_t m, uint32_t max_edits,
+                       void *d_out_dist, void *d_out_begin, void *d_out_end, void *d_out_n_cigar, void *d_out_cigar,
+                       void *d_workspace, uint64_t workspace_bytes, uint64_t *out_workspace_bytes, void *stream)
+{
+    return guarded([&] {
+        const gdx::FmIndex &f = deref(ix);
+        gdx::SearchCall c;
+        if (!d_workspace) {  // the size query: of the batch only the layout counts, no device pointer is looked at
+            apply_layout(c, nullptr, nullptr, 0, layout);
+            f.check_align(c.packed, max_edits);
+            if (out_workspace_bytes) gdx::align_workspace_bytes(c.uniform_len, m, max_edits, out_workspace_bytes);
+            return (int)GDX_OK;
+        }
+        apply_layout(c, d_qbuf, d_qoff, nq, layout);
+        f.check_align(c.packed, max_edits);
+        uint64_t need[2];
+        gdx::align_workspace_bytes(c.uniform_len, m, max_edits, need);
+        if (workspace_bytes < need[0])
+            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "workspace of %llu bytes, at least %llu are needed", (unsigned long long)workspace_bytes,
+                      (unsigned long long)need[0]);
+        if ((reinterpret_cast<uintptr_t>(d_workspace) & 15u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_workspace must be 16-byte aligned");
+        if (!d_out_dist || !d_out_begin || !d_out_end || !d_out_n_cigar || !d_out_cigar) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null output");
+        if (m == 0) return (int)GDX_OK;
+        if (!d_cand_query || !d_cand_begin || !d_cand_hits) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+        if (nq != 0 && !d_qbuf) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf is null");
+        DeviceGuard guard(f.config().device_id);
+        gdx::launch_align(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, static_cast<const uint32_t *>(d_cand_query),
+                          static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits), m, max_edits,
+                          static_cast<uint32_t *>(d_out_dist), static_cast<uint32_t *>(d_out_begin), static_cast<uint32_t *>(d_out_end),
+                          static_cast<uint32_t *>(d_out_n_cigar), static_cast<uint32_t *>(d_out_cigar), d_workspace, workspace_bytes,
+                          as_stream(stream));
+        GDX_HIP(hipGetLastError());
+        return (int)GDX_OK;
+    });
+}
+
+int gdx_align_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint32_t *cand_query,
+                   const uint32_t *cand_begin, const gdx_hit_t *cand_hits, uint64_t m, uint32_t max_edits, uint32_t *out_dist,
+                   uint32_t *out_begin, uint32_t *out_end, uint32_t *out_n_cigar, uint32_t *out_cigar)
+{
+    return guarded([&] {
+        return deref(ix).align_many(qbuf, qoff, nq, cand_query, cand_begin, cand_hits, m, max_edits, out_dist, out_begin, out_end,
+                                    out_n_cigar, out_cigar);
+    });
+}
+
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {

@@ -2408,6 +2408,65 @@ int FmIndex::edit_distance_many(const uint8_t *qbuf, const uint64_t *qoff, uint6
     return GDX_OK;
 }
 
+int FmIndex::align_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint32_t *cand_query, const uint32_t *cand_begin,
+                        const gdx_hit_t *cand_hits, uint64_t m, uint32_t max_edits, uint32_t *out_dist, uint32_t *out_begin,
+                        uint32_t *out_end, uint32_t *out_n_cigar, uint32_t *out_cigar) const
+{
+    check_align(false, max_edits);
+    check_queries(qbuf, qoff, nq);
+    if (!out_dist || !out_begin || !out_end || !out_n_cigar || !out_cigar) fail(GDX_ERR_INVALID_ARGUMENT, "null output");
+    if (m == 0) return GDX_OK;
+    if (!cand_query || !cand_begin || !cand_hits) fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+    if (nq == 0) {  // every candidate is out of range
+        for (uint64_t c = 0; c < m; c++) {
+            out_dist[c] = GDX_EDIT_INVALID;
+            out_begin[c] = out_end[c] = GDX_EDIT_NO_END;
+            out_n_cigar[c] = 0;
+        }
+        return GDX_OK;
+    }
+    std::vector<gdx_hit32_t> narrow(m);
+    for (uint64_t c = 0; c < m; c++) {
+        if (cand_query[c] >= nq)
+            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu belongs to query %u of %llu", (unsigned long long)c, cand_query[c],
+                 (unsigned long long)nq);
+        if (cand_hits[c].text_id >= n_texts_)
+            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu lies in text %llu of %llu", (unsigned long long)c,
+                 (unsigned long long)cand_hits[c].text_id, (unsigned long long)n_texts_);
+        if (cand_hits[c].position > 0xffffffffull)
+            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu: position %llu does not fit 32 bits", (unsigned long long)c,
+                 (unsigned long long)cand_hits[c].position);
+        narrow[c].text_id = static_cast<uint32_t>(cand_hits[c].text_id);
+        narrow[c].position = static_cast<uint32_t>(cand_hits[c].position);
+    }
+    make_current();
+    hipStream_t stream = hipStreamPerThread;
+    const uint64_t stride = 2ull * max_edits + 1;
+    uint64_t ws_bytes[2];
+    align_workspace_bytes(0, m, max_edits, ws_bytes);
+    DeviceQueries dq(qbuf, qoff, nq, stream);
+    DeviceBuffer<uint32_t> d_query(m), d_begin(m), d_out(4 * m), d_cigar(m * stride);  // d_out: dist, begin, end, n_cigar
+    DeviceBuffer<gdx_hit32_t> d_hits(m);
+    DeviceBuffer<uint8_t> d_ws(ws_bytes[1]);
+    GDX_HIP(hipMemcpyAsync(d_query.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_begin.get(), cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
+    launch_align(view_, dq.qbuf.get(), dq.qoff.get(), nq, false, 0, d_query.get(), d_begin.get(), d_hits.get(), m, max_edits,
+                 d_out.get(), d_out.get() + m, d_out.get() + 2 * m, d_out.get() + 3 * m, d_cigar.get(), d_ws.get(), ws_bytes[1], stream);
+    GDX_HIP(hipGetLastError());
+    GDX_HIP(hipMemcpyAsync(out_dist, d_out.get(), m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_begin, d_out.get() + m, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_end, d_out.get() + 2 * m, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_n_cigar, d_out.get() + 3 * m, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipStreamSynchronize(stream));
+    // only the words below n_cigar are the call's: the words behind them stay as the caller left them
+    std::vector<uint32_t> cigar(m * stride);
+    GDX_HIP(hipMemcpy(cigar.data(), d_cigar.get(), cigar.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint64_t c = 0; c < m; c++)
+        std::copy_n(cigar.data() + c * stride, out_n_cigar[c], out_cigar + c * stride);
+    return GDX_OK;
+}
+
 int FmIndex::rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const
 {
     if (m == 0) return GDX_OK;

@@ -152,6 +152,12 @@ public:
                            uint32_t *out_end) const;
     // what both forms of gdx_edit_distance_many refuse before they look at the batch (check_hamming's, and the limit)
     void check_edit_distance(bool packed, uint32_t max_edits) const;
+    // gdx_align_many: staged like edit_distance_many, with a workspace of the best size; all five outputs are required
+    int align_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, const uint32_t *cand_query, const uint32_t *cand_begin,
+                   const gdx_hit_t *cand_hits, uint64_t m, uint32_t max_edits, uint32_t *out_dist, uint32_t *out_begin,
+                   uint32_t *out_end, uint32_t *out_n_cigar, uint32_t *out_cigar) const;
+    // what both forms of gdx_align_many refuse before they look at the batch: check_edit_distance's
+    void check_align(bool packed, uint32_t max_edits) const { check_edit_distance(packed, max_edits); }
     int rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const;
     int symbol_at_many(const uint64_t *idx, uint64_t m, uint8_t *out) const;
 

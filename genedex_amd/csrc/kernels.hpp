@@ -189,6 +189,17 @@ void launch_edit_distance(const IndexView &ix, const uint8_t *d_qbuf, const uint
                           const gdx_hit32_t *d_cand_hits, uint64_t m, uint32_t max_edits, uint32_t *d_out_dist,
                           uint32_t *d_out_end, hipStream_t stream);
 
+// ---- align.hip ----------------------------------------------------------------------------
+// gdx_align_many_dev: launch_edit_distance's inputs, dist and end, and with them where the canonical best alignment begins and
+// its run-length CIGAR (stride 2 max_edits + 1 words per candidate, words from n_cigar on untouched).  All five outputs are
+// required.  d_workspace: 16-byte aligned, at least out[0] of align_workspace_bytes; the grid is as many blocks as it holds, at
+// most out[1]'s, and the outputs do not depend on that.  One launch.
+void align_workspace_bytes(uint32_t uniform_len, uint64_t m, uint32_t max_edits, uint64_t out[2]);
+void launch_align(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq, bool packed, uint32_t uniform_len,
+                  const uint32_t *d_cand_query, const uint32_t *d_cand_begin, const gdx_hit32_t *d_cand_hits, uint64_t m,
+                  uint32_t max_edits, uint32_t *d_out_dist, uint32_t *d_out_begin, uint32_t *d_out_end, uint32_t *d_out_n_cigar,
+                  uint32_t *d_out_cigar, void *d_workspace, uint64_t workspace_bytes, hipStream_t stream);
+
 // ---- locate.hip ---------------------------------------------------------------------------
 size_t hit_offsets_temp_bytes(uint64_t m);
 void launch_hit_offsets(const uint32_t *d_start, const uint32_t *d_end, uint64_t m, uint64_t *d_hit_offsets,

@@ -488,6 +488,48 @@ class DeviceEngine:
                                                        _ptr(out_dist), _ptr(out_end) if out_end is not None else None, _stream()))
         return out_dist, out_end
 
+    # ---- alignment traceback of verified seed hits (gdx_align_many_dev) ---------------------------------------
+    def align_workspace_bytes(self, q: DeviceQueries, m: int, max_edits: int):
+        """(least, best): the workspace sizes of align() for m candidates of q's layout -- the least that works and the one
+        beyond which more memory does not help.  Launches nothing."""
+        lay, _ = q.layout()
+        sizes = (C.c_uint64 * 2)()
+        _lib.check(self.lib.gdx_align_many_dev(self.h, None, None, 0, C.byref(lay) if lay is not None else None, None, None, None,
+                                               int(m), int(max_edits), None, None, None, None, None, None, 0, sizes, None))
+        return int(sizes[0]), int(sizes[1])
+
+    def align(self, q: DeviceQueries, cand_query: torch.Tensor, cand_begin: torch.Tensor, cand_hits: torch.Tensor, max_edits: int,
+              out: dict = None, workspace: torch.Tensor = None):
+        """One launch: per candidate of edit_distance() the distance and end it gives, where the canonical best alignment begins
+        and its run-length CIGAR.  -> {"dist", "begin", "end", "n_cigar": int32[m], "cigar": int32[m, 2 max_edits + 1]} (u32
+        values; tensors of `out` are used where given, the others made here).  cigar words are run_length << 4 | GDX_CIGAR_*;
+        the words of a row from n_cigar on are not written.  begin and end are -1 (GDX_EDIT_NO_END) and n_cigar 0 wherever dist
+        is not a distance <= max_edits.  workspace: a contiguous 16-byte aligned tensor of at least align_workspace_bytes()[0]
+        bytes, scratch for the call; None takes the best size from torch's allocator.  The result does not depend on its size."""
+        m = cand_query.numel()
+        if cand_begin.numel() != m or cand_hits.numel() != 2 * m:
+            raise ValueError("cand_query, cand_begin and cand_hits differ in length")
+        for t in (cand_query, cand_begin, cand_hits):
+            if t.element_size() != 4 or not t.is_contiguous():
+                raise ValueError("candidates are contiguous 32-bit tensors")
+        if workspace is None:
+            workspace = torch.empty(self.align_workspace_bytes(q, m, max_edits)[1], dtype=torch.uint8, device=self.dev)
+        if not workspace.is_contiguous():
+            raise ValueError("the workspace is a contiguous tensor")
+        out = dict(out) if out else {}
+        for name in ("dist", "begin", "end", "n_cigar"):
+            if out.get(name) is None:
+                out[name] = torch.empty(max(m, 1), dtype=torch.int32, device=self.dev)
+        if out.get("cigar") is None:
+            out["cigar"] = torch.empty((max(m, 1), 2 * int(max_edits) + 1), dtype=torch.int32, device=self.dev)
+        lay, qoff = q.layout()
+        _lib.check(self.lib.gdx_align_many_dev(self.h, _ptr(q.qbuf), qoff, q.nq, C.byref(lay) if lay is not None else None,
+                                               _ptr(cand_query), _ptr(cand_begin), _ptr(cand_hits), m, int(max_edits),
+                                               _ptr(out["dist"]), _ptr(out["begin"]), _ptr(out["end"]), _ptr(out["n_cigar"]),
+                                               _ptr(out["cigar"]), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                               None, _stream()))
+        return out
+
     def search_step_stats(self, q: DeviceQueries):
         """(LF steps, line fetches of all queries, fetch slots their wavefronts spent)"""
         steps = torch.zeros(3, dtype=torch.int64, device=self.dev)

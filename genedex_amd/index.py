@@ -37,6 +37,23 @@ class Smem(NamedTuple):
     cursor: "Cursor"
 
 
+class Alignment(NamedTuple):
+    """One candidate's alignment (FmIndex.align_many): query against text[begin : end] with `dist` edits; cigar is a SAM string
+    of = X I D runs.  begin, end and cigar are None where there is none (dist is then max_edits + 1 or a GDX_EDIT_* marker)."""
+    dist: int
+    begin: int
+    end: int
+    cigar: str
+
+
+_CIGAR_CHAR = {_lib.GDX_CIGAR_INS: "I", _lib.GDX_CIGAR_DEL: "D", _lib.GDX_CIGAR_EQ: "=", _lib.GDX_CIGAR_DIFF: "X"}
+
+
+def cigar_string(words) -> str:
+    """the cigar words of one candidate (run_length << 4 | op) as a SAM string such as 37=1X12=2I98="""
+    return "".join("%d%s" % (int(w) >> 4, _CIGAR_CHAR[int(w) & 15]) for w in words)
+
+
 def _p(a, t):
     return a.ctypes.data_as(t)
 
@@ -650,6 +667,40 @@ class FmIndex:
         qbuf, qoff = pack_queries(queries)
         h = np.asarray([tuple(x) for x in hits], dtype=np.uint64).reshape(-1, 2)
         return self.edit_distance_raw(qbuf, qoff, cand_query, cand_begin, h[:, 0], h[:, 1], max_edits)
+
+    # ---- alignment traceback of verified seed hits (gdx.h "alignment traceback") --------------------------
+    def align_raw(self, qbuf, qoff, cand_query, cand_begin, text_ids, positions, max_edits):
+        """gdx_align_many -> (dist, begin, end, n_cigar, cigar[m, 2 max_edits + 1]), uint32 arrays: per candidate of
+        edit_distance_raw the distance and end it gives, where the canonical best alignment begins and its runs
+        (run_length << 4 | GDX_CIGAR_*; the words of a row from n_cigar on are zero).  include/gdx.h has the definition."""
+        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
+        qoff = np.ascontiguousarray(qoff, dtype=np.uint64)
+        cq = np.ascontiguousarray(cand_query, dtype=np.uint32)
+        cb = np.ascontiguousarray(cand_begin, dtype=np.uint32)
+        m = cq.size
+        hits = np.zeros((max(m, 1), 2), dtype=np.uint64)
+        hits[:m, 0] = text_ids
+        hits[:m, 1] = positions
+        if cb.size != m:
+            raise ValueError("cand_query and cand_begin differ in length")
+        dist, begin, end, n_cigar = (np.zeros(max(m, 1), dtype=np.uint32) for _ in range(4))
+        # (a limit over GDX_EDIT_MAX_QUERY_LEN is refused by the call before it writes anything)
+        cigar = np.zeros((max(m, 1), 2 * min(int(max_edits), _lib.GDX_EDIT_MAX_QUERY_LEN) + 1), dtype=np.uint32)
+        _lib.check(self._lib.gdx_align_many(self._h, _p(qbuf, u8p), _p(qoff, u64p), qoff.size - 1, _p(cq, u32p), _p(cb, u32p),
+                                            hits.ctypes.data_as(C.POINTER(_lib.HitStruct)), m, int(max_edits), _p(dist, u32p),
+                                            _p(begin, u32p), _p(end, u32p), _p(n_cigar, u32p), _p(cigar, u32p)))
+        return dist[:m], begin[:m], end[:m], n_cigar[:m], cigar[:m]
+
+    def align_many(self, queries, cand_query, cand_begin, hits, max_edits):
+        """One Alignment(dist, begin, end, cigar) per candidate of edit_distance_many: dist as there; the canonical best
+        alignment of the WHOLE query is against text[begin : end] of the candidate's text, cigar its SAM string of = X I D runs
+        ("" for an empty query).  begin, end and cigar are None when dist > max_edits or the query has more than 256 symbols."""
+        qbuf, qoff = pack_queries(queries)
+        h = np.asarray([tuple(x) for x in hits], dtype=np.uint64).reshape(-1, 2)
+        dist, begin, end, n_cigar, cigar = self.align_raw(qbuf, qoff, cand_query, cand_begin, h[:, 0], h[:, 1], max_edits)
+        return [Alignment(int(d), None, None, None) if e == _lib.GDX_EDIT_NO_END
+                else Alignment(int(d), int(b), int(e), cigar_string(row[:n]))
+                for d, b, e, n, row in zip(dist, begin, end, n_cigar, cigar)]
 
     def cursor_empty(self) -> "Cursor":
         s = C.c_uint64(0)

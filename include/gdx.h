@@ -699,8 +699,8 @@ int gdx_hamming_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t 
  * not take packed queries.  A refused call writes nothing.
  * Device form: ONE launch, no synchronisation, no allocation, no copy from pageable memory.  Host form: plain queries only;
  * stages the whole batch (copy in, one launch, copy out) like gdx_hamming_many and narrows gdx_hit_t to 32 bits.
- * Out of scope: where the alignment starts, CIGAR / traceback, affine gaps, reads of more than 256 symbols; gdx_parts_t and
- * gdx_multi_t have no such call. */
+ * Where the alignment starts and its CIGAR: gdx_align_many below.  Out of scope: affine gaps, reads of more than 256 symbols;
+ * gdx_parts_t and gdx_multi_t have no such call. */
 #define GDX_EDIT_MAX_QUERY_LEN 256u
 #define GDX_EDIT_INVALID  0xFFFFFFFFu   /* dist: cand_query >= nq or text_id >= num_texts (device form) */
 #define GDX_EDIT_TOO_LONG 0xFFFFFFFEu   /* dist: the candidate's query has more than 256 symbols        */
@@ -712,6 +712,65 @@ int gdx_edit_distance_many_dev(const gdx_index_t *ix, const void *d_qbuf, const 
 int gdx_edit_distance_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq,
                            const uint32_t *cand_query, const uint32_t *cand_begin, const gdx_hit_t *cand_hits, uint64_t m,
                            uint32_t max_edits, uint32_t *out_dist, uint32_t *out_end /*or NULL*/);
+
+/* ---- alignment traceback of verified seed hits (the last stage of seed and verify) -------------------------------------
+ * A distance and an end do not make a SAM record: gdx_align_many returns, per candidate, distance, begin, end and the
+ * run-length CIGAR of ONE canonically chosen optimal alignment, from the text units the index already holds.
+ * Inputs are exactly those of gdx_edit_distance_many: all four query layouts, cand_query / cand_begin / cand_hits,
+ * max_edits = k <= 256, reads of at most GDX_EDIT_MAX_QUERY_LEN symbols; the window T[x0, x1), the MATCH rule and
+ * GDX_EDIT_INVALID / GDX_EDIT_TOO_LONG / GDX_EDIT_NO_END are unchanged, and so is the split between the device form (writes
+ * the markers, returns GDX_OK) and the host form (GDX_ERR_INVALID_ARGUMENT for a candidate out of range).
+ * The table, for 0 <= i <= L and x0 <= y <= x1:
+ *     D[0][y] = 0,   D[i][x0] = i,   D[i][y] = min(D[i-1][y-1] + c(i, y), D[i-1][y] + 1, D[i][y-1] + 1)
+ * with c(i, y) = 0 when q[i-1] MATCHES T[y-1], else 1.  dist = min over y of D[L][y] and end = the smallest such y: the
+ * definition of gdx_edit_distance_many.
+ * The canonical alignment, when dist <= k: walk back from (i, y) = (L, end) and take at each step the FIRST rule that applies:
+ *     1. y > x0 and q[i-1] MATCHES T[y-1]:     '=', to (i-1, y-1)     (then D[i-1][y-1] == D[i][y])
+ *     2. y > x0 and D[i-1][y-1] + 1 == D[i][y]: 'X', to (i-1, y-1)
+ *     3. D[i-1][y] + 1 == D[i][y]:              'I', to (i-1, y)       (the read symbol has no partner in the text)
+ *     4. otherwise:                             'D', to (i, y-1)       (then y > x0 and D[i][y-1] + 1 == D[i][y])
+ * until i == 0; begin = the y reached.  The ops, reversed, read from the read's first symbol to its last.  The ops other than
+ * '=' number dist, ed(q, T[begin, end)) == dist, neither the first nor the last op is 'D', and there are at most 2 dist + 1
+ * runs.
+ * Outputs per candidate c, all five required (a null one: GDX_ERR_INVALID_ARGUMENT):
+ *     out_dist[c]     min(dist, k + 1): bit for bit what gdx_edit_distance_many writes, markers included
+ *     out_end[c]      as in gdx_edit_distance_many
+ *     out_begin[c]    begin, a position in text text_id, begin <= end; GDX_EDIT_NO_END wherever out_end is
+ *     out_n_cigar[c]  the number of runs; 0 wherever out_end is GDX_EDIT_NO_END, and 0 for L == 0
+ *     out_cigar[c * stride .. c * stride + n_cigar), stride = 2 k + 1: the runs, first run of the read first, each word
+ *                     run_length << 4 | op with BAM's op codes below; adjacent runs differ in op; words from n_cigar on are
+ *                     NOT written.  The fixed stride is why no offsets pass and no second launch is needed.
+ * Workspace (device form): the walk needs the forward pass's history, so the call takes caller memory and never allocates.
+ * With d_workspace == NULL it launches nothing and looks at no other device pointer: it writes out_workspace_bytes[0], the
+ * least size that works (one block of 256 lanes), and [1], the size beyond which more memory does not help (every lane of the
+ * largest grid the call launches for this m, layout and max_edits), and returns GDX_OK.  Both are pure functions of m,
+ * max_edits and the layout (a uniform length bounds L, otherwise 256 does); a lane needs
+ * 16 bytes x ((L + 2 k) x ceil(L / 64) + ceil((2 k + 1) / 4)), e.g. 8 KB at L = 150, k = 8 and 51 KB at L = k = 256.  The
+ * resident lanes are capped at 1024 blocks (4 wavefronts per SIMD on 256 CUs) and at the blocks that 4 GiB hold, so [1]
+ * never exceeds 4 GiB and does not grow with m beyond 262144 candidates: the kernel is grid-stride and a lane reuses its
+ * slot for every candidate it takes.  With a workspace: workspace_bytes < [0] or a d_workspace not aligned to 16 bytes is
+ * GDX_ERR_INVALID_ARGUMENT and writes nothing; any size from [0] up is accepted, the grid is the blocks that fit, at most
+ * [1]'s, and THE OUTPUTS DO NOT DEPEND ON THE SIZE GIVEN.  out_workspace_bytes may be NULL and is written only by the size
+ * query.  The workspace's content is scratch: nothing is kept in it between calls.
+ * Device form: ONE launch, no synchronisation, no allocation, no copy from pageable memory.  Host form: plain queries only;
+ * staged like gdx_edit_distance_many (the same candidate checks and narrowing of gdx_hit_t), allocates [1] itself; with
+ * nq == 0 it writes the markers m times.  m == 0 is GDX_OK.  GDX_ERR_UNSUPPORTED and the other GDX_ERR_INVALID_ARGUMENT cases
+ * are those of gdx_edit_distance_many.  A refused call writes nothing.
+ * Out of scope: affine gaps, reads of more than 256 symbols; gdx_parts_t and gdx_multi_t have no such call. */
+#define GDX_CIGAR_INS  1u   /* 'I': a read symbol without a partner in the text */
+#define GDX_CIGAR_DEL  2u   /* 'D': a text symbol without a partner in the read */
+#define GDX_CIGAR_EQ   7u   /* '=': a pair that MATCHES                         */
+#define GDX_CIGAR_DIFF 8u   /* 'X': a pair that does not                        */
+int gdx_align_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
+                       const gdx_query_layout_t *layout, const void *d_cand_query /*u32[m]*/,
+                       const void *d_cand_begin /*u32[m]*/, const void *d_cand_hits /*gdx_hit32_t[m]*/, uint64_t m,
+                       uint32_t max_edits, void *d_out_dist /*u32[m]*/, void *d_out_begin /*u32[m]*/, void *d_out_end /*u32[m]*/,
+                       void *d_out_n_cigar /*u32[m]*/, void *d_out_cigar /*u32[m * (2 max_edits + 1)]*/, void *d_workspace,
+                       uint64_t workspace_bytes, uint64_t *out_workspace_bytes /*u64[2] or NULL*/, void *stream);
+int gdx_align_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq,
+                   const uint32_t *cand_query, const uint32_t *cand_begin, const gdx_hit_t *cand_hits, uint64_t m,
+                   uint32_t max_edits, uint32_t *out_dist, uint32_t *out_begin, uint32_t *out_end, uint32_t *out_n_cigar,
+                   uint32_t *out_cigar);
 
 /* ---- batched cursor extension by strings (Cursor::extend_query_front, cursor.rs:34-51, applied to every symbol of
  * a string from its last to its first; ROADMAP.md:33 "API to use batched search with cursors") --------------------
