@@ -142,6 +142,9 @@ pub const GDX_CIGAR_INS: u32 = 1;
 pub const GDX_CIGAR_DEL: u32 = 2;
 pub const GDX_CIGAR_EQ: u32 = 7;
 pub const GDX_CIGAR_DIFF: u32 = 8;
+pub const GDX_CAND_NONE: u32 = 0xFFFF_FFFF;
+pub const GDX_CAND_BAD_SEEDS: u8 = 1;
+pub const GDX_CAND_MAX_ANCHORS: u32 = 1024;
 
 /// gdx_query_layout_t
 #[repr(C)]
@@ -303,6 +306,21 @@ extern "C" {
         ix: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, cand_query: *const u32, cand_begin: *const u32,
         cand_hits: *const Hit, m: u64, max_edits: u32, out_dist: *mut u32, out_begin: *mut u32, out_end: *mut u32,
         out_n_cigar: *mut u32, out_cigar: *mut u32,
+    ) -> c_int;
+    /// Seed-hit candidates (include/gdx_experimental.h "seed-hit candidates"): the seed slots of nq queries, in the layout
+    /// gdx_smems_many[_dev] writes, as ranked, de-duplicated candidates in slots of stride max_candidates that go straight
+    /// into the verify calls; unused slots hold cand_query GDX_CAND_NONE and zeros
+    pub fn gdx_seed_candidates_many_dev(
+        ix: *const gdx_index_t, nq: u64, max_seeds: u32, d_n_seeds: *const c_void, d_begin: *const c_void, d_length: *const c_void,
+        d_start: *const c_void, d_end: *const c_void, max_occ: u32, band: u32, max_candidates: u32, d_n_candidates: *mut c_void,
+        d_n_groups: *mut c_void, d_n_skipped: *mut c_void, d_cand_query: *mut c_void, d_cand_begin: *mut c_void,
+        d_cand_hits: *mut c_void, d_cand_weight: *mut c_void, d_status: *mut c_void, stream: *mut c_void,
+    ) -> c_int;
+    pub fn gdx_seed_candidates_many(
+        ix: *const gdx_index_t, nq: u64, max_seeds: u32, n_seeds: *const u32, begin: *const u32, length: *const u32,
+        start: *const u64, end: *const u64, max_occ: u32, band: u32, max_candidates: u32, out_n_candidates: *mut u32,
+        out_n_groups: *mut u32, out_n_skipped: *mut u32, out_cand_query: *mut u32, out_cand_begin: *mut u32,
+        out_cand_hits: *mut Hit, out_cand_weight: *mut u32, out_status: *mut u8,
     ) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
@@ -753,6 +771,51 @@ impl GpuFmIndex {
                         let k = i * max_smems as usize + j;
                         let b = begin[k] as usize;
                         (b, b + length[k] as usize, GpuCursor { index: self, start: s[k], end: e[k] })
+                    })
+                    .collect()
+            })
+            .collect()
+    }
+
+    /// The link between `smems_many` and the verify calls: per query its verification candidates (seed begin, hit, weight),
+    /// best first, at most `max_candidates` each.  `seeds[i]` is what `smems_many` returned for query i.  Seeds on more than
+    /// `max_occ` rows are left out; hits of one text within `band` diagonals of a group's first are ONE candidate, whose
+    /// weight is the number of query symbols its seeds cover.  Element (b, hit, w) of query i goes into `hamming_many` /
+    /// `edit_distance_many` / `align_many` as cand_query = i, cand_begin = b, cand_hits = hit.  Panics when the most seeds of
+    /// a query times `max_occ` exceeds GDX_CAND_MAX_ANCHORS and on an index without SA[row] in one fetch.
+    pub fn seed_candidates_many(
+        &self, seeds: &[Vec<(usize, usize, GpuCursor<'_>)>], max_occ: u32, band: u32, max_candidates: u32,
+    ) -> Vec<Vec<(u32, Hit, u32)>> {
+        let nq = seeds.len();
+        let ms = seeds.iter().map(|s| s.len()).max().unwrap_or(0).max(1);
+        let n_seeds: Vec<u32> = seeds.iter().map(|s| s.len() as u32).collect();
+        let (mut begin, mut length) = (vec![0u32; nq * ms], vec![0u32; nq * ms]);
+        let (mut s, mut e) = (vec![0u64; nq * ms], vec![0u64; nq * ms]);
+        for (i, list) in seeds.iter().enumerate() {
+            for (j, (b, end, cursor)) in list.iter().enumerate() {
+                let k = i * ms + j;
+                begin[k] = *b as u32;
+                length[k] = (*end - *b) as u32;
+                s[k] = cursor.start;
+                e[k] = cursor.end;
+            }
+        }
+        let slots = nq * max_candidates as usize;
+        let (mut n_cand, mut n_groups, mut n_skipped) = (vec![0u32; nq], vec![0u32; nq], vec![0u32; nq]);
+        let (mut cq, mut cb, mut cw) = (vec![0u32; slots], vec![0u32; slots], vec![0u32; slots]);
+        let mut hits = vec![Hit { text_id: 0, position: 0 }; slots];
+        check(unsafe {
+            gdx_seed_candidates_many(self.raw, nq as u64, ms as u32, n_seeds.as_ptr(), begin.as_ptr(), length.as_ptr(), s.as_ptr(),
+                                     e.as_ptr(), max_occ, band, max_candidates, n_cand.as_mut_ptr(), n_groups.as_mut_ptr(),
+                                     n_skipped.as_mut_ptr(), cq.as_mut_ptr(), cb.as_mut_ptr(), hits.as_mut_ptr(), cw.as_mut_ptr(),
+                                     std::ptr::null_mut())
+        });
+        (0..nq)
+            .map(|i| {
+                (0..n_cand[i] as usize)
+                    .map(|c| {
+                        let k = i * max_candidates as usize + c;
+                        (cb[k], hits[k], cw[k])
                     })
                     .collect()
             })

@@ -7,7 +7,8 @@ include/gdx.h, built into libgdx.so), and the host-side mirror of the reference'
 from . import alphabet
 from .alphabet import Alphabet
 
-__all__ = ["alphabet", "Alphabet", "FmIndexConfig", "FmIndex", "PartitionedFmIndex", "Cursor", "Hit", "Smem", "Alignment", "GdxError",
+__all__ = ["alphabet", "Alphabet", "FmIndexConfig", "FmIndex", "PartitionedFmIndex", "Cursor", "Hit", "Smem", "Alignment", "SeedCandidate",
+           "GdxError",
            "reversed_texts"]
 
 
@@ -18,7 +19,7 @@ def reversed_texts(texts):
 
 def __getattr__(name):
     # the query API needs libgdx.so; importing the alphabet tables alone does not
-    if name in ("FmIndexConfig", "FmIndex", "PartitionedFmIndex", "Cursor", "Hit", "Smem", "Alignment", "pack_queries"):
+    if name in ("FmIndexConfig", "FmIndex", "PartitionedFmIndex", "Cursor", "Hit", "Smem", "Alignment", "SeedCandidate", "pack_queries"):
         from . import index
 
         return getattr(index, name)

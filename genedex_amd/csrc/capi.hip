@@ -1850,6 +1850,48 @@ int gdx_align_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *q
     });
 }
 
+// ---- seed-hit candidates (candidates.hip) -----------------------------------------------------------------------
+
+int gdx_seed_candidates_many_dev(const gdx_index_t *ix, uint64_t nq, uint32_t max_seeds, const void *d_n_seeds, const void *d_begin,
+                                 const void *d_length, const void *d_start, const void *d_end, uint32_t max_occ, uint32_t band,
+                                 uint32_t max_candidates, void *d_n_candidates, void *d_n_groups, void *d_n_skipped,
+                                 void *d_cand_query, void *d_cand_begin, void *d_cand_hits, void *d_cand_weight, void *d_status,
+                                 void *stream)
+{
+    return guarded([&] {
+        const gdx::FmIndex &f = deref(ix);
+        f.check_seed_candidates(max_seeds, max_occ, max_candidates);
+        if (nq == 0) return (int)GDX_OK;
+        if (nq >= 0xffffffffull) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "more than 2^32 - 2 queries (cand_query is 32 bits wide)");
+        if (!d_n_seeds || !d_begin || !d_length || !d_start || !d_end || !d_n_candidates || !d_n_groups || !d_n_skipped ||
+            !d_cand_query || !d_cand_begin || !d_cand_hits || !d_cand_weight)
+            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+        DeviceGuard guard(f.config().device_id);
+        gdx::launch_seed_candidates(f.view(), nq, max_seeds, static_cast<const uint32_t *>(d_n_seeds),
+                                    static_cast<const uint32_t *>(d_begin), static_cast<const uint32_t *>(d_length),
+                                    static_cast<const uint32_t *>(d_start), static_cast<const uint32_t *>(d_end), max_occ, band,
+                                    max_candidates, static_cast<uint32_t *>(d_n_candidates), static_cast<uint32_t *>(d_n_groups),
+                                    static_cast<uint32_t *>(d_n_skipped), static_cast<uint32_t *>(d_cand_query),
+                                    static_cast<uint32_t *>(d_cand_begin), static_cast<gdx_hit32_t *>(d_cand_hits),
+                                    static_cast<uint32_t *>(d_cand_weight), static_cast<uint8_t *>(d_status), as_stream(stream));
+        GDX_HIP(hipGetLastError());
+        return (int)GDX_OK;
+    });
+}
+
+int gdx_seed_candidates_many(const gdx_index_t *ix, uint64_t nq, uint32_t max_seeds, const uint32_t *n_seeds, const uint32_t *begin,
+                             const uint32_t *length, const uint64_t *start, const uint64_t *end, uint32_t max_occ, uint32_t band,
+                             uint32_t max_candidates, uint32_t *out_n_candidates, uint32_t *out_n_groups, uint32_t *out_n_skipped,
+                             uint32_t *out_cand_query, uint32_t *out_cand_begin, gdx_hit_t *out_cand_hits, uint32_t *out_cand_weight,
+                             uint8_t *out_status)
+{
+    return guarded([&] {
+        return deref(ix).seed_candidates_many(nq, max_seeds, n_seeds, begin, length, start, end, max_occ, band, max_candidates,
+                                              out_n_candidates, out_n_groups, out_n_skipped, out_cand_query, out_cand_begin,
+                                              out_cand_hits, out_cand_weight, out_status);
+    });
+}
+
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {

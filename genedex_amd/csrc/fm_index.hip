@@ -3,6 +3,7 @@
 // concatenate + densely encode -> count -> suffix array -> BWT + text borders -> SA sampling ->
 // occurrence table -> lookup tables; every stage is a HIP kernel, nothing is computed on the host
 // except O(#texts) bookkeeping.
+#include "../../include/gdx_experimental.h"
 #include "fm_index.hpp"
 
 #include <algorithm>
@@ -2465,6 +2466,72 @@ int FmIndex::align_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, 
     for (uint64_t c = 0; c < m; c++)
         std::copy_n(cigar.data() + c * stride, out_n_cigar[c], out_cigar + c * stride);
     return GDX_OK;
+}
+
+void FmIndex::check_seed_candidates(uint32_t max_seeds, uint32_t max_occ, uint32_t max_candidates) const
+{
+    if (max_seeds == 0) fail(GDX_ERR_INVALID_ARGUMENT, "max_seeds must be at least 1");
+    if (max_occ == 0) fail(GDX_ERR_INVALID_ARGUMENT, "max_occ must be at least 1");
+    if (max_candidates == 0 || max_candidates > 1024u) fail(GDX_ERR_INVALID_ARGUMENT, "max_candidates must be 1..1024");
+    if (static_cast<uint64_t>(max_seeds) * max_occ > GDX_CAND_MAX_ANCHORS)
+        fail(GDX_ERR_INVALID_ARGUMENT, "max_seeds * max_occ = %llu exceeds GDX_CAND_MAX_ANCHORS (%u)",
+             (unsigned long long)max_seeds * max_occ, GDX_CAND_MAX_ANCHORS);
+    if (!seed_candidates_supported(view_))
+        fail(GDX_ERR_UNSUPPORTED, "seed candidates need SA[row] in one fetch: an index with full_suffix_array or 32-byte jump entries");
+}
+
+int FmIndex::seed_candidates_many(uint64_t nq, uint32_t max_seeds, const uint32_t *n_seeds, const uint32_t *begin,
+                                  const uint32_t *length, const uint64_t *start, const uint64_t *end, uint32_t max_occ, uint32_t band,
+                                  uint32_t max_candidates, uint32_t *out_n_candidates, uint32_t *out_n_groups, uint32_t *out_n_skipped,
+                                  uint32_t *out_cand_query, uint32_t *out_cand_begin, gdx_hit_t *out_cand_hits,
+                                  uint32_t *out_cand_weight, uint8_t *out_status) const
+{
+    check_seed_candidates(max_seeds, max_occ, max_candidates);
+    if (nq == 0) return GDX_OK;
+    if (nq >= 0xffffffffull) fail(GDX_ERR_INVALID_ARGUMENT, "more than 2^32 - 2 queries (cand_query is 32 bits wide)");
+    if (!n_seeds || !begin || !length || !start || !end || !out_n_candidates || !out_n_groups || !out_n_skipped || !out_cand_query ||
+        !out_cand_begin || !out_cand_hits || !out_cand_weight)
+        fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+    const uint64_t slots = nq * max_seeds, outs = nq * max_candidates;
+    std::vector<uint32_t> narrow(2 * slots);  // start, end
+    for (uint64_t s = 0; s < slots; s++) {
+        if (start[s] > 0xffffffffull || end[s] > 0xffffffffull)
+            fail(GDX_ERR_INVALID_ARGUMENT, "seed slot %llu: interval [%llu, %llu) does not fit 32 bits", (unsigned long long)s,
+                 (unsigned long long)start[s], (unsigned long long)end[s]);
+        narrow[s] = static_cast<uint32_t>(start[s]);
+        narrow[slots + s] = static_cast<uint32_t>(end[s]);
+    }
+    make_current();
+    hipStream_t stream = hipStreamPerThread;
+    DeviceBuffer<uint32_t> d_n(nq), d_begin(slots), d_len(slots), d_iv(2 * slots);
+    DeviceBuffer<uint32_t> d_per(3 * nq), d_out(3 * outs);  // d_per: n_candidates, n_groups, n_skipped; d_out: query, begin, weight
+    DeviceBuffer<gdx_hit32_t> d_hits(outs);
+    DeviceBuffer<uint8_t> d_status(nq);
+    GDX_HIP(hipMemcpyAsync(d_n.get(), n_seeds, nq * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_begin.get(), begin, slots * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_len.get(), length, slots * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_iv.get(), narrow.data(), 2 * slots * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    launch_seed_candidates(view_, nq, max_seeds, d_n.get(), d_begin.get(), d_len.get(), d_iv.get(), d_iv.get() + slots, max_occ, band,
+                           max_candidates, d_per.get(), d_per.get() + nq, d_per.get() + 2 * nq, d_out.get(), d_out.get() + outs,
+                           d_hits.get(), d_out.get() + 2 * outs, d_status.get(), stream);
+    GDX_HIP(hipGetLastError());
+    std::vector<gdx_hit32_t> hits(outs);
+    std::vector<uint8_t> st(nq);
+    GDX_HIP(hipMemcpyAsync(out_n_candidates, d_per.get(), nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_n_groups, d_per.get() + nq, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_n_skipped, d_per.get() + 2 * nq, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_cand_query, d_out.get(), outs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_cand_begin, d_out.get() + outs, outs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(out_cand_weight, d_out.get() + 2 * outs, outs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(hits.data(), d_hits.get(), outs * sizeof(gdx_hit32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(st.data(), d_status.get(), nq, hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipStreamSynchronize(stream));
+    for (uint64_t c = 0; c < outs; c++) {
+        out_cand_hits[c].text_id = hits[c].text_id;
+        out_cand_hits[c].position = hits[c].position;
+    }
+    if (out_status) std::memcpy(out_status, st.data(), nq);
+    return any_status(st.data(), nq);
 }
 
 int FmIndex::rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const

@@ -158,6 +158,14 @@ public:
                    uint32_t *out_end, uint32_t *out_n_cigar, uint32_t *out_cigar) const;
     // what both forms of gdx_align_many refuse before they look at the batch: check_edit_distance's
     void check_align(bool packed, uint32_t max_edits) const { check_edit_distance(packed, max_edits); }
+    // gdx_seed_candidates_many: the whole batch staged (copy in, one launch, copy out); start / end narrowed to 32 bits,
+    // cand_hits widened to gdx_hit_t
+    int seed_candidates_many(uint64_t nq, uint32_t max_seeds, const uint32_t *n_seeds, const uint32_t *begin, const uint32_t *length,
+                             const uint64_t *start, const uint64_t *end, uint32_t max_occ, uint32_t band, uint32_t max_candidates,
+                             uint32_t *out_n_candidates, uint32_t *out_n_groups, uint32_t *out_n_skipped, uint32_t *out_cand_query,
+                             uint32_t *out_cand_begin, gdx_hit_t *out_cand_hits, uint32_t *out_cand_weight, uint8_t *out_status) const;
+    // what both forms of gdx_seed_candidates_many refuse before they look at the batch
+    void check_seed_candidates(uint32_t max_seeds, uint32_t max_occ, uint32_t max_candidates) const;
     int rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const;
     int symbol_at_many(const uint64_t *idx, uint64_t m, uint8_t *out) const;
 

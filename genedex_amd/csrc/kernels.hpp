@@ -200,6 +200,18 @@ void launch_align(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *d_
                   uint32_t max_edits, uint32_t *d_out_dist, uint32_t *d_out_begin, uint32_t *d_out_end, uint32_t *d_out_n_cigar,
                   uint32_t *d_out_cigar, void *d_workspace, uint64_t workspace_bytes, hipStream_t stream);
 
+// ---- candidates.hip -----------------------------------------------------------------------
+// gdx_seed_candidates_many_dev: the seed slots of nq queries (the layout gdx_smems_many_dev writes) -> per query up to
+// max_candidates ranked candidates in slots of stride max_candidates, unused slots holding the none pattern.  The caller has
+// checked max_seeds, max_occ, max_candidates >= 1, max_candidates <= 1024, max_seeds * max_occ <= GDX_CAND_MAX_ANCHORS and
+// seed_candidates_supported(ix): SA[row] is one fetch.  d_status may be null.  One launch.
+bool seed_candidates_supported(const IndexView &ix);
+void launch_seed_candidates(const IndexView &ix, uint64_t nq, uint32_t max_seeds, const uint32_t *d_n_seeds, const uint32_t *d_begin,
+                            const uint32_t *d_length, const uint32_t *d_start, const uint32_t *d_end, uint32_t max_occ, uint32_t band,
+                            uint32_t max_candidates, uint32_t *d_n_candidates, uint32_t *d_n_groups, uint32_t *d_n_skipped,
+                            uint32_t *d_cand_query, uint32_t *d_cand_begin, gdx_hit32_t *d_cand_hits, uint32_t *d_cand_weight,
+                            uint8_t *d_status, hipStream_t stream);
+
 // ---- locate.hip ---------------------------------------------------------------------------
 size_t hit_offsets_temp_bytes(uint64_t m);
 void launch_hit_offsets(const uint32_t *d_start, const uint32_t *d_end, uint64_t m, uint64_t *d_hit_offsets,

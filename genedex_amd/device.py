@@ -442,6 +442,32 @@ class DeviceEngine:
             _ptr(out["remaining"]), _ptr(out["begin"]), _ptr(out["length"]), _ptr(out["start"]), _ptr(out["end"]),
             _ptr(out["status"]) if out.get("status") is not None else None, _stream()))
 
+    # ---- seed-hit candidates (gdx_seed_candidates_many_dev) --------------------------------------------------
+    def alloc_seed_candidates(self, nq: int, max_candidates: int):
+        d = self.dev
+        slots = max(nq * max_candidates, 1)
+        out = {name: torch.empty(max(nq, 1), dtype=torch.int32, device=d) for name in ("n_candidates", "n_groups", "n_skipped")}
+        out.update({name: torch.empty(slots, dtype=torch.int32, device=d) for name in ("cand_query", "cand_begin", "cand_weight")})
+        out["cand_hits"] = torch.empty((slots, 2), dtype=torch.int32, device=d)
+        out["status"] = torch.empty(max(nq, 1), dtype=torch.uint8, device=d)
+        return out
+
+    def seed_candidates(self, seeds: dict, nq: int, max_seeds: int, max_occ: int, band: int, max_candidates: int, out: dict = None):
+        """One launch: the seed slots of nq queries -> ranked, de-duplicated candidates in `out` (alloc_seed_candidates; made
+        here when None) -> out.  seeds: the `out` dict of smems() as it is ("n_smems", "begin", "length", "start", "end";
+        max_seeds = its max_smems), or one with "n_seeds" / "n_segments" in its place.  out["cand_query"], ["cand_begin"] and
+        ["cand_hits"] go straight into hamming() / edit_distance() / align() with all nq * max_candidates slots: an unused slot
+        has cand_query -1 (GDX_CAND_NONE) and gets the verify call's INVALID marker."""
+        n_seeds = next(seeds[name] for name in ("n_seeds", "n_smems", "n_segments") if seeds.get(name) is not None)
+        if out is None:
+            out = self.alloc_seed_candidates(nq, int(max_candidates))
+        _lib.check(self.lib.gdx_seed_candidates_many_dev(
+            self.h, int(nq), int(max_seeds), _ptr(n_seeds), _ptr(seeds["begin"]), _ptr(seeds["length"]), _ptr(seeds["start"]),
+            _ptr(seeds["end"]), int(max_occ), int(band), int(max_candidates), _ptr(out["n_candidates"]), _ptr(out["n_groups"]),
+            _ptr(out["n_skipped"]), _ptr(out["cand_query"]), _ptr(out["cand_begin"]), _ptr(out["cand_hits"]),
+            _ptr(out["cand_weight"]), _ptr(out["status"]) if out.get("status") is not None else None, _stream()))
+        return out
+
     # ---- Hamming verification of located seeds (gdx_hamming_many_dev) ---------------------------------------
     def hamming(self, q: DeviceQueries, cand_query: torch.Tensor, cand_begin: torch.Tensor, cand_hits: torch.Tensor,
                 max_mismatches: int, out: torch.Tensor = None) -> torch.Tensor:

@@ -46,6 +46,15 @@ class Alignment(NamedTuple):
     cigar: str
 
 
+class SeedCandidate(NamedTuple):
+    """One verification candidate of a query (FmIndex.seed_candidates_many): the seed query[begin:] lies at `position` of text
+    `text_id`; weight = the query symbols covered by the seeds that agree with it."""
+    begin: int
+    text_id: int
+    position: int
+    weight: int
+
+
 _CIGAR_CHAR = {_lib.GDX_CIGAR_INS: "I", _lib.GDX_CIGAR_DEL: "D", _lib.GDX_CIGAR_EQ: "=", _lib.GDX_CIGAR_DIFF: "X"}
 
 
@@ -530,6 +539,51 @@ class FmIndex:
             ks = range(i * max_smems, i * max_smems + int(n_smems[i]))
             out.append([Smem(int(begin[k]), int(begin[k]) + int(length[k]), Cursor(self, int(start[k]), int(end[k]))) for k in ks])
         return out
+
+    # ---- seed-hit candidates (gdx_experimental.h "seed-hit candidates") -------------------------------------
+    def seed_candidates_raw(self, n_seeds, begin, length, start, end, max_seeds, max_occ, band, max_candidates, strict=True):
+        """gdx_seed_candidates_many -> (n_candidates, n_groups, n_skipped: u32[nq]; cand_query, cand_begin: u32[nq *
+        max_candidates]; text_ids, positions: u64[..]; cand_weight: u32[..]; status u8[nq]): the seed slots of nq = len(n_seeds)
+        queries (the arrays of smems_raw, max_seeds = its max_smems) as ranked, de-duplicated verification candidates; unused
+        slots hold cand_query GDX_CAND_NONE and zeros.  strict=False: a query with bad seed slots is reported in status only."""
+        n_seeds = np.ascontiguousarray(n_seeds, dtype=np.uint32)
+        nq, ms, mc = n_seeds.size, int(max_seeds), int(max_candidates)
+        begin, length = (np.ascontiguousarray(x, dtype=np.uint32) for x in (begin, length))
+        start, end = (np.ascontiguousarray(x, dtype=np.uint64) for x in (start, end))
+        for x in (begin, length, start, end):
+            if x.size != nq * ms:
+                raise ValueError("seed arrays hold nq * max_seeds slots")
+        outs = max(nq * min(max(mc, 0), 1024), 1)
+        n_cand, n_groups, n_skipped = (np.zeros(max(nq, 1), dtype=np.uint32) for _ in range(3))
+        cq, cb, cw = (np.zeros(outs, dtype=np.uint32) for _ in range(3))
+        hits = np.zeros((outs, 2), dtype=np.uint64)
+        status = np.zeros(max(nq, 1), dtype=np.uint8)
+        st = self._lib.gdx_seed_candidates_many(self._h, nq, ms, _p(n_seeds, u32p), _p(begin, u32p), _p(length, u32p),
+                                                _p(start, u64p), _p(end, u64p), int(max_occ), int(band), mc, _p(n_cand, u32p),
+                                                _p(n_groups, u32p), _p(n_skipped, u32p), _p(cq, u32p), _p(cb, u32p),
+                                                hits.ctypes.data_as(C.POINTER(_lib.HitStruct)), _p(cw, u32p), _p(status, u8p))
+        _lib.check(st, allow=() if strict else (_lib.GDX_ERR_QUERY_STATUS,))
+        k = nq * mc
+        return n_cand[:nq], n_groups[:nq], n_skipped[:nq], cq[:k], cb[:k], hits[:k, 0], hits[:k, 1], cw[:k], status[:nq]
+
+    def seed_candidates_many(self, smems, max_occ, band, max_candidates):
+        """Per query the list of its SeedCandidate(begin, text_id, position, weight), best first: `smems` is what smems_many
+        returns (per query its Smem list).  Seeds on more than max_occ rows are left out; hits of one text within `band`
+        diagonals of a group's first are one candidate, whose weight is the number of query symbols its seeds cover."""
+        nq = len(smems)
+        ms = max([len(s) for s in smems] + [1])
+        n_seeds = np.array([len(s) for s in smems], dtype=np.uint32)
+        begin, length = np.zeros(nq * ms, dtype=np.uint32), np.zeros(nq * ms, dtype=np.uint32)
+        start, end = np.zeros(nq * ms, dtype=np.uint64), np.zeros(nq * ms, dtype=np.uint64)
+        for i, seeds in enumerate(smems):
+            for j, s in enumerate(seeds):
+                k = i * ms + j
+                begin[k], length[k], start[k], end[k] = s.query_begin, s.query_end - s.query_begin, s.cursor.start, s.cursor.end
+        n_cand, _, _, _, cb, t, p, cw, _ = self.seed_candidates_raw(n_seeds, begin, length, start, end, ms, max_occ, band,
+                                                                    max_candidates)
+        mc = int(max_candidates)
+        return [[SeedCandidate(int(cb[k]), int(t[k]), int(p[k]), int(cw[k])) for k in range(i * mc, i * mc + int(n_cand[i]))]
+                for i in range(nq)]
 
     def rank_many(self, symbols, idx):
         """TextWithRankSupport::rank (text_with_rank_support/mod.rs:106-110), batched."""

@@ -756,7 +756,9 @@ int gdx_edit_distance_many(const gdx_index_t *ix, const uint8_t *qbuf, const uin
  * staged like gdx_edit_distance_many (the same candidate checks and narrowing of gdx_hit_t), allocates [1] itself; with
  * nq == 0 it writes the markers m times.  m == 0 is GDX_OK.  GDX_ERR_UNSUPPORTED and the other GDX_ERR_INVALID_ARGUMENT cases
  * are those of gdx_edit_distance_many.  A refused call writes nothing.
- * Out of scope: affine gaps, reads of more than 256 symbols; gdx_parts_t and gdx_multi_t have no such call. */
+ * Out of scope: affine gaps, reads of more than 256 symbols; gdx_parts_t and gdx_multi_t have no such call.
+ * Where the candidates come from: gdx_seed_candidates_many[_dev] (gdx_experimental.h "seed-hit candidates") turns the slots of
+ * gdx_smems_many_dev into (cand_query, cand_begin, cand_hits) on the device, in slots that go straight into these calls. */
 #define GDX_CIGAR_INS  1u   /* 'I': a read symbol without a partner in the text */
 #define GDX_CIGAR_DEL  2u   /* 'D': a text symbol without a partner in the read */
 #define GDX_CIGAR_EQ   7u   /* '=': a pair that MATCHES                         */

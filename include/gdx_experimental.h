@@ -3,7 +3,9 @@
  * replaced, hint arrays, compact-result plumbing of the multi-GPU gather) and building blocks the tests and bench.py still
  * drive one by one.  Exported and tested like the core (tests/test_abi.py, tests/test_gpu_*.py), but not what a binding of the
  * reference's API needs (INTEGRATION.md binds gdx.h only), and free to change.  Every call returns the results of the core call
- * it is a part of: lib.rs:155-246 of the reference. */
+ * it is a part of: lib.rs:155-246 of the reference.  The last section, "seed-hit candidates", is a call of the seed-and-verify
+ * chain that the reference has no counterpart of; it is declared here because the core header keeps to its budget of names
+ * (tests/test_abi.py). */
 #ifndef GDX_EXPERIMENTAL_H
 #define GDX_EXPERIMENTAL_H
 
@@ -181,6 +183,68 @@ int gdx_locate_many_search_totals_compact_layout_dev(const gdx_index_t *ix, cons
                                                      void *d_compact, void *d_scan_workspace, void *d_totals, void *stream);
 
 int gdx_multi_from_indexes(gdx_index_t **replicas, int n_replicas, gdx_multi_t **out);
+
+/* ---- seed-hit candidates (the link between gdx_smems_many and the verify calls of gdx.h) ---------------------------------
+ * gdx_smems_many[_dev] ends at suffix-array intervals in fixed-stride slots; gdx_hamming_many, gdx_edit_distance_many and
+ * gdx_align_many start at one (text_id, position) per candidate.  gdx_seed_candidates_many turns the seed slots of a batch into
+ * ranked, de-duplicated candidates on the device: three seeds of one read on one diagonal are ONE candidate.
+ * Inputs: nq queries, each with at most max_seeds seeds in the slot layout gdx_smems_many[_dev] writes: n_seeds[i], and seed j of
+ * query i in slot i * max_seeds + j of begin, length, start, end; [start, end) are rows of ix.  The out arrays of
+ * gdx_smems_many_dev are valid input unchanged, and so are arrays made from gdx_suffix_segments_many.  The query bytes are
+ * not needed.
+ * Knobs: max_occ >= 1: a seed on more rows than this is skipped, as mappers do with repeats.  band, any u32: diagonals this
+ * close together are one candidate.  max_candidates, 1..1024: the slots per query in the output.  max_seeds * max_occ must
+ * not exceed GDX_CAND_MAX_ANCHORS.
+ * Per query i:
+ *  1. Check.  The status is GDX_CAND_BAD_SEEDS when n_seeds[i] > max_seeds; when for some seed j < n_seeds[i] length == 0,
+ *     start > end or end > n (this guards the suffix-array reads and comes before any of them); or when the seeds are not in
+ *     strictly descending order of both begin and begin + length, compared in 64 bits (the order in which both seed calls
+ *     report them).  Such a query gets 0 candidates, 0 groups, 0 skipped and the none pattern in all its slots.  Otherwise the
+ *     status is 0.
+ *  2. Anchors.  A seed with end - start > max_occ adds 1 to n_skipped[i] and gives no anchor.  Every other seed gives one anchor
+ *     per row r in [start, end): (t, pos) is the hit gdx_cursor_locate_many returns for row r (SA[r] through the text-id
+ *     lower bound), and d = (int64) pos - (int64) begin_j is the anchor's diagonal.  It may be negative.
+ *  3. Order.  The anchors are sorted by (t, d, begin) ascending: a total order, since two anchors with the same triple would
+ *     be the same text position.
+ *  4. Groups.  Scanning in that order, an anchor opens a new group when it is the first, when its t differs from the group's,
+ *     or when d - d_first > band, d_first being the diagonal of the group's FIRST anchor.  A group therefore never spans more
+ *     than band diagonals, however long a tandem repeat's run is.  n_groups[i] is the number of groups.
+ *  5. Per group.  weight = the number of query symbols covered by at least one of the group's anchors: a seed that occurs
+ *     twice in the group counts once, overlapping seeds count their union (2^32 - 1 if it were more).  representative = the
+ *     anchor of the greatest seed length, among equals the first in the order of step 3.
+ *  6. Output.  The groups by descending weight, among equals by ascending (t, d_first); only the first max_candidates of
+ *     them.  n_candidates[i] = min(n_groups[i], max_candidates).  Slot i * max_candidates + c holds cand_query = i,
+ *     cand_begin = the representative's seed begin, cand_hits = {t, pos} of the representative, and cand_weight.  Unused slots
+ *     hold the NONE PATTERN: cand_query = GDX_CAND_NONE, cand_begin = 0, cand_hits = {0, 0}, cand_weight = 0.
+ * The slots go straight into the verify calls: an unused slot carries a query number >= nq, for which the device forms of
+ * gdx_hamming_many, gdx_edit_distance_many and gdx_align_many already write their *_INVALID marker and return GDX_OK.  The
+ * caller passes d_cand_query, d_cand_begin, d_cand_hits as they are with m = nq * max_candidates: no compaction, no offsets
+ * pass, no synchronisation and no glue in between.  A compacted form is out of scope.
+ * Device form: ONE launch, no synchronisation, no allocation, no copy from pageable memory; returns GDX_OK.  d_status may be
+ * NULL.  Host form: the same arguments without the stream; start / end are u64 as gdx_smems_many writes them (a value of 2^32
+ * or more: GDX_ERR_INVALID_ARGUMENT), cand_hits is gdx_hit_t, out_status may be NULL.  It stages the whole batch (copy in, one
+ * launch, copy out) and returns GDX_ERR_QUERY_STATUS, after writing all outputs, when any query has a status != 0, like
+ * gdx_smems_many.
+ * GDX_ERR_INVALID_ARGUMENT: max_seeds, max_occ or max_candidates is 0; max_candidates > 1024; max_seeds * max_occ >
+ * GDX_CAND_MAX_ANCHORS (computed in 64 bits); nq >= 2^32 - 1 (a query number must differ from GDX_CAND_NONE); a null required
+ * pointer.  GDX_ERR_UNSUPPORTED: a handle of the 64-bit engine; an index on which SA[row] is not one fetch, i.e. one with
+ * neither full_suffix_array nor 32-byte jump entries (the default shape has the full suffix array; the kernel does not walk).
+ * nq == 0 is GDX_OK and writes nothing.  A refused call writes nothing.  gdx_parts_t and gdx_multi_t have no such call. */
+#define GDX_CAND_NONE        0xFFFFFFFFu   /* cand_query of an unused slot                                */
+#define GDX_CAND_BAD_SEEDS   1             /* status: the query's seed slots fail the check of step 1     */
+#define GDX_CAND_MAX_ANCHORS 1024u         /* the most anchors of one query: max_seeds * max_occ at most  */
+int gdx_seed_candidates_many_dev(const gdx_index_t *ix, uint64_t nq, uint32_t max_seeds, const void *d_n_seeds /*u32[nq]*/,
+                                 const void *d_begin /*u32[nq * max_seeds]*/, const void *d_length /*u32[..]*/,
+                                 const void *d_start /*u32[..]*/, const void *d_end /*u32[..]*/, uint32_t max_occ, uint32_t band,
+                                 uint32_t max_candidates, void *d_n_candidates /*u32[nq]*/, void *d_n_groups /*u32[nq]*/,
+                                 void *d_n_skipped /*u32[nq]*/, void *d_cand_query /*u32[nq * max_candidates]*/,
+                                 void *d_cand_begin /*u32[..]*/, void *d_cand_hits /*gdx_hit32_t[..]*/,
+                                 void *d_cand_weight /*u32[..]*/, void *d_status /*u8[nq] or NULL*/, void *stream);
+int gdx_seed_candidates_many(const gdx_index_t *ix, uint64_t nq, uint32_t max_seeds, const uint32_t *n_seeds,
+                             const uint32_t *begin, const uint32_t *length, const uint64_t *start, const uint64_t *end,
+                             uint32_t max_occ, uint32_t band, uint32_t max_candidates, uint32_t *out_n_candidates,
+                             uint32_t *out_n_groups, uint32_t *out_n_skipped, uint32_t *out_cand_query, uint32_t *out_cand_begin,
+                             gdx_hit_t *out_cand_hits, uint32_t *out_cand_weight, uint8_t *out_status /*or NULL*/);
 
 #ifdef __cplusplus
 }
