@@ -1,13 +1,15 @@
 // align.hip -- the last stage of seed and verify: distance, begin, end and run-length CIGAR of one canonically chosen
 // optimal alignment per candidate (gdx_align_many[_dev]).  Inputs, window, MATCH rule and markers are those of
-// edit_distance.hip; include/gdx.h "alignment traceback" has the table D and the four rules of the walk.
+// edit_distance.hip (the shared parts live in verify.hpp); include/gdx.h "alignment traceback" has the table D and the four
+// rules of the walk.
 //
 //   align_kernel<kXlate, kUniform, W>
 //                       ONE lane per candidate, grid-stride, the instantiation scheme of edit_kernel.  The forward pass is
-//                       edit_lane's column loop (Myers / Hyyro block step, the block step duplicated here so that
-//                       edit_distance.hip stays as it is).  Per block and column it additionally stores ONE 16-byte
-//                       element {diag, pick} into the lane's workspace slot: the walk's decision at every cell of the column,
-//                       which is a function of three planes the block step has anyway,
+//                       edit_lane's column loop (Myers / Hyyro block step), written out here a second time: shared through a
+//                       per-block hook it measured slower in one setting (profiles/r15/verify_refactor.md).  A change to the
+//                       window rule, the MATCH rule or a text-unit edge goes into both.  Per block and column it additionally
+//                       stores ONE 16-byte element {diag, pick} into the lane's workspace slot: the walk's decision at every
+//                       cell of the column, which is a function of three planes the block step has anyway,
 //                           Eq  (before the carry is folded in)         row matches                       -> rule 1
 //                           D0 = Xh | Mv                                D[i][y] == D[i-1][y-1]            -> rule 2 when clear
 //                           Pv' (the column's new vertical plus plane)  D[i][y] == D[i-1][y] + 1          -> rule 3
@@ -25,9 +27,7 @@
 //                       the slot and copied out reversed, so out_cigar gets exactly words 0 .. n_cigar.  It reads columns
 //                       begin + 1 .. end of the candidate it belongs to and nothing else: a lane's earlier candidate cannot
 //                       show through.  At y == x0 the rest of the read is one run of insertions (D[i][x0] = i).
-#include "common.hpp"
-#include "kernels.hpp"
-#include "read_codes.hpp"
+#include "verify.hpp"
 
 namespace gdx {
 
@@ -38,106 +38,33 @@ constexpr int kBlock = 256;
 constexpr uint64_t kMaxBlocks = 1024;
 constexpr uint64_t kMaxBytes = 4ull << 30;
 
-struct AlignArgs {
-    const u32x4 *text_units;
-    const uint32_t *sentinels;
-    const uint8_t *io_to_dense;
-    uint32_t perm_code_lo, perm_code_hi, perm_exp_lo, perm_exp_hi, perm_mask;
-    uint32_t n_texts;
-    const uint8_t *qbuf;
-    const uint64_t *qoff;  // null for a uniform batch
-    uint64_t nq;
-    uint32_t uniform_len;
-    const uint32_t *cand_query, *cand_begin;
-    const gdx_hit32_t *cand_hits;
-    uint64_t m;
+struct AlignArgs : VerifyArgs {
     uint32_t max_edits;  // <= 256
     uint32_t *out_dist, *out_begin, *out_end, *out_n_cigar, *out_cigar;
     ulonglong2 *ws;       // lane-interleaved slots, gridDim.x * kBlock lanes
     uint32_t hist_elems;  // history elements of a slot; the run stack lies behind them
 };
 
-// (edit_distance.hip's read_chunk) symbols [at, at + n_c) of the batch, n_c in 1..32 -> qc: symbol i in bits 2 i + 1 : 2 i
-// (garbage from n_c on); inv: bit i set when symbol i is not one of 1..4
-template <int kXlate>
-__device__ __forceinline__ void read_chunk(const AlignArgs &a, const uint8_t *s_dense, uint64_t at, uint32_t n_c, uint64_t &qc,
-                                           uint32_t &inv)
+// the outputs of a candidate without an alignment: dist is a marker or max_edits + 1
+__device__ __forceinline__ void store_no_alignment(const AlignArgs &a, uint64_t c, uint32_t dist)
 {
-    inv = 0;
-    const uint32_t n_need = (static_cast<uint32_t>(at & 7u) + n_c + 7u) >> 3;
-    if (kXlate == 2) {
-        const uint16_t *up = reinterpret_cast<const uint16_t *>(a.qbuf) + (at >> 3);
-        const uint32_t sh = static_cast<uint32_t>(at & 7u) * 2u;
-        uint64_t lo64 = up[0];
-        uint32_t hi16 = 0;
-        if (n_need > 1u) lo64 |= static_cast<uint64_t>(up[1]) << 16;
-        if (n_need > 2u) lo64 |= static_cast<uint64_t>(up[2]) << 32;
-        if (n_need > 3u) lo64 |= static_cast<uint64_t>(up[3]) << 48;
-        if (n_need > 4u) hi16 = up[4];
-        qc = sh != 0u ? (lo64 >> sh) | (static_cast<uint64_t>(hi16) << (64u - sh)) : lo64;
-    } else {
-        const uint64_t *wp = reinterpret_cast<const uint64_t *>(a.qbuf) + (at >> 3);
-        const uint32_t sh = static_cast<uint32_t>(at & 7u) * 8u;
-        uint64_t w0 = wp[0], w1 = 0, w2 = 0, w3 = 0, w4 = 0;
-        if (n_need > 1u) w1 = wp[1];
-        if (n_need > 2u) w2 = wp[2];
-        if (n_need > 3u) w3 = wp[3];
-        if (n_need > 4u) w4 = wp[4];
-        if (sh != 0u) {
-            w0 = (w0 >> sh) | (w1 << (64u - sh));
-            w1 = (w1 >> sh) | (w2 << (64u - sh));
-            w2 = (w2 >> sh) | (w3 << (64u - sh));
-            w3 = (w3 >> sh) | (w4 << (64u - sh));
-        }
-        const uint32_t wd[8] = {static_cast<uint32_t>(w0), static_cast<uint32_t>(w0 >> 32), static_cast<uint32_t>(w1),
-                                static_cast<uint32_t>(w1 >> 32), static_cast<uint32_t>(w2), static_cast<uint32_t>(w2 >> 32),
-                                static_cast<uint32_t>(w3), static_cast<uint32_t>(w3 >> 32)};
-        qc = 0;
-#pragma unroll
-        for (uint32_t g = 0; g < 8; g++) {
-            uint32_t bad;
-            const uint32_t code = kXlate == 1 ? pack4_perm(a, wd[g], bad) : pack4_lds(s_dense, wd[g], bad);
-            qc |= static_cast<uint64_t>(code) << (8u * g);
-            inv |= bad << (4u * g);
-        }
-    }
+    a.out_dist[c] = dist;
+    a.out_begin[c] = GDX_EDIT_NO_END;
+    a.out_end[c] = GDX_EDIT_NO_END;
+    a.out_n_cigar[c] = 0;
 }
-
-__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // candidate c, start to finish; `lane` of `n_lanes` owns slot `lane` of the workspace
 template <int kXlate, bool kUniform, int W>
 __device__ __forceinline__ void align_lane(const AlignArgs &a, const uint8_t *s_dense, uint64_t c, uint64_t lane, uint64_t n_lanes)
 {
-    const uint32_t q = a.cand_query[c], b = a.cand_begin[c];
-    const gdx_hit32_t hit = a.cand_hits[c];
-    uint32_t dist;
-    uint64_t begin = 0;
-    uint32_t L = 0;
-    if (q >= a.nq || hit.text_id >= a.n_texts) {
-        dist = GDX_EDIT_INVALID;
-    } else {
-        if (kUniform) {
-            begin = static_cast<uint64_t>(q) * a.uniform_len;
-            L = a.uniform_len;
-        } else {
-            begin = a.qoff[q];
-            const uint64_t len = a.qoff[q + 1] - begin;
-            L = len > GDX_EDIT_MAX_QUERY_LEN ? GDX_EDIT_MAX_QUERY_LEN + 1u : static_cast<uint32_t>(len);
-        }
-        dist = L > GDX_EDIT_MAX_QUERY_LEN ? GDX_EDIT_TOO_LONG : 0u;
-    }
-    if (dist != 0u) {
-        a.out_dist[c] = dist;
-        a.out_begin[c] = GDX_EDIT_NO_END;
-        a.out_end[c] = GDX_EDIT_NO_END;
-        a.out_n_cigar[c] = 0;
-        return;
-    }
-    // the text's own symbols are [t0, t0 + t_len) of the concatenation: between the sentinel in front and its own
-    const int64_t t0 = hit.text_id == 0u ? 0 : static_cast<int64_t>(a.sentinels[hit.text_id - 1u]) + 1;
-    const int64_t t_len = static_cast<int64_t>(a.sentinels[hit.text_id]) - t0;
-    const int64_t s = static_cast<int64_t>(hit.position) - static_cast<int64_t>(b);
+    Candidate cand;
+    const uint32_t marker = resolve_candidate<kUniform, true>(a, c, cand);
+    if (marker != 0u) return store_no_alignment(a, c, marker);
+    resolve_text(a, cand);
+    const uint64_t begin = cand.begin;
+    const uint32_t L = cand.L;
+    const int64_t t0 = cand.t0, t_len = cand.t_len, s = cand.s;
     const int64_t k = a.max_edits;
     const int64_t x0 = clamp64(s - k, 0, t_len), x1 = clamp64(s + static_cast<int64_t>(L) + k, 0, t_len);
     const uint32_t nb = kUniform ? static_cast<uint32_t>(W) : (L + 63u) >> 6;  // blocks of this read (W when uniform: L > 64 (W - 1))
@@ -225,13 +152,7 @@ __device__ __forceinline__ void align_lane(const AlignArgs &a, const uint8_t *s_
             }
         }
     }
-    if (best > a.max_edits) {
-        a.out_dist[c] = a.max_edits + 1u;
-        a.out_begin[c] = GDX_EDIT_NO_END;
-        a.out_end[c] = GDX_EDIT_NO_END;
-        a.out_n_cigar[c] = 0;
-        return;
-    }
+    if (best > a.max_edits) return store_no_alignment(a, c, a.max_edits + 1u);
 
     // the walk: rules 1 to 4 from (L, end) to row 0
     const uint32_t stride = 2u * a.max_edits + 1u;
@@ -284,10 +205,7 @@ template <int kXlate, bool kUniform, int W>
 __global__ __launch_bounds__(kBlock) void align_kernel(const AlignArgs a)
 {
     __shared__ uint8_t s_dense[256];
-    if (kXlate == 0) {
-        for (int i = threadIdx.x; i < 256; i += kBlock) s_dense[i] = a.io_to_dense[i];
-        __syncthreads();
-    }
+    load_dense_table<kXlate, kBlock>(s_dense, a.io_to_dense);
     const uint64_t lane = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x, n_lanes = static_cast<uint64_t>(gridDim.x) * kBlock;
     for (uint64_t c = lane; c < a.m; c += n_lanes) align_lane<kXlate, kUniform, W>(a, s_dense, c, lane, n_lanes);
 }
@@ -296,17 +214,9 @@ template <int kXlate>
 void launch_xlate(const AlignArgs &a, unsigned blocks, hipStream_t stream)
 {
     const dim3 grid(blocks), block(kBlock);
-    if (a.uniform_len == 0u) {
-        hipLaunchKernelGGL((align_kernel<kXlate, false, 4>), grid, block, 0, stream, a);
-        return;
-    }
-    // (a uniform batch over the limit: every lane leaves with GDX_EDIT_TOO_LONG before it looks at a block)
-    switch (a.uniform_len > GDX_EDIT_MAX_QUERY_LEN ? 4u : (a.uniform_len + 63u) >> 6) {
-    case 1: hipLaunchKernelGGL((align_kernel<kXlate, true, 1>), grid, block, 0, stream, a); break;
-    case 2: hipLaunchKernelGGL((align_kernel<kXlate, true, 2>), grid, block, 0, stream, a); break;
-    case 3: hipLaunchKernelGGL((align_kernel<kXlate, true, 3>), grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL((align_kernel<kXlate, true, 4>), grid, block, 0, stream, a); break;
-    }
+    dispatch_blocks(a.uniform_len, [&](auto uniform, auto w) {
+        hipLaunchKernelGGL((align_kernel<kXlate, decltype(uniform)::value, decltype(w)::value>), grid, block, 0, stream, a);
+    });
 }
 
 // history elements of one lane's slot: the longest window times the blocks of the longest read
@@ -349,23 +259,7 @@ void launch_align(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *d_
     if (blocks > most) blocks = most;
     if (blocks == 0) fail(GDX_ERR_INVALID_ARGUMENT, "the workspace holds no block of lanes");
     AlignArgs a;
-    a.text_units = ix.text_units;
-    a.sentinels = ix.sentinels;
-    a.io_to_dense = ix.io_to_dense;
-    a.perm_code_lo = ix.perm_code_lo;
-    a.perm_code_hi = ix.perm_code_hi;
-    a.perm_exp_lo = ix.perm_exp_lo;
-    a.perm_exp_hi = ix.perm_exp_hi;
-    a.perm_mask = ix.perm_mask;
-    a.n_texts = ix.n_texts;
-    a.qbuf = d_qbuf;
-    a.qoff = uniform_len ? nullptr : d_qoff;
-    a.nq = nq;
-    a.uniform_len = uniform_len;
-    a.cand_query = d_cand_query;
-    a.cand_begin = d_cand_begin;
-    a.cand_hits = d_cand_hits;
-    a.m = m;
+    fill_verify_args(a, ix, d_qbuf, d_qoff, nq, uniform_len, d_cand_query, d_cand_begin, d_cand_hits, m);
     a.max_edits = max_edits;
     a.out_dist = d_out_dist;
     a.out_begin = d_out_begin;

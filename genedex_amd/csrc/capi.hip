@@ -1742,6 +1742,15 @@ int gdx_locate_many_alloc_strands(const gdx_index_t *ix, const uint8_t *qbuf, co
 
 // ---- Hamming verification of located seeds (hamming.hip) --------------------------------------------------------
 
+// what the three verify _dev entries refuse once m != 0: a null candidate array, a null d_out (the output the entry has not
+// looked at itself) and a null d_qbuf of a batch with queries
+static void check_verify_pointers(const void *d_qbuf, uint64_t nq, const void *d_cand_query, const void *d_cand_begin,
+                                  const void *d_cand_hits, const void *d_out)
+{
+    if (!d_cand_query || !d_cand_begin || !d_cand_hits || !d_out) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+    if (nq != 0 && !d_qbuf) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf is null");
+}
+
 int gdx_hamming_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq, const gdx_query_layout_t *layout,
                          const void *d_cand_query, const void *d_cand_begin, const void *d_cand_hits, uint64_t m,
                          uint32_t max_mismatches, void *d_out, void *stream)
@@ -1752,8 +1761,7 @@ int gdx_hamming_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *
         apply_layout(c, d_qbuf, d_qoff, nq, layout);
         f.check_hamming(c.packed, max_mismatches);
         if (m == 0) return (int)GDX_OK;
-        if (!d_cand_query || !d_cand_begin || !d_cand_hits || !d_out) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-        if (nq != 0 && !d_qbuf) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf is null");
+        check_verify_pointers(d_qbuf, nq, d_cand_query, d_cand_begin, d_cand_hits, d_out);
         DeviceGuard guard(f.config().device_id);
         gdx::launch_hamming(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, static_cast<const uint32_t *>(d_cand_query),
                             static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits), m,
@@ -1781,8 +1789,7 @@ int gdx_edit_distance_many_dev(const gdx_index_t *ix, const void *d_qbuf, const 
         apply_layout(c, d_qbuf, d_qoff, nq, layout);
         f.check_edit_distance(c.packed, max_edits);
         if (m == 0) return (int)GDX_OK;
-        if (!d_cand_query || !d_cand_begin || !d_cand_hits || !d_out_dist) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-        if (nq != 0 && !d_qbuf) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf is null");
+        check_verify_pointers(d_qbuf, nq, d_cand_query, d_cand_begin, d_cand_hits, d_out_dist);
         DeviceGuard guard(f.config().device_id);
         gdx::launch_edit_distance(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, static_cast<const uint32_t *>(d_cand_query),
                                   static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits), m,
@@ -1827,8 +1834,7 @@ int gdx_align_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_
         if ((reinterpret_cast<uintptr_t>(d_workspace) & 15u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_workspace must be 16-byte aligned");
         if (!d_out_dist || !d_out_begin || !d_out_end || !d_out_n_cigar || !d_out_cigar) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null output");
         if (m == 0) return (int)GDX_OK;
-        if (!d_cand_query || !d_cand_begin || !d_cand_hits) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-        if (nq != 0 && !d_qbuf) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf is null");
+        check_verify_pointers(d_qbuf, nq, d_cand_query, d_cand_begin, d_cand_hits, d_out_dist);  // (the outputs: checked above)
         DeviceGuard guard(f.config().device_id);
         gdx::launch_align(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, static_cast<const uint32_t *>(d_cand_query),
                           static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits), m, max_edits,

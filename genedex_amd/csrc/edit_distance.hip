@@ -18,9 +18,13 @@
 //                       with the least score is the end.  Every loop is bounded by the clipped window: at most
 //                       L + 2 k <= 768 columns of at most 4 blocks.  A uniform batch runs the instance with
 //                       W = ceil(uniform_len / 64) blocks, an offsets batch W = 4 with the lane's own block count.
-#include "common.hpp"
-#include "kernels.hpp"
-#include "read_codes.hpp"
+//                       The argument block, the read loader read_chunk, clamp64, the LDS table load and the instance
+//                       dispatch are verify.hpp's, shared with hamming.hip and align.hip.  The lane itself is kept as it
+//                       was, candidate resolution included: routed through the shared resolution or a shared forward pass
+//                       it compiled to other code and measured slower at 50 symbols (profiles/r15/verify_refactor.md).
+//                       align_lane carries the same forward pass with its history stores: a change to the window rule, the
+//                       MATCH rule or a text-unit edge goes into both.
+#include "verify.hpp"
 
 namespace gdx {
 
@@ -28,71 +32,10 @@ namespace {
 
 constexpr int kBlock = 256;
 
-struct EditArgs {
-    const u32x4 *text_units;
-    const uint32_t *sentinels;
-    const uint8_t *io_to_dense;
-    uint32_t perm_code_lo, perm_code_hi, perm_exp_lo, perm_exp_hi, perm_mask;
-    uint32_t n_texts;
-    const uint8_t *qbuf;
-    const uint64_t *qoff;  // null for a uniform batch
-    uint64_t nq;
-    uint32_t uniform_len;
-    const uint32_t *cand_query, *cand_begin;
-    const gdx_hit32_t *cand_hits;
-    uint64_t m;
+struct EditArgs : VerifyArgs {
     uint32_t max_edits;  // <= 256
     uint32_t *out_dist, *out_end;  // out_end may be null
 };
-
-// symbols [at, at + n_c) of the batch, n_c in 1..32 -> qc: symbol i in bits 2 i + 1 : 2 i (garbage from n_c on); inv: bit i
-// set when symbol i is not one of 1..4.  The loads are those of hamming_kernel: only units / 8-byte words that hold one of
-// the chunk's symbols.
-template <int kXlate>
-__device__ __forceinline__ void read_chunk(const EditArgs &a, const uint8_t *s_dense, uint64_t at, uint32_t n_c, uint64_t &qc,
-                                           uint32_t &inv)
-{
-    inv = 0;
-    const uint32_t n_need = (static_cast<uint32_t>(at & 7u) + n_c + 7u) >> 3;
-    if (kXlate == 2) {
-        const uint16_t *up = reinterpret_cast<const uint16_t *>(a.qbuf) + (at >> 3);
-        const uint32_t sh = static_cast<uint32_t>(at & 7u) * 2u;
-        uint64_t lo64 = up[0];
-        uint32_t hi16 = 0;
-        if (n_need > 1u) lo64 |= static_cast<uint64_t>(up[1]) << 16;
-        if (n_need > 2u) lo64 |= static_cast<uint64_t>(up[2]) << 32;
-        if (n_need > 3u) lo64 |= static_cast<uint64_t>(up[3]) << 48;
-        if (n_need > 4u) hi16 = up[4];
-        qc = sh != 0u ? (lo64 >> sh) | (static_cast<uint64_t>(hi16) << (64u - sh)) : lo64;
-    } else {
-        const uint64_t *wp = reinterpret_cast<const uint64_t *>(a.qbuf) + (at >> 3);
-        const uint32_t sh = static_cast<uint32_t>(at & 7u) * 8u;
-        uint64_t w0 = wp[0], w1 = 0, w2 = 0, w3 = 0, w4 = 0;
-        if (n_need > 1u) w1 = wp[1];
-        if (n_need > 2u) w2 = wp[2];
-        if (n_need > 3u) w3 = wp[3];
-        if (n_need > 4u) w4 = wp[4];
-        if (sh != 0u) {
-            w0 = (w0 >> sh) | (w1 << (64u - sh));
-            w1 = (w1 >> sh) | (w2 << (64u - sh));
-            w2 = (w2 >> sh) | (w3 << (64u - sh));
-            w3 = (w3 >> sh) | (w4 << (64u - sh));
-        }
-        const uint32_t wd[8] = {static_cast<uint32_t>(w0), static_cast<uint32_t>(w0 >> 32), static_cast<uint32_t>(w1),
-                                static_cast<uint32_t>(w1 >> 32), static_cast<uint32_t>(w2), static_cast<uint32_t>(w2 >> 32),
-                                static_cast<uint32_t>(w3), static_cast<uint32_t>(w3 >> 32)};
-        qc = 0;
-#pragma unroll
-        for (uint32_t g = 0; g < 8; g++) {
-            uint32_t bad;
-            const uint32_t code = kXlate == 1 ? pack4_perm(a, wd[g], bad) : pack4_lds(s_dense, wd[g], bad);
-            qc |= static_cast<uint64_t>(code) << (8u * g);
-            inv |= bad << (4u * g);
-        }
-    }
-}
-
-__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // candidate c, start to finish
 template <int kXlate, bool kUniform, int W>
@@ -214,10 +157,7 @@ template <int kXlate, bool kUniform, int W>
 __global__ __launch_bounds__(kBlock) void edit_kernel(const EditArgs a)
 {
     __shared__ uint8_t s_dense[256];
-    if (kXlate == 0) {
-        for (int i = threadIdx.x; i < 256; i += kBlock) s_dense[i] = a.io_to_dense[i];
-        __syncthreads();
-    }
+    load_dense_table<kXlate, kBlock>(s_dense, a.io_to_dense);
     for (uint64_t c = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; c < a.m; c += static_cast<uint64_t>(gridDim.x) * kBlock)
         edit_lane<kXlate, kUniform, W>(a, s_dense, c);
 }
@@ -226,17 +166,9 @@ template <int kXlate>
 void launch_xlate(const EditArgs &a, hipStream_t stream)
 {
     const dim3 grid(grid_for(a.m, kBlock, 256u * 32u)), block(kBlock);
-    if (a.uniform_len == 0u) {
-        hipLaunchKernelGGL((edit_kernel<kXlate, false, 4>), grid, block, 0, stream, a);
-        return;
-    }
-    // (a uniform batch over the limit: every lane leaves with GDX_EDIT_TOO_LONG before it looks at a block)
-    switch (a.uniform_len > GDX_EDIT_MAX_QUERY_LEN ? 4u : (a.uniform_len + 63u) >> 6) {
-    case 1: hipLaunchKernelGGL((edit_kernel<kXlate, true, 1>), grid, block, 0, stream, a); break;
-    case 2: hipLaunchKernelGGL((edit_kernel<kXlate, true, 2>), grid, block, 0, stream, a); break;
-    case 3: hipLaunchKernelGGL((edit_kernel<kXlate, true, 3>), grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL((edit_kernel<kXlate, true, 4>), grid, block, 0, stream, a); break;
-    }
+    dispatch_blocks(a.uniform_len, [&](auto uniform, auto w) {
+        hipLaunchKernelGGL((edit_kernel<kXlate, decltype(uniform)::value, decltype(w)::value>), grid, block, 0, stream, a);
+    });
 }
 
 }  // namespace
@@ -248,23 +180,7 @@ void launch_edit_distance(const IndexView &ix, const uint8_t *d_qbuf, const uint
 {
     if (m == 0) return;
     EditArgs a;
-    a.text_units = ix.text_units;
-    a.sentinels = ix.sentinels;
-    a.io_to_dense = ix.io_to_dense;
-    a.perm_code_lo = ix.perm_code_lo;
-    a.perm_code_hi = ix.perm_code_hi;
-    a.perm_exp_lo = ix.perm_exp_lo;
-    a.perm_exp_hi = ix.perm_exp_hi;
-    a.perm_mask = ix.perm_mask;
-    a.n_texts = ix.n_texts;
-    a.qbuf = d_qbuf;
-    a.qoff = uniform_len ? nullptr : d_qoff;
-    a.nq = nq;
-    a.uniform_len = uniform_len;
-    a.cand_query = d_cand_query;
-    a.cand_begin = d_cand_begin;
-    a.cand_hits = d_cand_hits;
-    a.m = m;
+    fill_verify_args(a, ix, d_qbuf, d_qoff, nq, uniform_len, d_cand_query, d_cand_begin, d_cand_hits, m);
     a.max_edits = max_edits;
     a.out_dist = d_out_dist;
     a.out_end = d_out_end;

@@ -1987,6 +1987,46 @@ struct DeviceQueries {
     }
 };
 
+// the calls whose kernels keep a query's length in 32 bits
+void check_query_lengths(const uint64_t *qoff, uint64_t nq)
+{
+    for (uint64_t i = 0; i < nq; i++)
+        if (qoff[i + 1] - qoff[i] > 0xffffffffull)
+            fail(GDX_ERR_INVALID_ARGUMENT, "query %llu is longer than 2^32 - 1 symbols", (unsigned long long)i);
+}
+
+// the m candidates of a verify call (hamming_many, edit_distance_many, align_many) on the index's device: checked against the
+// batch and the index, the hits narrowed to 32 bits, uploaded on `stream` of the current device
+struct DeviceCandidates {
+    DeviceBuffer<uint32_t> query, begin;
+    DeviceBuffer<gdx_hit32_t> hits;
+    std::vector<gdx_hit32_t> narrow;  // the source of an asynchronous copy: lives until the call has synchronised
+    DeviceCandidates(uint64_t n_texts, uint64_t nq, const uint32_t *cand_query, const uint32_t *cand_begin, const gdx_hit_t *cand_hits,
+                     uint64_t m, hipStream_t stream)
+        : narrow(m)
+    {
+        for (uint64_t c = 0; c < m; c++) {
+            if (cand_query[c] >= nq)
+                fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu belongs to query %u of %llu", (unsigned long long)c, cand_query[c],
+                     (unsigned long long)nq);
+            if (cand_hits[c].text_id >= n_texts)
+                fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu lies in text %llu of %llu", (unsigned long long)c,
+                     (unsigned long long)cand_hits[c].text_id, (unsigned long long)n_texts);
+            if (cand_hits[c].position > 0xffffffffull)
+                fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu: position %llu does not fit 32 bits", (unsigned long long)c,
+                     (unsigned long long)cand_hits[c].position);
+            narrow[c].text_id = static_cast<uint32_t>(cand_hits[c].text_id);
+            narrow[c].position = static_cast<uint32_t>(cand_hits[c].position);
+        }
+        query.alloc(m);
+        begin.alloc(m);
+        hits.alloc(m);
+        GDX_HIP(hipMemcpyAsync(query.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        GDX_HIP(hipMemcpyAsync(begin.get(), cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        GDX_HIP(hipMemcpyAsync(hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
+    }
+};
+
 void check_queries(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq)
 {
     if (!qoff) fail(GDX_ERR_INVALID_ARGUMENT, "qoff is null");
@@ -2155,9 +2195,7 @@ int FmIndex::suffix_segments_many(const uint8_t *qbuf, const uint64_t *qoff, uin
     check_queries(qbuf, qoff, nq);
     if (nq == 0) return GDX_OK;
     if (!out_n_segments || !out_remaining || !out_length || !out_start || !out_end) fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-    for (uint64_t i = 0; i < nq; i++)
-        if (qoff[i + 1] - qoff[i] > 0xffffffffull)
-            fail(GDX_ERR_INVALID_ARGUMENT, "query %llu is longer than 2^32 - 1 symbols", (unsigned long long)i);
+    check_query_lengths(qoff, nq);
     make_current();
     hipStream_t stream = hipStreamPerThread;
     DeviceQueries dq(qbuf, qoff, nq, stream);
@@ -2204,9 +2242,7 @@ int FmIndex::smems_many(const FmIndex &reversed, const uint8_t *qbuf, const uint
     if (nq == 0) return GDX_OK;
     if (!out_n_smems || !out_remaining || !out_begin || !out_length || !out_start || !out_end)
         fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-    for (uint64_t i = 0; i < nq; i++)
-        if (qoff[i + 1] - qoff[i] > 0xffffffffull)
-            fail(GDX_ERR_INVALID_ARGUMENT, "query %llu is longer than 2^32 - 1 symbols", (unsigned long long)i);
+    check_query_lengths(qoff, nq);
     make_current();
     hipStream_t stream = hipStreamPerThread;
     DeviceQueries dq(qbuf, qoff, nq, stream);
@@ -2323,32 +2359,13 @@ int FmIndex::hamming_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq
         for (uint64_t c = 0; c < m; c++) out[c] = GDX_HAMMING_INVALID;
         return GDX_OK;
     }
-    for (uint64_t i = 0; i < nq; i++)
-        if (qoff[i + 1] - qoff[i] > 0xffffffffull)
-            fail(GDX_ERR_INVALID_ARGUMENT, "query %llu is longer than 2^32 - 1 symbols", (unsigned long long)i);
-    std::vector<gdx_hit32_t> narrow(m);
-    for (uint64_t c = 0; c < m; c++) {
-        if (cand_query[c] >= nq)
-            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu belongs to query %u of %llu", (unsigned long long)c, cand_query[c],
-                 (unsigned long long)nq);
-        if (cand_hits[c].text_id >= n_texts_)
-            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu lies in text %llu of %llu", (unsigned long long)c,
-                 (unsigned long long)cand_hits[c].text_id, (unsigned long long)n_texts_);
-        if (cand_hits[c].position > 0xffffffffull)
-            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu: position %llu does not fit 32 bits", (unsigned long long)c,
-                 (unsigned long long)cand_hits[c].position);
-        narrow[c].text_id = static_cast<uint32_t>(cand_hits[c].text_id);
-        narrow[c].position = static_cast<uint32_t>(cand_hits[c].position);
-    }
+    check_query_lengths(qoff, nq);
     make_current();
     hipStream_t stream = hipStreamPerThread;
+    DeviceCandidates dc(n_texts_, nq, cand_query, cand_begin, cand_hits, m, stream);
     DeviceQueries dq(qbuf, qoff, nq, stream);
-    DeviceBuffer<uint32_t> d_query(m), d_begin(m), d_out(m);
-    DeviceBuffer<gdx_hit32_t> d_hits(m);
-    GDX_HIP(hipMemcpyAsync(d_query.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_begin.get(), cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
-    launch_hamming(view_, dq.qbuf.get(), dq.qoff.get(), nq, false, 0, d_query.get(), d_begin.get(), d_hits.get(), m, max_mismatches,
+    DeviceBuffer<uint32_t> d_out(m);
+    launch_hamming(view_, dq.qbuf.get(), dq.qoff.get(), nq, false, 0, dc.query.get(), dc.begin.get(), dc.hits.get(), m, max_mismatches,
                    d_out.get(), stream);
     GDX_HIP(hipGetLastError());
     GDX_HIP(hipMemcpyAsync(out, d_out.get(), m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -2378,29 +2395,12 @@ int FmIndex::edit_distance_many(const uint8_t *qbuf, const uint64_t *qoff, uint6
         }
         return GDX_OK;
     }
-    std::vector<gdx_hit32_t> narrow(m);
-    for (uint64_t c = 0; c < m; c++) {
-        if (cand_query[c] >= nq)
-            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu belongs to query %u of %llu", (unsigned long long)c, cand_query[c],
-                 (unsigned long long)nq);
-        if (cand_hits[c].text_id >= n_texts_)
-            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu lies in text %llu of %llu", (unsigned long long)c,
-                 (unsigned long long)cand_hits[c].text_id, (unsigned long long)n_texts_);
-        if (cand_hits[c].position > 0xffffffffull)
-            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu: position %llu does not fit 32 bits", (unsigned long long)c,
-                 (unsigned long long)cand_hits[c].position);
-        narrow[c].text_id = static_cast<uint32_t>(cand_hits[c].text_id);
-        narrow[c].position = static_cast<uint32_t>(cand_hits[c].position);
-    }
     make_current();
     hipStream_t stream = hipStreamPerThread;
+    DeviceCandidates dc(n_texts_, nq, cand_query, cand_begin, cand_hits, m, stream);
     DeviceQueries dq(qbuf, qoff, nq, stream);
-    DeviceBuffer<uint32_t> d_query(m), d_begin(m), d_dist(m), d_end(out_end ? m : 0);
-    DeviceBuffer<gdx_hit32_t> d_hits(m);
-    GDX_HIP(hipMemcpyAsync(d_query.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_begin.get(), cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
-    launch_edit_distance(view_, dq.qbuf.get(), dq.qoff.get(), nq, false, 0, d_query.get(), d_begin.get(), d_hits.get(), m, max_edits,
+    DeviceBuffer<uint32_t> d_dist(m), d_end(out_end ? m : 0);
+    launch_edit_distance(view_, dq.qbuf.get(), dq.qoff.get(), nq, false, 0, dc.query.get(), dc.begin.get(), dc.hits.get(), m, max_edits,
                          d_dist.get(), out_end ? d_end.get() : nullptr, stream);
     GDX_HIP(hipGetLastError());
     GDX_HIP(hipMemcpyAsync(out_dist, d_dist.get(), m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -2426,33 +2426,16 @@ int FmIndex::align_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, 
         }
         return GDX_OK;
     }
-    std::vector<gdx_hit32_t> narrow(m);
-    for (uint64_t c = 0; c < m; c++) {
-        if (cand_query[c] >= nq)
-            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu belongs to query %u of %llu", (unsigned long long)c, cand_query[c],
-                 (unsigned long long)nq);
-        if (cand_hits[c].text_id >= n_texts_)
-            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu lies in text %llu of %llu", (unsigned long long)c,
-                 (unsigned long long)cand_hits[c].text_id, (unsigned long long)n_texts_);
-        if (cand_hits[c].position > 0xffffffffull)
-            fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu: position %llu does not fit 32 bits", (unsigned long long)c,
-                 (unsigned long long)cand_hits[c].position);
-        narrow[c].text_id = static_cast<uint32_t>(cand_hits[c].text_id);
-        narrow[c].position = static_cast<uint32_t>(cand_hits[c].position);
-    }
     make_current();
     hipStream_t stream = hipStreamPerThread;
+    DeviceCandidates dc(n_texts_, nq, cand_query, cand_begin, cand_hits, m, stream);
     const uint64_t stride = 2ull * max_edits + 1;
     uint64_t ws_bytes[2];
     align_workspace_bytes(0, m, max_edits, ws_bytes);
     DeviceQueries dq(qbuf, qoff, nq, stream);
-    DeviceBuffer<uint32_t> d_query(m), d_begin(m), d_out(4 * m), d_cigar(m * stride);  // d_out: dist, begin, end, n_cigar
-    DeviceBuffer<gdx_hit32_t> d_hits(m);
+    DeviceBuffer<uint32_t> d_out(4 * m), d_cigar(m * stride);  // d_out: dist, begin, end, n_cigar
     DeviceBuffer<uint8_t> d_ws(ws_bytes[1]);
-    GDX_HIP(hipMemcpyAsync(d_query.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_begin.get(), cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
-    launch_align(view_, dq.qbuf.get(), dq.qoff.get(), nq, false, 0, d_query.get(), d_begin.get(), d_hits.get(), m, max_edits,
+    launch_align(view_, dq.qbuf.get(), dq.qoff.get(), nq, false, 0, dc.query.get(), dc.begin.get(), dc.hits.get(), m, max_edits,
                  d_out.get(), d_out.get() + m, d_out.get() + 2 * m, d_out.get() + 3 * m, d_cigar.get(), d_ws.get(), ws_bytes[1], stream);
     GDX_HIP(hipGetLastError());
     GDX_HIP(hipMemcpyAsync(out_dist, d_out.get(), m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));

@@ -1,12 +1,12 @@
-// read_codes.hpp -- read bytes -> 2-bit codes for the kernels that compare reads with the text units (hamming.hip,
-// edit_distance.hip).  Device code only.
+// read_codes.hpp -- read bytes -> 2-bit codes and the bit helpers of the kernels that compare reads with the text units
+// (hamming.hip, edit_distance.hip, align.hip).  Device code only; verify.hpp builds the read loader read_chunk on it.
 #pragma once
 #include <cstdint>
 
 namespace gdx {
 
 // four read bytes -> their 2-bit codes in 8 bits (byte 0 in bits 1:0) and, in bits 0..3 of `bad`, which of them are not
-// one of the dense symbols 1..4.  Args carries IndexView's perm_code_lo / _hi, perm_exp_lo / _hi and perm_mask.
+// one of the dense symbols 1..4.  Args carries IndexView's perm_code_lo / _hi, perm_exp_lo / _hi and perm_mask (VerifyArgs).
 template <class Args>
 __device__ __forceinline__ uint32_t pack4_perm(const Args &a, uint32_t c, uint32_t &bad)
 {

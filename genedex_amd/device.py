@@ -24,6 +24,22 @@ def _ptr(t: torch.Tensor) -> C.c_void_p:
     return C.c_void_p(t.data_ptr())
 
 
+def _layout_arg(lay):
+    """the layout pointer of a _dev call: NULL for a batch in the plain form"""
+    return C.byref(lay) if lay is not None else None
+
+
+def _check_candidates(cand_query: torch.Tensor, cand_begin: torch.Tensor, cand_hits: torch.Tensor) -> int:
+    """the candidate tensors of the verify calls (hamming, edit_distance, align) -> m"""
+    m = cand_query.numel()
+    if cand_begin.numel() != m or cand_hits.numel() != 2 * m:
+        raise ValueError("cand_query, cand_begin and cand_hits differ in length")
+    for t in (cand_query, cand_begin, cand_hits):
+        if t.element_size() != 4 or not t.is_contiguous():
+            raise ValueError("candidates are contiguous 32-bit tensors")
+    return m
+
+
 def _stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -476,16 +492,11 @@ class DeviceEngine:
         forms (a batch made by with_strands goes straight in); cand_query / cand_begin: int32[m] holding u32 values; cand_hits:
         int32[m, 2] = (text_id, position), the hits tensor of locate().  A candidate whose query or text id is out of range
         gets -1 (GDX_HAMMING_INVALID)."""
-        m = cand_query.numel()
-        if cand_begin.numel() != m or cand_hits.numel() != 2 * m:
-            raise ValueError("cand_query, cand_begin and cand_hits differ in length")
-        for t in (cand_query, cand_begin, cand_hits):
-            if t.element_size() != 4 or not t.is_contiguous():
-                raise ValueError("candidates are contiguous 32-bit tensors")
+        m = _check_candidates(cand_query, cand_begin, cand_hits)
         if out is None:
             out = torch.empty(max(m, 1), dtype=torch.int32, device=self.dev)
         lay, qoff = q.layout()
-        _lib.check(self.lib.gdx_hamming_many_dev(self.h, _ptr(q.qbuf), qoff, q.nq, C.byref(lay) if lay is not None else None,
+        _lib.check(self.lib.gdx_hamming_many_dev(self.h, _ptr(q.qbuf), qoff, q.nq, _layout_arg(lay),
                                                  _ptr(cand_query), _ptr(cand_begin), _ptr(cand_hits), m, int(max_mismatches),
                                                  _ptr(out), _stream()))
         return out
@@ -498,18 +509,13 @@ class DeviceEngine:
         leftmost best alignment into out_end (u32 values in int32 tensors of m entries; made here when None; want_end=False
         with out_end None passes NULL).  -> (out_dist, out_end).  Out-of-range candidates get -1 (GDX_EDIT_INVALID), longer
         queries -2 (GDX_EDIT_TOO_LONG); out_end is -1 (GDX_EDIT_NO_END) wherever out_dist is not a distance <= max_edits."""
-        m = cand_query.numel()
-        if cand_begin.numel() != m or cand_hits.numel() != 2 * m:
-            raise ValueError("cand_query, cand_begin and cand_hits differ in length")
-        for t in (cand_query, cand_begin, cand_hits):
-            if t.element_size() != 4 or not t.is_contiguous():
-                raise ValueError("candidates are contiguous 32-bit tensors")
+        m = _check_candidates(cand_query, cand_begin, cand_hits)
         if out_dist is None:
             out_dist = torch.empty(max(m, 1), dtype=torch.int32, device=self.dev)
         if out_end is None and want_end:
             out_end = torch.empty(max(m, 1), dtype=torch.int32, device=self.dev)
         lay, qoff = q.layout()
-        _lib.check(self.lib.gdx_edit_distance_many_dev(self.h, _ptr(q.qbuf), qoff, q.nq, C.byref(lay) if lay is not None else None,
+        _lib.check(self.lib.gdx_edit_distance_many_dev(self.h, _ptr(q.qbuf), qoff, q.nq, _layout_arg(lay),
                                                        _ptr(cand_query), _ptr(cand_begin), _ptr(cand_hits), m, int(max_edits),
                                                        _ptr(out_dist), _ptr(out_end) if out_end is not None else None, _stream()))
         return out_dist, out_end
@@ -520,7 +526,7 @@ class DeviceEngine:
         beyond which more memory does not help.  Launches nothing."""
         lay, _ = q.layout()
         sizes = (C.c_uint64 * 2)()
-        _lib.check(self.lib.gdx_align_many_dev(self.h, None, None, 0, C.byref(lay) if lay is not None else None, None, None, None,
+        _lib.check(self.lib.gdx_align_many_dev(self.h, None, None, 0, _layout_arg(lay), None, None, None,
                                                int(m), int(max_edits), None, None, None, None, None, None, 0, sizes, None))
         return int(sizes[0]), int(sizes[1])
 
@@ -532,12 +538,7 @@ class DeviceEngine:
         the words of a row from n_cigar on are not written.  begin and end are -1 (GDX_EDIT_NO_END) and n_cigar 0 wherever dist
         is not a distance <= max_edits.  workspace: a contiguous 16-byte aligned tensor of at least align_workspace_bytes()[0]
         bytes, scratch for the call; None takes the best size from torch's allocator.  The result does not depend on its size."""
-        m = cand_query.numel()
-        if cand_begin.numel() != m or cand_hits.numel() != 2 * m:
-            raise ValueError("cand_query, cand_begin and cand_hits differ in length")
-        for t in (cand_query, cand_begin, cand_hits):
-            if t.element_size() != 4 or not t.is_contiguous():
-                raise ValueError("candidates are contiguous 32-bit tensors")
+        m = _check_candidates(cand_query, cand_begin, cand_hits)
         if workspace is None:
             workspace = torch.empty(self.align_workspace_bytes(q, m, max_edits)[1], dtype=torch.uint8, device=self.dev)
         if not workspace.is_contiguous():
@@ -549,7 +550,7 @@ class DeviceEngine:
         if out.get("cigar") is None:
             out["cigar"] = torch.empty((max(m, 1), 2 * int(max_edits) + 1), dtype=torch.int32, device=self.dev)
         lay, qoff = q.layout()
-        _lib.check(self.lib.gdx_align_many_dev(self.h, _ptr(q.qbuf), qoff, q.nq, C.byref(lay) if lay is not None else None,
+        _lib.check(self.lib.gdx_align_many_dev(self.h, _ptr(q.qbuf), qoff, q.nq, _layout_arg(lay),
                                                _ptr(cand_query), _ptr(cand_begin), _ptr(cand_hits), m, int(max_edits),
                                                _ptr(out["dist"]), _ptr(out["begin"]), _ptr(out["end"]), _ptr(out["n_cigar"]),
                                                _ptr(out["cigar"]), _ptr(workspace), workspace.numel() * workspace.element_size(),

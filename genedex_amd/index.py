@@ -661,10 +661,10 @@ class FmIndex:
         return [(rows[2 * i], rows[2 * i + 1]) for i in range(qoff.size - 1)]
 
     # ---- Hamming verification of located seeds (gdx.h "Hamming verification") ---------------------------
-    def hamming_raw(self, qbuf, qoff, cand_query, cand_begin, text_ids, positions, max_mismatches):
-        """gdx_hamming_many -> u32[m]: per candidate (query, where its seed begins in the query, the (text_id, position) the
-        seed was located at) the mismatches of the whole query against its text on that diagonal, capped at
-        max_mismatches + 1 (include/gdx.h has the definition)."""
+    @staticmethod
+    def _verify_arrays(qbuf, qoff, cand_query, cand_begin, text_ids, positions):
+        """the batch and the candidates of a verify call as the C ABI takes them -> (qbuf, qoff, cand_query, cand_begin,
+        hits u64[max(m, 1), 2], m)"""
         qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
         qoff = np.ascontiguousarray(qoff, dtype=np.uint64)
         cq = np.ascontiguousarray(cand_query, dtype=np.uint32)
@@ -675,6 +675,13 @@ class FmIndex:
         hits[:m, 1] = positions
         if cb.size != m:
             raise ValueError("cand_query and cand_begin differ in length")
+        return qbuf, qoff, cq, cb, hits, m
+
+    def hamming_raw(self, qbuf, qoff, cand_query, cand_begin, text_ids, positions, max_mismatches):
+        """gdx_hamming_many -> u32[m]: per candidate (query, where its seed begins in the query, the (text_id, position) the
+        seed was located at) the mismatches of the whole query against its text on that diagonal, capped at
+        max_mismatches + 1 (include/gdx.h has the definition)."""
+        qbuf, qoff, cq, cb, hits, m = self._verify_arrays(qbuf, qoff, cand_query, cand_begin, text_ids, positions)
         out = np.zeros(max(m, 1), dtype=np.uint32)
         _lib.check(self._lib.gdx_hamming_many(self._h, _p(qbuf, u8p), _p(qoff, u64p), qoff.size - 1, _p(cq, u32p), _p(cb, u32p),
                                               hits.ctypes.data_as(C.POINTER(_lib.HitStruct)), m, int(max_mismatches), _p(out, u32p)))
@@ -695,16 +702,7 @@ class FmIndex:
         """gdx_edit_distance_many -> (dist u32[m], end u32[m] or None): per candidate of hamming_raw the infix edit distance of
         the whole query against its text within max_edits of the seed's diagonal, capped at max_edits + 1, and the exclusive end
         of the leftmost best alignment in that text (include/gdx.h has the definition)."""
-        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
-        qoff = np.ascontiguousarray(qoff, dtype=np.uint64)
-        cq = np.ascontiguousarray(cand_query, dtype=np.uint32)
-        cb = np.ascontiguousarray(cand_begin, dtype=np.uint32)
-        m = cq.size
-        hits = np.zeros((max(m, 1), 2), dtype=np.uint64)
-        hits[:m, 0] = text_ids
-        hits[:m, 1] = positions
-        if cb.size != m:
-            raise ValueError("cand_query and cand_begin differ in length")
+        qbuf, qoff, cq, cb, hits, m = self._verify_arrays(qbuf, qoff, cand_query, cand_begin, text_ids, positions)
         dist = np.zeros(max(m, 1), dtype=np.uint32)
         end = np.zeros(max(m, 1), dtype=np.uint32) if want_end else None
         _lib.check(self._lib.gdx_edit_distance_many(self._h, _p(qbuf, u8p), _p(qoff, u64p), qoff.size - 1, _p(cq, u32p), _p(cb, u32p),
@@ -727,16 +725,7 @@ class FmIndex:
         """gdx_align_many -> (dist, begin, end, n_cigar, cigar[m, 2 max_edits + 1]), uint32 arrays: per candidate of
         edit_distance_raw the distance and end it gives, where the canonical best alignment begins and its runs
         (run_length << 4 | GDX_CIGAR_*; the words of a row from n_cigar on are zero).  include/gdx.h has the definition."""
-        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
-        qoff = np.ascontiguousarray(qoff, dtype=np.uint64)
-        cq = np.ascontiguousarray(cand_query, dtype=np.uint32)
-        cb = np.ascontiguousarray(cand_begin, dtype=np.uint32)
-        m = cq.size
-        hits = np.zeros((max(m, 1), 2), dtype=np.uint64)
-        hits[:m, 0] = text_ids
-        hits[:m, 1] = positions
-        if cb.size != m:
-            raise ValueError("cand_query and cand_begin differ in length")
+        qbuf, qoff, cq, cb, hits, m = self._verify_arrays(qbuf, qoff, cand_query, cand_begin, text_ids, positions)
         dist, begin, end, n_cigar = (np.zeros(max(m, 1), dtype=np.uint32) for _ in range(4))
         # (a limit over GDX_EDIT_MAX_QUERY_LEN is refused by the call before it writes anything)
         cigar = np.zeros((max(m, 1), 2 * min(int(max_edits), _lib.GDX_EDIT_MAX_QUERY_LEN) + 1), dtype=np.uint32)

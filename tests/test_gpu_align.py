@@ -10,7 +10,7 @@ from genedex_amd import alphabet as alph
 from oracle.oracle import pack_queries
 from test_align_model import DEL, INS, align_model, replay_all, runs_of, sam
 from test_edit_distance_model import INVALID, NO_END, TOO_LONG
-from test_gpu_edit_distance import _LIMITS, _random_case, planted_read, status_of, variant  # noqa: F401  (variant: a fixture)
+from test_gpu_edit_distance import _LIMITS, _layouts_case, _random_case, planted_read, status_of, variant  # noqa: F401  (variant: a fixture)
 from test_gpu_hamming import expand_candidates
 from test_gpu_parity import gpu_index
 from test_smems_model import model_arrays, oracle_pair
@@ -232,6 +232,18 @@ def test_word_borders_and_unit_phases_in_both_layouts():
         local = [i - part.start for i in cq[part]]
         for k in _SWEEP_LIMITS:
             assert_equal(device_call(eng, dq, local, cb[part], hits[part], k), _slice_of(c["want"][k], part), ("packed + uniform", ln, k))
+    # the two forms the sweep leaves out, on the reads of test_gpu_edit_distance's layouts test: plain + uniform of 1, 2, 3 and
+    # 4 blocks (align_kernel<1, true, 1..4>) and packed + offsets (align_kernel<2, false, 4>)
+    for ulen in (50, 70, 150, 256):
+        a, texts, qs, (cq, cb, hits) = _layouts_case(ulen)
+        g = gpu_index(texts, a)
+        eng = DeviceEngine(g)
+        plain = DeviceQueries.from_host(*join(qs))
+        for k in (0, 3):
+            want = align_model(texts, a, qs, cq, cb, hits, k)
+            assert (want[2] != NO_END).sum() > 30 and (want[2] == NO_END).sum() > 30   # the input condition
+            assert_equal(device_call(eng, plain.as_uniform(ulen), cq, cb, hits, k), want, ("uniform", ulen, k))
+            assert_equal(device_call(eng, plain.as_packed(g), cq, cb, hits, k), want, ("packed", ulen, k))
 
 
 def test_word_borders_and_unit_phases_with_the_alphabet_table_in_lds():

@@ -252,10 +252,14 @@ def test_word_borders_and_window_phases():
 # ------------------------------------------------------------------------------------------------
 # 3. all four query layouts
 
-@pytest.mark.parametrize("ulen", (50, 150, 256))        # 1, 3 and 4 blocks; the last block's top bit is 49, 21 and 63
-def test_all_four_layouts_give_the_same_arrays(ulen):
-    from genedex_amd.device import DeviceEngine, DeviceQueries
+_LAYOUT_CASES = {}
 
+
+def _layouts_case(ulen):
+    """300 reads of ulen symbols with planted edits or over an end of their text, one candidate each in shuffled order
+    -> (alphabet, texts, reads, (cand_query, cand_begin, hits)); shared with test_gpu_align.py"""
+    if ulen in _LAYOUT_CASES:
+        return _LAYOUT_CASES[ulen]
     rng = np.random.default_rng(12060 + ulen)
     a = alph.ascii_dna()
     texts = [bytes(b"ACGT"[i] for i in rng.integers(0, 4, n)) for n in (2100, 900)]
@@ -276,9 +280,19 @@ def test_all_four_layouts_give_the_same_arrays(ulen):
         qs.append(q), cq.append(i), cb.append(b), hits.append((text_id, position))
     order = rng.permutation(300)                        # candidates need not come in query order
     cq, cb, hits = [cq[i] for i in order], [cb[i] for i in order], [hits[i] for i in order]
-    wants = {k: edit_model(texts, a, qs, cq, cb, hits, k) for k in (2, 9)}
-    for k, want in wants.items():                       # the input condition, on the models alone
-        ham = hamming_model(texts, a, qs, cq, cb, hits, k)
+    _LAYOUT_CASES[ulen] = (a, texts, qs, (cq, cb, hits))
+    return _LAYOUT_CASES[ulen]
+
+
+# 1, 2, 3 and 4 blocks (edit_kernel<1 and 2, true, 1..4>, <1 and 2, false, 4>); the last block's top bit is 49, 5, 21 and 63
+@pytest.mark.parametrize("ulen", (50, 70, 150, 256))
+def test_all_four_layouts_give_the_same_arrays(ulen):
+    from genedex_amd.device import DeviceEngine, DeviceQueries
+
+    a, texts, qs, (cq, cb, hits) = _layouts_case(ulen)
+    wants = {k: edit_model(texts, a, qs, cq, cb, hits, k) for k in (0, 2, 3, 9)}
+    for k in (2, 9):                                    # the input condition, on the models alone
+        want, ham = wants[k], hamming_model(texts, a, qs, cq, cb, hits, k)
         assert (want[0] <= 2).sum() > 60 and (want[0] > 2).sum() > 60 and (want[0] < ham).sum() > 60
     g = gpu_index(texts, a)
     eng = DeviceEngine(g)
@@ -299,10 +313,10 @@ def test_all_four_layouts_give_the_same_arrays(ulen):
         assert_equal((dist,), want[:1], ("host", k, "no end"))
 
 
-@pytest.mark.parametrize("ulen", (0, 70))   # 0: lengths 1 .. 256 behind offsets
+@pytest.mark.parametrize("ulen", (0, 50, 70, 150, 256))   # 0: lengths 1 .. 256 behind offsets; else 1, 2, 3 and 4 blocks
 def test_alphabet_whose_symbols_share_their_low_three_bits(ulen):
     """A, I, Q and Y agree in their low three bits, so the index has no v_perm tables and plain reads are translated through
-    the alphabet table in LDS (edit_kernel<0, ., .>), which no stock DNA alphabet reaches"""
+    the alphabet table in LDS (edit_kernel<0, false, 4> and <0, true, 1..4>), which no stock DNA alphabet reaches"""
     from genedex_amd.device import DeviceEngine, DeviceQueries
 
     rng = np.random.default_rng(12065 + ulen)
@@ -330,8 +344,8 @@ def test_alphabet_whose_symbols_share_their_low_three_bits(ulen):
         for _ in range(i % 2):
             q[int(rng.integers(0, ln))] = wrong[int(rng.integers(0, len(wrong)))]
         qs.append(bytes(q)), cq.append(i), cb.append(b), hits.append((text_id, position))
-    wants = {k: edit_model(texts, a, qs, cq, cb, hits, k) for k in (2, 7)}
-    for want in wants.values():                         # the input condition, on the model alone
+    wants = {k: edit_model(texts, a, qs, cq, cb, hits, k) for k in (0, 2, 3, 7)}
+    for want in (wants[2], wants[7]):                   # the input condition, on the model alone
         assert (want[0] == 0).sum() > 20 and ((want[0] > 0) & (want[0] <= 2)).sum() > 60 and (want[0] > 2).sum() > 30
     g = gpu_index(texts, a)
     eng = DeviceEngine(g)
