@@ -145,6 +145,9 @@ pub const GDX_CIGAR_DIFF: u32 = 8;
 pub const GDX_CAND_NONE: u32 = 0xFFFF_FFFF;
 pub const GDX_CAND_BAD_SEEDS: u8 = 1;
 pub const GDX_CAND_MAX_ANCHORS: u32 = 1024;
+pub const GDX_BEST_NONE: u32 = 0xFFFF_FFFF;
+pub const GDX_BEST_MAPQ_NONE: u32 = 255;
+pub const GDX_BEST_MAX_GROUP_SLOTS: u32 = 64;
 
 /// gdx_query_layout_t
 #[repr(C)]
@@ -322,6 +325,22 @@ extern "C" {
         out_n_groups: *mut u32, out_n_skipped: *mut u32, out_cand_query: *mut u32, out_cand_begin: *mut u32,
         out_cand_hits: *mut Hit, out_cand_weight: *mut u32, out_status: *mut u8,
     ) -> c_int;
+    /// Best hit per read (include/gdx_experimental.h "best hit per read"): every group of group_slots consecutive candidate
+    /// slots with the distances of a verify call -> the best slot, its distance, the runner-up's, the counts, a mapping quality
+    /// and the winner as a one-slot candidate; a group without a live slot gets GDX_BEST_NONE, GDX_BEST_MAPQ_NONE and the none
+    /// pattern.  d_end / end may be null
+    pub fn gdx_best_hits_many_dev(
+        ix: *const gdx_index_t, n_groups: u64, group_slots: u32, d_cand_query: *const c_void, d_cand_begin: *const c_void,
+        d_cand_hits: *const c_void, d_dist: *const c_void, d_end: *const c_void, max_dist: u32, d_best_slot: *mut c_void,
+        d_best_dist: *mut c_void, d_sub_dist: *mut c_void, d_n_live: *mut c_void, d_n_best: *mut c_void, d_mapq: *mut c_void,
+        d_win_query: *mut c_void, d_win_begin: *mut c_void, d_win_hits: *mut c_void, stream: *mut c_void,
+    ) -> c_int;
+    pub fn gdx_best_hits_many(
+        ix: *const gdx_index_t, n_groups: u64, group_slots: u32, cand_query: *const u32, cand_begin: *const u32,
+        cand_hits: *const Hit, dist: *const u32, end: *const u32, max_dist: u32, out_best_slot: *mut u32, out_best_dist: *mut u32,
+        out_sub_dist: *mut u32, out_n_live: *mut u32, out_n_best: *mut u32, out_mapq: *mut u32, out_win_query: *mut u32,
+        out_win_begin: *mut u32, out_win_hits: *mut Hit,
+    ) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
     ) -> c_int;
@@ -482,6 +501,20 @@ pub struct Alignment {
     pub dist: u32,
     pub span: Option<(u32, u32)>,
     pub cigar: Vec<(u32, u32)>,
+}
+
+/// One group's best hit (`GpuFmIndex::best_hits_many`): `slot` is None for a group without a live slot (then best_dist =
+/// sub_dist = max_dist + 1, mapq = GDX_BEST_MAPQ_NONE and `winner` is (GDX_CAND_NONE, 0, {0, 0})).  `winner` = (cand_query,
+/// cand_begin, hit) of the best slot, a candidate of `align_many`.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct BestHit {
+    pub slot: Option<u32>,
+    pub best_dist: u32,
+    pub sub_dist: u32,
+    pub n_live: u32,
+    pub n_best: u32,
+    pub mapq: u32,
+    pub winner: (u32, u32, Hit),
 }
 
 /// Hits of one call, owned by the library's allocation; handed out per query without copying.
@@ -818,6 +851,41 @@ impl GpuFmIndex {
                         (cb[k], hits[k], cw[k])
                     })
                     .collect()
+            })
+            .collect()
+    }
+
+    /// The reduction behind the verify calls: the slots are groups of `group_slots` consecutive candidates (`group_slots` =
+    /// the candidates call's max_candidates makes a group a query), `dist` what `hamming_many` / `edit_distance_many` gave for
+    /// them and `end` the ends of the latter, or None.  Per group the slot with the least (dist, slot) among those within
+    /// `max_dist`, duplicates of one locus counted once, with the runner-up's distance, the counts and a mapping quality.
+    /// Panics when `group_slots` is 0 or above GDX_BEST_MAX_GROUP_SLOTS, `max_dist` above 2^31, or the slices do not hold a
+    /// whole number of groups.
+    pub fn best_hits_many(
+        &self, group_slots: u32, cand_query: &[u32], cand_begin: &[u32], cand_hits: &[Hit], dist: &[u32], end: Option<&[u32]>,
+        max_dist: u32,
+    ) -> Vec<BestHit> {
+        let m = cand_query.len();
+        assert!(group_slots != 0 && m % group_slots as usize == 0);
+        assert!(cand_begin.len() == m && cand_hits.len() == m && dist.len() == m && end.map_or(true, |e| e.len() == m));
+        let ng = m / group_slots as usize;
+        let mut out: Vec<Vec<u32>> = (0..8).map(|_| vec![0u32; ng]).collect();
+        let mut win = vec![Hit { text_id: 0, position: 0 }; ng];
+        let p: Vec<*mut u32> = out.iter_mut().map(|v| v.as_mut_ptr()).collect();
+        check(unsafe {
+            gdx_best_hits_many(self.raw, ng as u64, group_slots, cand_query.as_ptr(), cand_begin.as_ptr(), cand_hits.as_ptr(),
+                               dist.as_ptr(), end.map_or(std::ptr::null(), |e| e.as_ptr()), max_dist, p[0], p[1], p[2], p[3], p[4],
+                               p[5], p[6], p[7], win.as_mut_ptr())
+        });
+        (0..ng)
+            .map(|g| BestHit {
+                slot: if out[0][g] == GDX_BEST_NONE { None } else { Some(out[0][g]) },
+                best_dist: out[1][g],
+                sub_dist: out[2][g],
+                n_live: out[3][g],
+                n_best: out[4][g],
+                mapq: out[5][g],
+                winner: (out[6][g], out[7][g], win[g]),
             })
             .collect()
     }

@@ -42,6 +42,9 @@ GDX_CIGAR_DIFF = 8
 GDX_CAND_NONE = 0xFFFFFFFF        # gdx_seed_candidates_many[_dev]: cand_query of an unused slot
 GDX_CAND_BAD_SEEDS = 1            # status: the query's seed slots fail the check
 GDX_CAND_MAX_ANCHORS = 1024       # max_seeds * max_occ at most
+GDX_BEST_NONE = 0xFFFFFFFF        # gdx_best_hits_many[_dev]: best_slot of a group without a live slot
+GDX_BEST_MAPQ_NONE = 255          # mapq of such a group
+GDX_BEST_MAX_GROUP_SLOTS = 64     # group_slots at most
 GDX_Q_OK = 0
 GDX_Q_INVALID_SYMBOL = 1
 GDX_Q_UNSEARCHABLE_IN_LOOKUP = 2
@@ -254,6 +257,9 @@ SIGNATURES = {
                                      vp, vp, vp, vp, vp, vp],
     "gdx_seed_candidates_many": [vp, C.c_uint64, C.c_uint32, u32p, u32p, u32p, u64p, u64p, C.c_uint32, C.c_uint32, C.c_uint32,
                                  u32p, u32p, u32p, u32p, u32p, C.POINTER(HitStruct), u32p, u8p],
+    "gdx_best_hits_many_dev": [vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "gdx_best_hits_many": [vp, C.c_uint64, C.c_uint32, u32p, u32p, C.POINTER(HitStruct), u32p, u32p, C.c_uint32, u32p, u32p, u32p,
+                           u32p, u32p, u32p, u32p, u32p, C.POINTER(HitStruct)],
     # gdx_bench.h
     "gdx_index_build_stats": [vp, C.POINTER(BuildStats)],
     "gdx_synth_text_dev": [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp],

@@ -1898,6 +1898,46 @@ int gdx_seed_candidates_many(const gdx_index_t *ix, uint64_t nq, uint32_t max_se
     });
 }
 
+// ---- best hit per read (best_hits.hip) ---------------------------------------------------------------------------
+
+int gdx_best_hits_many_dev(const gdx_index_t *ix, uint64_t n_groups, uint32_t group_slots, const void *d_cand_query,
+                           const void *d_cand_begin, const void *d_cand_hits, const void *d_dist, const void *d_end, uint32_t max_dist,
+                           void *d_best_slot, void *d_best_dist, void *d_sub_dist, void *d_n_live, void *d_n_best, void *d_mapq,
+                           void *d_win_query, void *d_win_begin, void *d_win_hits, void *stream)
+{
+    return guarded([&] {
+        const gdx::FmIndex &f = deref(ix);
+        f.check_best_hits(n_groups, group_slots, max_dist);
+        if (n_groups == 0) return (int)GDX_OK;
+        if (!d_cand_query || !d_cand_begin || !d_cand_hits || !d_dist || !d_best_slot || !d_best_dist || !d_sub_dist || !d_n_live ||
+            !d_n_best || !d_mapq || !d_win_query || !d_win_begin || !d_win_hits)
+            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+        DeviceGuard guard(f.config().device_id);
+        gdx::launch_best_hits(n_groups, group_slots, static_cast<const uint32_t *>(d_cand_query),
+                              static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits),
+                              static_cast<const uint32_t *>(d_dist), static_cast<const uint32_t *>(d_end), max_dist,
+                              static_cast<uint32_t *>(d_best_slot), static_cast<uint32_t *>(d_best_dist),
+                              static_cast<uint32_t *>(d_sub_dist), static_cast<uint32_t *>(d_n_live), static_cast<uint32_t *>(d_n_best),
+                              static_cast<uint32_t *>(d_mapq), static_cast<uint32_t *>(d_win_query),
+                              static_cast<uint32_t *>(d_win_begin), static_cast<gdx_hit32_t *>(d_win_hits), as_stream(stream));
+        GDX_HIP(hipGetLastError());
+        return (int)GDX_OK;
+    });
+}
+
+int gdx_best_hits_many(const gdx_index_t *ix, uint64_t n_groups, uint32_t group_slots, const uint32_t *cand_query,
+                       const uint32_t *cand_begin, const gdx_hit_t *cand_hits, const uint32_t *dist, const uint32_t *end,
+                       uint32_t max_dist, uint32_t *out_best_slot, uint32_t *out_best_dist, uint32_t *out_sub_dist, uint32_t *out_n_live,
+                       uint32_t *out_n_best, uint32_t *out_mapq, uint32_t *out_win_query, uint32_t *out_win_begin,
+                       gdx_hit_t *out_win_hits)
+{
+    return guarded([&] {
+        return deref(ix).best_hits_many(n_groups, group_slots, cand_query, cand_begin, cand_hits, dist, end, max_dist, out_best_slot,
+                                        out_best_dist, out_sub_dist, out_n_live, out_n_best, out_mapq, out_win_query, out_win_begin,
+                                        out_win_hits);
+    });
+}
+
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {

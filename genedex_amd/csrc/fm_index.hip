@@ -2517,6 +2517,64 @@ int FmIndex::seed_candidates_many(uint64_t nq, uint32_t max_seeds, const uint32_
     return any_status(st.data(), nq);
 }
 
+void FmIndex::check_best_hits(uint64_t n_groups, uint32_t group_slots, uint32_t max_dist) const
+{
+    if (group_slots == 0 || group_slots > GDX_BEST_MAX_GROUP_SLOTS)
+        fail(GDX_ERR_INVALID_ARGUMENT, "group_slots must be 1..%u", GDX_BEST_MAX_GROUP_SLOTS);
+    if (max_dist > 0x80000000u) fail(GDX_ERR_INVALID_ARGUMENT, "max_dist must not exceed 2^31");
+    if (n_groups > ~0ull / group_slots)
+        fail(GDX_ERR_INVALID_ARGUMENT, "%llu groups of %u slots: the number of slots does not fit 64 bits", (unsigned long long)n_groups,
+             group_slots);
+}
+
+int FmIndex::best_hits_many(uint64_t n_groups, uint32_t group_slots, const uint32_t *cand_query, const uint32_t *cand_begin,
+                            const gdx_hit_t *cand_hits, const uint32_t *dist, const uint32_t *end, uint32_t max_dist,
+                            uint32_t *out_best_slot, uint32_t *out_best_dist, uint32_t *out_sub_dist, uint32_t *out_n_live,
+                            uint32_t *out_n_best, uint32_t *out_mapq, uint32_t *out_win_query, uint32_t *out_win_begin,
+                            gdx_hit_t *out_win_hits) const
+{
+    check_best_hits(n_groups, group_slots, max_dist);
+    if (n_groups == 0) return GDX_OK;
+    if (!cand_query || !cand_begin || !cand_hits || !dist || !out_best_slot || !out_best_dist || !out_sub_dist || !out_n_live ||
+        !out_n_best || !out_mapq || !out_win_query || !out_win_begin || !out_win_hits)
+        fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+    const uint64_t m = n_groups * group_slots;
+    std::vector<gdx_hit32_t> narrow(m);
+    for (uint64_t s = 0; s < m; s++) {
+        if (cand_hits[s].position > 0xffffffffull || cand_hits[s].text_id > 0xffffffffull)
+            fail(GDX_ERR_INVALID_ARGUMENT, "slot %llu: hit (%llu, %llu) does not fit 32 bits", (unsigned long long)s,
+                 (unsigned long long)cand_hits[s].text_id, (unsigned long long)cand_hits[s].position);
+        narrow[s].text_id = static_cast<uint32_t>(cand_hits[s].text_id);
+        narrow[s].position = static_cast<uint32_t>(cand_hits[s].position);
+    }
+    make_current();
+    hipStream_t stream = hipStreamPerThread;
+    DeviceBuffer<uint32_t> d_in((end ? 4 : 3) * m);  // query, begin, dist, end
+    DeviceBuffer<uint32_t> d_out(8 * n_groups);      // the six results, win_query, win_begin
+    DeviceBuffer<gdx_hit32_t> d_hits(m), d_win(n_groups);
+    GDX_HIP(hipMemcpyAsync(d_in.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_in.get() + m, cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_in.get() + 2 * m, dist, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    if (end) GDX_HIP(hipMemcpyAsync(d_in.get() + 3 * m, end, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
+    uint32_t *o = d_out.get();
+    launch_best_hits(n_groups, group_slots, d_in.get(), d_in.get() + m, d_hits.get(), d_in.get() + 2 * m,
+                     end ? d_in.get() + 3 * m : nullptr, max_dist, o, o + n_groups, o + 2 * n_groups, o + 3 * n_groups, o + 4 * n_groups,
+                     o + 5 * n_groups, o + 6 * n_groups, o + 7 * n_groups, d_win.get(), stream);
+    GDX_HIP(hipGetLastError());
+    std::vector<gdx_hit32_t> win(n_groups);
+    uint32_t *outs[8] = {out_best_slot, out_best_dist, out_sub_dist, out_n_live, out_n_best, out_mapq, out_win_query, out_win_begin};
+    for (int x = 0; x < 8; x++)
+        GDX_HIP(hipMemcpyAsync(outs[x], o + x * n_groups, n_groups * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(win.data(), d_win.get(), n_groups * sizeof(gdx_hit32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipStreamSynchronize(stream));
+    for (uint64_t g = 0; g < n_groups; g++) {
+        out_win_hits[g].text_id = win[g].text_id;
+        out_win_hits[g].position = win[g].position;
+    }
+    return GDX_OK;
+}
+
 int FmIndex::rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const
 {
     if (m == 0) return GDX_OK;

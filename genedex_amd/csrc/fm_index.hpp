@@ -166,6 +166,14 @@ public:
                              uint32_t *out_cand_begin, gdx_hit_t *out_cand_hits, uint32_t *out_cand_weight, uint8_t *out_status) const;
     // what both forms of gdx_seed_candidates_many refuse before they look at the batch
     void check_seed_candidates(uint32_t max_seeds, uint32_t max_occ, uint32_t max_candidates) const;
+    // gdx_best_hits_many: the whole batch staged (copy in, one launch, copy out); cand_hits narrowed to 32 bits (a position of
+    // 2^32 or more is refused), win_hits widened to gdx_hit_t; end may be null
+    int best_hits_many(uint64_t n_groups, uint32_t group_slots, const uint32_t *cand_query, const uint32_t *cand_begin,
+                       const gdx_hit_t *cand_hits, const uint32_t *dist, const uint32_t *end, uint32_t max_dist, uint32_t *out_best_slot,
+                       uint32_t *out_best_dist, uint32_t *out_sub_dist, uint32_t *out_n_live, uint32_t *out_n_best, uint32_t *out_mapq,
+                       uint32_t *out_win_query, uint32_t *out_win_begin, gdx_hit_t *out_win_hits) const;
+    // what both forms of gdx_best_hits_many refuse before they look at the batch
+    void check_best_hits(uint64_t n_groups, uint32_t group_slots, uint32_t max_dist) const;
     int rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const;
     int symbol_at_many(const uint64_t *idx, uint64_t m, uint8_t *out) const;
 

@@ -212,6 +212,16 @@ void launch_seed_candidates(const IndexView &ix, uint64_t nq, uint32_t max_seeds
                             uint32_t *d_cand_query, uint32_t *d_cand_begin, gdx_hit32_t *d_cand_hits, uint32_t *d_cand_weight,
                             uint8_t *d_status, hipStream_t stream);
 
+// ---- best_hits.hip ------------------------------------------------------------------------
+// gdx_best_hits_many_dev: n_groups groups of group_slots consecutive candidate slots and their distances from a verify call ->
+// per group the best slot, its distance, the runner-up's, the two counts, the mapping quality and the winner as a one-slot
+// candidate (the none pattern for a group without a live slot).  The caller has checked 1 <= group_slots <=
+// GDX_BEST_MAX_GROUP_SLOTS, max_dist <= 2^31 and that n_groups * group_slots fits 64 bits.  d_end may be null.  One launch.
+void launch_best_hits(uint64_t n_groups, uint32_t group_slots, const uint32_t *d_cand_query, const uint32_t *d_cand_begin,
+                      const gdx_hit32_t *d_cand_hits, const uint32_t *d_dist, const uint32_t *d_end, uint32_t max_dist,
+                      uint32_t *d_best_slot, uint32_t *d_best_dist, uint32_t *d_sub_dist, uint32_t *d_n_live, uint32_t *d_n_best,
+                      uint32_t *d_mapq, uint32_t *d_win_query, uint32_t *d_win_begin, gdx_hit32_t *d_win_hits, hipStream_t stream);
+
 // ---- locate.hip ---------------------------------------------------------------------------
 size_t hit_offsets_temp_bytes(uint64_t m);
 void launch_hit_offsets(const uint32_t *d_start, const uint32_t *d_end, uint64_t m, uint64_t *d_hit_offsets,

@@ -557,6 +557,60 @@ class DeviceEngine:
                                                None, _stream()))
         return out
 
+    # ---- best hit per read (gdx_best_hits_many_dev) -----------------------------------------------------------
+    def alloc_best_hits(self, n_groups: int):
+        d = self.dev
+        n = max(n_groups, 1)
+        out = {name: torch.empty(n, dtype=torch.int32, device=d)
+               for name in ("best_slot", "best_dist", "sub_dist", "n_live", "n_best", "mapq", "win_query", "win_begin")}
+        out["win_hits"] = torch.empty((n, 2), dtype=torch.int32, device=d)
+        return out
+
+    def best_hits(self, cands: dict, dist: torch.Tensor, end, n_groups: int, group_slots: int, max_dist: int, out: dict = None):
+        """One launch: every group of group_slots consecutive candidate slots and the distances a verify call gave them -> the
+        group's best hit in `out` (alloc_best_hits; made here when None) -> out.  cands: the `out` dict of seed_candidates() as
+        it is ("cand_query", "cand_begin", "cand_hits"); dist / end: what edit_distance() returned for all its slots, end None
+        after hamming().  group_slots = max_candidates makes a group a query; after with_strands(mode="both") group_slots =
+        2 * max_candidates makes it a read.  out["win_query"], ["win_begin"] and ["win_hits"] go straight into align() /
+        edit_distance() / hamming() as n_groups candidates: an unmapped read (best_slot -1, GDX_BEST_NONE; mapq 255) has
+        win_query -1 (GDX_CAND_NONE) and gets the verify call's INVALID marker."""
+        m = _check_candidates(cands["cand_query"], cands["cand_begin"], cands["cand_hits"])
+        n_groups, group_slots = int(n_groups), int(group_slots)
+        if n_groups * group_slots > m or dist.numel() < n_groups * group_slots or (end is not None and end.numel() < n_groups * group_slots):
+            raise ValueError("candidates, dist and end hold n_groups * group_slots slots")
+        if out is None:
+            out = self.alloc_best_hits(n_groups)
+        _lib.check(self.lib.gdx_best_hits_many_dev(
+            self.h, n_groups, group_slots, _ptr(cands["cand_query"]), _ptr(cands["cand_begin"]), _ptr(cands["cand_hits"]), _ptr(dist),
+            _ptr(end) if end is not None else None, int(max_dist), _ptr(out["best_slot"]), _ptr(out["best_dist"]),
+            _ptr(out["sub_dist"]), _ptr(out["n_live"]), _ptr(out["n_best"]), _ptr(out["mapq"]), _ptr(out["win_query"]),
+            _ptr(out["win_begin"]), _ptr(out["win_hits"]), _stream()))
+        return out
+
+    def map_reads(self, q: DeviceQueries, reversed_index, *, max_smems: int, min_length: int, max_occ: int, band: int,
+                  max_candidates: int, max_edits: int, both_strands: bool = True) -> dict:
+        """The seed-and-verify chain on resident reads, every stage reading what the one before left in HBM: with_strands ->
+        smems -> seed_candidates -> edit_distance -> best_hits -> align over the winners, one slot per read.  q: a plain batch;
+        reversed_index as in smems().
+        -> per-read tensors (u32 values in int32): "strand" (1 = the reverse complement; 0 without both_strands), "text_id",
+        "begin", "end" (the alignment's text range), "dist", "sub_dist", "n_best", "mapq", "n_cigar" and "cigar" (int32[reads,
+        2 max_edits + 1]).  An unmapped read has mapq 255 (GDX_BEST_MAPQ_NONE), n_best 0, n_cigar 0, begin and end -1, dist and
+        sub_dist max_edits + 1; its strand and text_id say nothing.  The align workspace is sized for one candidate per read.
+        No result crosses to the host in between (with_strands reads the batch's symbol count once to size its output)."""
+        n_reads = q.nq
+        sq = q.with_strands(self.index, "both") if both_strands else q
+        nq, mc = sq.nq, int(max_candidates)
+        seeds = self.alloc_smems(nq, int(max_smems))
+        self.smems(sq, reversed_index, int(max_smems), int(min_length), seeds)
+        cands = self.seed_candidates(seeds, nq, int(max_smems), max_occ, band, mc)
+        dist, end = self.edit_distance(sq, cands["cand_query"], cands["cand_begin"], cands["cand_hits"], max_edits)
+        best = self.best_hits(cands, dist, end, n_reads, mc * (2 if both_strands else 1), max_edits)
+        aligned = self.align(sq, best["win_query"][:n_reads], best["win_begin"][:n_reads], best["win_hits"][:n_reads], max_edits)
+        strand = best["win_query"] & 1 if both_strands else torch.zeros_like(best["win_query"])  # (win_query = 2 read + strand)
+        return {"strand": strand, "text_id": best["win_hits"][:, 0], "begin": aligned["begin"], "end": aligned["end"],
+                "dist": best["best_dist"], "sub_dist": best["sub_dist"], "n_best": best["n_best"], "mapq": best["mapq"],
+                "n_cigar": aligned["n_cigar"], "cigar": aligned["cigar"]}
+
     def search_step_stats(self, q: DeviceQueries):
         """(LF steps, line fetches of all queries, fetch slots their wavefronts spent)"""
         steps = torch.zeros(3, dtype=torch.int64, device=self.dev)

@@ -585,6 +585,29 @@ class FmIndex:
         return [[SeedCandidate(int(cb[k]), int(t[k]), int(p[k]), int(cw[k])) for k in range(i * mc, i * mc + int(n_cand[i]))]
                 for i in range(nq)]
 
+    # ---- best hit per read (gdx_experimental.h "best hit per read") ------------------------------------------
+    def best_hits_raw(self, cand_query, cand_begin, text_ids, positions, dist, end, n_groups, group_slots, max_dist):
+        """gdx_best_hits_many -> (best_slot, best_dist, sub_dist, n_live, n_best, mapq, win_query, win_begin: u32[n_groups];
+        win_text_ids, win_positions: u64[n_groups]): every group of group_slots consecutive candidate slots (the arrays of
+        seed_candidates_raw) with the distances a verify call gave them reduced to its best hit; `end` = the ends of the
+        edit-distance call, or None (the Hamming case: the diagonal tells loci apart).  A group without a live slot has
+        best_slot GDX_BEST_NONE, mapq GDX_BEST_MAPQ_NONE and the none pattern as its winner."""
+        ng, gs = int(n_groups), int(group_slots)
+        m = ng * gs
+        cq, cb, dist = (np.ascontiguousarray(x, dtype=np.uint32) for x in (cand_query, cand_begin, dist))
+        end = None if end is None else np.ascontiguousarray(end, dtype=np.uint32)
+        hits = np.ascontiguousarray(np.stack([np.asarray(text_ids, dtype=np.uint64), np.asarray(positions, dtype=np.uint64)], axis=1))
+        for x in (cq, cb, dist, end, hits[:, 0]):
+            if x is not None and x.size != m:
+                raise ValueError("slot arrays hold n_groups * group_slots slots")
+        outs = [np.zeros(max(ng, 1), dtype=np.uint32) for _ in range(8)]
+        win = np.zeros((max(ng, 1), 2), dtype=np.uint64)
+        _lib.check(self._lib.gdx_best_hits_many(self._h, ng, gs, _p(cq, u32p), _p(cb, u32p),
+                                                hits.ctypes.data_as(C.POINTER(_lib.HitStruct)), _p(dist, u32p),
+                                                _p(end, u32p) if end is not None else None, int(max_dist),
+                                                *(_p(o, u32p) for o in outs), win.ctypes.data_as(C.POINTER(_lib.HitStruct))))
+        return tuple(o[:ng] for o in outs) + (win[:ng, 0], win[:ng, 1])
+
     def rank_many(self, symbols, idx):
         """TextWithRankSupport::rank (text_with_rank_support/mod.rs:106-110), batched."""
         sym = np.ascontiguousarray(symbols, dtype=np.uint8)

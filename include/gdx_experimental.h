@@ -3,9 +3,9 @@
  * replaced, hint arrays, compact-result plumbing of the multi-GPU gather) and building blocks the tests and bench.py still
  * drive one by one.  Exported and tested like the core (tests/test_abi.py, tests/test_gpu_*.py), but not what a binding of the
  * reference's API needs (INTEGRATION.md binds gdx.h only), and free to change.  Every call returns the results of the core call
- * it is a part of: lib.rs:155-246 of the reference.  The last section, "seed-hit candidates", is a call of the seed-and-verify
- * chain that the reference has no counterpart of; it is declared here because the core header keeps to its budget of names
- * (tests/test_abi.py). */
+ * it is a part of: lib.rs:155-246 of the reference.  The last two sections, "seed-hit candidates" and "best hit per read", are
+ * calls of the seed-and-verify chain that the reference has no counterpart of; they are declared here because the core header
+ * keeps to its budget of names (tests/test_abi.py). */
 #ifndef GDX_EXPERIMENTAL_H
 #define GDX_EXPERIMENTAL_H
 
@@ -245,6 +245,56 @@ int gdx_seed_candidates_many(const gdx_index_t *ix, uint64_t nq, uint32_t max_se
                              uint32_t max_occ, uint32_t band, uint32_t max_candidates, uint32_t *out_n_candidates,
                              uint32_t *out_n_groups, uint32_t *out_n_skipped, uint32_t *out_cand_query, uint32_t *out_cand_begin,
                              gdx_hit_t *out_cand_hits, uint32_t *out_cand_weight, uint8_t *out_status /*or NULL*/);
+
+/* ---- best hit per read (the reduction between the verify calls of gdx.h and gdx_align_many) ------------------------------
+ * gdx_hamming_many and gdx_edit_distance_many give one distance per candidate slot; a mapper wants one alignment per read, to
+ * know whether it is unique, and a traceback of that one alone.  gdx_best_hits_many reduces every GROUP of group_slots
+ * consecutive slots to one record and writes the group's winner as a one-slot candidate list.
+ * Inputs: m = n_groups * group_slots slots, slot j of group g being g * group_slots + j: cand_query, cand_begin, cand_hits as
+ * gdx_seed_candidates_many[_dev] writes them (group_slots = its max_candidates: a group is a query), dist as a verify call wrote
+ * it for these slots, and end (gdx_edit_distance_many's out_end) or NULL.  After gdx_strands_expand_dev with GDX_STRANDS_BOTH
+ * queries 2i and 2i + 1 are the two strands of read i and their 2 * max_candidates slots are adjacent: group_slots =
+ * 2 * max_candidates makes a group a read.  The call never looks at the queries or at the index's arrays.
+ * Per group g, with k = max_dist:
+ *  1. Live.  Slot j is live when cand_query[j] != GDX_CAND_NONE and dist[j] <= k.  GDX_EDIT_INVALID, GDX_EDIT_TOO_LONG,
+ *     GDX_HAMMING_INVALID and the capped value k + 1 are all > k: a dead slot needs no special case.
+ *  2. Same locus.  The key of a live slot is (cand_query, text_id, e): e = end[j] when end is given, otherwise the diagonal
+ *     position - cand_begin in wrapping 32-bit arithmetic (the Hamming case).  Of the live slots with one key only the one with
+ *     the least (dist, j) stays live; the others are duplicates: two diagonal bands that reach the same alignment must not make
+ *     a read look ambiguous.
+ *  3. Results, over the slots still live.  n_live = their number.  The best slot is the one with the least (dist, j): best_slot
+ *     = j, best_dist = its distance.  n_best = the live slots with dist == best_dist.  sub_dist = the least distance among the
+ *     live slots other than the best one: best_dist when n_best >= 2, k + 1 when there is no other live slot.
+ *     mapq = min(60, 60 * (sub_dist - best_dist) / (k + 1)), in 64 bits with integer division: 0 for a tie, 60 for a lone hit
+ *     at distance 0.  A group without a live slot gets best_slot = GDX_BEST_NONE, best_dist = sub_dist = k + 1, n_live = n_best
+ *     = 0 and mapq = GDX_BEST_MAPQ_NONE.  The raw fields are returned so that a caller with another quality model can apply it.
+ *  4. Winner.  win_query[g], win_begin[g], win_hits[g] are cand_query, cand_begin, cand_hits of the best slot; for a group
+ *     without one they hold the none pattern of the candidates call: GDX_CAND_NONE, 0, {0, 0}.
+ * The three winner arrays go straight into gdx_align_many_dev, gdx_edit_distance_many_dev and gdx_hamming_many_dev with m =
+ * n_groups: an unmapped read gets their *_INVALID marker there, as an unused candidate slot does.  With GDX_STRANDS_BOTH in
+ * front and group_slots = 2 * max_candidates, win_query >> 1 is the read and win_query & 1 its strand.
+ * Device form: ONE launch, no synchronisation, no allocation, no copy from pageable memory; returns GDX_OK.  All nine outputs
+ * are u32[n_groups] (d_win_hits: gdx_hit32_t[n_groups]) and must not overlap the inputs.  Host form: the same arguments without
+ * the stream; cand_hits and win_hits are gdx_hit_t (a text id or a position of 2^32 or more: GDX_ERR_INVALID_ARGUMENT).  It
+ * stages the whole batch (copy in, one launch, copy out) like gdx_seed_candidates_many.
+ * GDX_ERR_INVALID_ARGUMENT: group_slots == 0 or > GDX_BEST_MAX_GROUP_SLOTS; max_dist > 2^31; n_groups * group_slots does not fit
+ * 64 bits; a null required pointer (only d_end / end may be null).  GDX_ERR_UNSUPPORTED: a handle of the 64-bit engine.
+ * n_groups == 0 is GDX_OK and writes nothing.  A refused call writes nothing.  gdx_parts_t and gdx_multi_t have no such call.
+ * Out of scope: secondary alignments beyond the counts, paired-end pairing, a compacted list of the mapped reads only. */
+#define GDX_BEST_NONE            0xFFFFFFFFu  /* best_slot of a group without a live slot       */
+#define GDX_BEST_MAPQ_NONE       255u         /* mapq of such a group (SAM: not available)      */
+#define GDX_BEST_MAX_GROUP_SLOTS 64u          /* the most slots of one group                    */
+int gdx_best_hits_many_dev(const gdx_index_t *ix, uint64_t n_groups, uint32_t group_slots, const void *d_cand_query /*u32[m]*/,
+                           const void *d_cand_begin /*u32[m]*/, const void *d_cand_hits /*gdx_hit32_t[m]*/,
+                           const void *d_dist /*u32[m]*/, const void *d_end /*u32[m] or NULL*/, uint32_t max_dist,
+                           void *d_best_slot, void *d_best_dist, void *d_sub_dist, void *d_n_live, void *d_n_best,
+                           void *d_mapq /*u32[n_groups] each*/, void *d_win_query /*u32[n_groups]*/,
+                           void *d_win_begin /*u32[n_groups]*/, void *d_win_hits /*gdx_hit32_t[n_groups]*/, void *stream);
+int gdx_best_hits_many(const gdx_index_t *ix, uint64_t n_groups, uint32_t group_slots, const uint32_t *cand_query,
+                       const uint32_t *cand_begin, const gdx_hit_t *cand_hits, const uint32_t *dist, const uint32_t *end /*or NULL*/,
+                       uint32_t max_dist, uint32_t *out_best_slot, uint32_t *out_best_dist, uint32_t *out_sub_dist,
+                       uint32_t *out_n_live, uint32_t *out_n_best, uint32_t *out_mapq, uint32_t *out_win_query,
+                       uint32_t *out_win_begin, gdx_hit_t *out_win_hits);
 
 #ifdef __cplusplus
 }
