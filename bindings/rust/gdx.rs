@@ -148,6 +148,9 @@ pub const GDX_CAND_MAX_ANCHORS: u32 = 1024;
 pub const GDX_BEST_NONE: u32 = 0xFFFF_FFFF;
 pub const GDX_BEST_MAPQ_NONE: u32 = 255;
 pub const GDX_BEST_MAX_GROUP_SLOTS: u32 = 64;
+pub const GDX_PAIR_NONE: u32 = 0xFFFF_FFFF;
+pub const GDX_PAIR_MAPQ_NONE: u32 = 255;
+pub const GDX_PAIR_MAX_MATE_SLOTS: u32 = 32;
 
 /// gdx_query_layout_t
 #[repr(C)]
@@ -341,6 +344,24 @@ extern "C" {
         out_sub_dist: *mut u32, out_n_live: *mut u32, out_n_best: *mut u32, out_mapq: *mut u32, out_win_query: *mut u32,
         out_win_begin: *mut u32, out_win_hits: *mut Hit,
     ) -> c_int;
+    /// Paired-end pairing (include/gdx_experimental.h "paired-end pairing"): 2 * n_pairs mates of mate_slots consecutive
+    /// candidate slots with the distances of a verify call -> per pair the best proper combination (one text, opposite strands,
+    /// min_insert <= span <= max_insert), its counts and mapping quality; per mate the winner as a one-slot candidate, the
+    /// single-end best when the pair has no proper combination.  d_end / end may be null
+    pub fn gdx_pair_hits_many_dev(
+        ix: *const gdx_index_t, n_pairs: u64, mate_slots: u32, d_cand_query: *const c_void, d_cand_begin: *const c_void,
+        d_cand_hits: *const c_void, d_dist: *const c_void, d_end: *const c_void, max_dist: u32, min_insert: u32, max_insert: u32,
+        d_n_proper: *mut c_void, d_n_best: *mut c_void, d_pair_dist: *mut c_void, d_sub_dist: *mut c_void, d_mapq: *mut c_void,
+        d_pair_span: *mut c_void, d_mate_slot: *mut c_void, d_mate_dist: *mut c_void, d_win_query: *mut c_void,
+        d_win_begin: *mut c_void, d_win_hits: *mut c_void, stream: *mut c_void,
+    ) -> c_int;
+    pub fn gdx_pair_hits_many(
+        ix: *const gdx_index_t, n_pairs: u64, mate_slots: u32, cand_query: *const u32, cand_begin: *const u32,
+        cand_hits: *const Hit, dist: *const u32, end: *const u32, max_dist: u32, min_insert: u32, max_insert: u32,
+        out_n_proper: *mut u32, out_n_best: *mut u32, out_pair_dist: *mut u32, out_sub_dist: *mut u32, out_mapq: *mut u32,
+        out_pair_span: *mut u32, out_mate_slot: *mut u32, out_mate_dist: *mut u32, out_win_query: *mut u32,
+        out_win_begin: *mut u32, out_win_hits: *mut Hit,
+    ) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
     ) -> c_int;
@@ -515,6 +536,28 @@ pub struct BestHit {
     pub n_best: u32,
     pub mapq: u32,
     pub winner: (u32, u32, Hit),
+}
+
+/// One mate of a `PairHit`: `slot` is None for a mate without a live slot (then dist = max_dist + 1 and `winner` is
+/// (GDX_CAND_NONE, 0, {0, 0})).  `winner` = (cand_query, cand_begin, hit) of the slot, a candidate of `align_many`.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct MateHit {
+    pub slot: Option<u32>,
+    pub dist: u32,
+    pub winner: (u32, u32, Hit),
+}
+
+/// One pair's result (`GpuFmIndex::pair_hits_many`): without a proper combination n_proper = n_best = 0, pair_dist = sub_dist =
+/// 2 max_dist + 2, pair_span = 0, mapq = GDX_PAIR_MAPQ_NONE and `mates` are the single-end bests.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct PairHit {
+    pub n_proper: u32,
+    pub n_best: u32,
+    pub pair_dist: u32,
+    pub sub_dist: u32,
+    pub mapq: u32,
+    pub pair_span: u32,
+    pub mates: [MateHit; 2],
 }
 
 /// Hits of one call, owned by the library's allocation; handed out per query without copying.
@@ -886,6 +929,47 @@ impl GpuFmIndex {
                 n_best: out[4][g],
                 mapq: out[5][g],
                 winner: (out[6][g], out[7][g], win[g]),
+            })
+            .collect()
+    }
+
+    /// Paired-end pairing: the slots are mates of `mate_slots` consecutive candidates, mates 2p and 2p + 1 making pair p;
+    /// `dist` / `end` as in `best_hits_many`.  Per pair the best combination of one live slot of each mate that lies on one
+    /// text, on opposite strands and with min_insert <= span <= max_insert, whether it is unique, and per mate the winner.
+    /// Panics when `mate_slots` is 0 or above GDX_PAIR_MAX_MATE_SLOTS, `max_dist` above 2^30, the insert bounds are not
+    /// min_insert <= max_insert <= 2^31 - 1, or the slices do not hold a whole number of pairs.
+    pub fn pair_hits_many(
+        &self, mate_slots: u32, cand_query: &[u32], cand_begin: &[u32], cand_hits: &[Hit], dist: &[u32], end: Option<&[u32]>,
+        max_dist: u32, min_insert: u32, max_insert: u32,
+    ) -> Vec<PairHit> {
+        let m = cand_query.len();
+        assert!(mate_slots != 0 && m % (2 * mate_slots as usize) == 0);
+        assert!(cand_begin.len() == m && cand_hits.len() == m && dist.len() == m && end.map_or(true, |e| e.len() == m));
+        let np = m / (2 * mate_slots as usize);
+        let mut pairs: Vec<Vec<u32>> = (0..6).map(|_| vec![0u32; np]).collect();
+        let mut mates: Vec<Vec<u32>> = (0..4).map(|_| vec![0u32; 2 * np]).collect();
+        let mut win = vec![Hit { text_id: 0, position: 0 }; 2 * np];
+        let p: Vec<*mut u32> = pairs.iter_mut().map(|v| v.as_mut_ptr()).collect();
+        let q: Vec<*mut u32> = mates.iter_mut().map(|v| v.as_mut_ptr()).collect();
+        check(unsafe {
+            gdx_pair_hits_many(self.raw, np as u64, mate_slots, cand_query.as_ptr(), cand_begin.as_ptr(), cand_hits.as_ptr(),
+                               dist.as_ptr(), end.map_or(std::ptr::null(), |e| e.as_ptr()), max_dist, min_insert, max_insert,
+                               p[0], p[1], p[2], p[3], p[4], p[5], q[0], q[1], q[2], q[3], win.as_mut_ptr())
+        });
+        let mate = |x: usize| MateHit {
+            slot: if mates[0][x] == GDX_PAIR_NONE { None } else { Some(mates[0][x]) },
+            dist: mates[1][x],
+            winner: (mates[2][x], mates[3][x], win[x]),
+        };
+        (0..np)
+            .map(|g| PairHit {
+                n_proper: pairs[0][g],
+                n_best: pairs[1][g],
+                pair_dist: pairs[2][g],
+                sub_dist: pairs[3][g],
+                mapq: pairs[4][g],
+                pair_span: pairs[5][g],
+                mates: [mate(2 * g), mate(2 * g + 1)],
             })
             .collect()
     }

@@ -45,6 +45,9 @@ GDX_CAND_MAX_ANCHORS = 1024       # max_seeds * max_occ at most
 GDX_BEST_NONE = 0xFFFFFFFF        # gdx_best_hits_many[_dev]: best_slot of a group without a live slot
 GDX_BEST_MAPQ_NONE = 255          # mapq of such a group
 GDX_BEST_MAX_GROUP_SLOTS = 64     # group_slots at most
+GDX_PAIR_NONE = 0xFFFFFFFF        # gdx_pair_hits_many[_dev]: mate_slot of a mate without a live slot
+GDX_PAIR_MAPQ_NONE = 255          # mapq of a pair without a proper combination
+GDX_PAIR_MAX_MATE_SLOTS = 32      # mate_slots at most
 GDX_Q_OK = 0
 GDX_Q_INVALID_SYMBOL = 1
 GDX_Q_UNSEARCHABLE_IN_LOOKUP = 2
@@ -260,6 +263,10 @@ SIGNATURES = {
     "gdx_best_hits_many_dev": [vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "gdx_best_hits_many": [vp, C.c_uint64, C.c_uint32, u32p, u32p, C.POINTER(HitStruct), u32p, u32p, C.c_uint32, u32p, u32p, u32p,
                            u32p, u32p, u32p, u32p, u32p, C.POINTER(HitStruct)],
+    "gdx_pair_hits_many_dev": [vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
+                               vp, vp, vp, vp, vp, vp],
+    "gdx_pair_hits_many": [vp, C.c_uint64, C.c_uint32, u32p, u32p, C.POINTER(HitStruct), u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                           u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.POINTER(HitStruct)],
     # gdx_bench.h
     "gdx_index_build_stats": [vp, C.POINTER(BuildStats)],
     "gdx_synth_text_dev": [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp],

@@ -1938,6 +1938,49 @@ int gdx_best_hits_many(const gdx_index_t *ix, uint64_t n_groups, uint32_t group_
     });
 }
 
+// ---- paired-end pairing (pair_hits.hip) --------------------------------------------------------------------------
+
+int gdx_pair_hits_many_dev(const gdx_index_t *ix, uint64_t n_pairs, uint32_t mate_slots, const void *d_cand_query,
+                           const void *d_cand_begin, const void *d_cand_hits, const void *d_dist, const void *d_end, uint32_t max_dist,
+                           uint32_t min_insert, uint32_t max_insert, void *d_n_proper, void *d_n_best, void *d_pair_dist,
+                           void *d_sub_dist, void *d_mapq, void *d_pair_span, void *d_mate_slot, void *d_mate_dist, void *d_win_query,
+                           void *d_win_begin, void *d_win_hits, void *stream)
+{
+    return guarded([&] {
+        const gdx::FmIndex &f = deref(ix);
+        f.check_pair_hits(n_pairs, mate_slots, max_dist, min_insert, max_insert);
+        if (n_pairs == 0) return (int)GDX_OK;
+        if (!d_cand_query || !d_cand_begin || !d_cand_hits || !d_dist || !d_n_proper || !d_n_best || !d_pair_dist || !d_sub_dist ||
+            !d_mapq || !d_pair_span || !d_mate_slot || !d_mate_dist || !d_win_query || !d_win_begin || !d_win_hits)
+            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+        DeviceGuard guard(f.config().device_id);
+        gdx::launch_pair_hits(n_pairs, mate_slots, static_cast<const uint32_t *>(d_cand_query),
+                              static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits),
+                              static_cast<const uint32_t *>(d_dist), static_cast<const uint32_t *>(d_end), max_dist, min_insert,
+                              max_insert, static_cast<uint32_t *>(d_n_proper), static_cast<uint32_t *>(d_n_best),
+                              static_cast<uint32_t *>(d_pair_dist), static_cast<uint32_t *>(d_sub_dist), static_cast<uint32_t *>(d_mapq),
+                              static_cast<uint32_t *>(d_pair_span), static_cast<uint32_t *>(d_mate_slot),
+                              static_cast<uint32_t *>(d_mate_dist), static_cast<uint32_t *>(d_win_query),
+                              static_cast<uint32_t *>(d_win_begin), static_cast<gdx_hit32_t *>(d_win_hits), as_stream(stream));
+        GDX_HIP(hipGetLastError());
+        return (int)GDX_OK;
+    });
+}
+
+int gdx_pair_hits_many(const gdx_index_t *ix, uint64_t n_pairs, uint32_t mate_slots, const uint32_t *cand_query,
+                       const uint32_t *cand_begin, const gdx_hit_t *cand_hits, const uint32_t *dist, const uint32_t *end,
+                       uint32_t max_dist, uint32_t min_insert, uint32_t max_insert, uint32_t *out_n_proper, uint32_t *out_n_best,
+                       uint32_t *out_pair_dist, uint32_t *out_sub_dist, uint32_t *out_mapq, uint32_t *out_pair_span,
+                       uint32_t *out_mate_slot, uint32_t *out_mate_dist, uint32_t *out_win_query, uint32_t *out_win_begin,
+                       gdx_hit_t *out_win_hits)
+{
+    return guarded([&] {
+        return deref(ix).pair_hits_many(n_pairs, mate_slots, cand_query, cand_begin, cand_hits, dist, end, max_dist, min_insert,
+                                        max_insert, out_n_proper, out_n_best, out_pair_dist, out_sub_dist, out_mapq, out_pair_span,
+                                        out_mate_slot, out_mate_dist, out_win_query, out_win_begin, out_win_hits);
+    });
+}
+
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {

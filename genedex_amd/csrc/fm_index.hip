@@ -2575,6 +2575,71 @@ int FmIndex::best_hits_many(uint64_t n_groups, uint32_t group_slots, const uint3
     return GDX_OK;
 }
 
+void FmIndex::check_pair_hits(uint64_t n_pairs, uint32_t mate_slots, uint32_t max_dist, uint32_t min_insert, uint32_t max_insert) const
+{
+    if (mate_slots == 0 || mate_slots > GDX_PAIR_MAX_MATE_SLOTS)
+        fail(GDX_ERR_INVALID_ARGUMENT, "mate_slots must be 1..%u", GDX_PAIR_MAX_MATE_SLOTS);
+    if (max_dist > 0x40000000u) fail(GDX_ERR_INVALID_ARGUMENT, "max_dist must not exceed 2^30");
+    if (min_insert > max_insert || max_insert > 0x7fffffffu)
+        fail(GDX_ERR_INVALID_ARGUMENT, "insert bounds [%u, %u]: min_insert <= max_insert <= 2^31 - 1", min_insert, max_insert);
+    if (n_pairs > ~0ull / mate_slots / 2)
+        fail(GDX_ERR_INVALID_ARGUMENT, "%llu pairs of 2 x %u slots: the number of slots does not fit 64 bits", (unsigned long long)n_pairs,
+             mate_slots);
+}
+
+int FmIndex::pair_hits_many(uint64_t n_pairs, uint32_t mate_slots, const uint32_t *cand_query, const uint32_t *cand_begin,
+                            const gdx_hit_t *cand_hits, const uint32_t *dist, const uint32_t *end, uint32_t max_dist,
+                            uint32_t min_insert, uint32_t max_insert, uint32_t *out_n_proper, uint32_t *out_n_best,
+                            uint32_t *out_pair_dist, uint32_t *out_sub_dist, uint32_t *out_mapq, uint32_t *out_pair_span,
+                            uint32_t *out_mate_slot, uint32_t *out_mate_dist, uint32_t *out_win_query, uint32_t *out_win_begin,
+                            gdx_hit_t *out_win_hits) const
+{
+    check_pair_hits(n_pairs, mate_slots, max_dist, min_insert, max_insert);
+    if (n_pairs == 0) return GDX_OK;
+    if (!cand_query || !cand_begin || !cand_hits || !dist || !out_n_proper || !out_n_best || !out_pair_dist || !out_sub_dist ||
+        !out_mapq || !out_pair_span || !out_mate_slot || !out_mate_dist || !out_win_query || !out_win_begin || !out_win_hits)
+        fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+    const uint64_t n_mates = 2 * n_pairs, m = n_mates * mate_slots;
+    std::vector<gdx_hit32_t> narrow(m);
+    for (uint64_t s = 0; s < m; s++) {
+        if (cand_hits[s].position > 0xffffffffull || cand_hits[s].text_id > 0xffffffffull)
+            fail(GDX_ERR_INVALID_ARGUMENT, "slot %llu: hit (%llu, %llu) does not fit 32 bits", (unsigned long long)s,
+                 (unsigned long long)cand_hits[s].text_id, (unsigned long long)cand_hits[s].position);
+        narrow[s].text_id = static_cast<uint32_t>(cand_hits[s].text_id);
+        narrow[s].position = static_cast<uint32_t>(cand_hits[s].position);
+    }
+    make_current();
+    hipStream_t stream = hipStreamPerThread;
+    DeviceBuffer<uint32_t> d_in((end ? 4 : 3) * m);  // query, begin, dist, end
+    DeviceBuffer<uint32_t> d_out(14 * n_pairs);      // six per pair, then four per mate
+    DeviceBuffer<gdx_hit32_t> d_hits(m), d_win(n_mates);
+    GDX_HIP(hipMemcpyAsync(d_in.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_in.get() + m, cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_in.get() + 2 * m, dist, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    if (end) GDX_HIP(hipMemcpyAsync(d_in.get() + 3 * m, end, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
+    uint32_t *o = d_out.get(), *w = o + 6 * n_pairs;
+    launch_pair_hits(n_pairs, mate_slots, d_in.get(), d_in.get() + m, d_hits.get(), d_in.get() + 2 * m,
+                     end ? d_in.get() + 3 * m : nullptr, max_dist, min_insert, max_insert, o, o + n_pairs, o + 2 * n_pairs,
+                     o + 3 * n_pairs, o + 4 * n_pairs, o + 5 * n_pairs, w, w + n_mates, w + 2 * n_mates, w + 3 * n_mates, d_win.get(),
+                     stream);
+    GDX_HIP(hipGetLastError());
+    std::vector<gdx_hit32_t> win(n_mates);
+    uint32_t *per_pair[6] = {out_n_proper, out_n_best, out_pair_dist, out_sub_dist, out_mapq, out_pair_span};
+    uint32_t *per_mate[4] = {out_mate_slot, out_mate_dist, out_win_query, out_win_begin};
+    for (int x = 0; x < 6; x++)
+        GDX_HIP(hipMemcpyAsync(per_pair[x], o + x * n_pairs, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    for (int x = 0; x < 4; x++)
+        GDX_HIP(hipMemcpyAsync(per_mate[x], w + x * n_mates, n_mates * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipMemcpyAsync(win.data(), d_win.get(), n_mates * sizeof(gdx_hit32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipStreamSynchronize(stream));
+    for (uint64_t g = 0; g < n_mates; g++) {
+        out_win_hits[g].text_id = win[g].text_id;
+        out_win_hits[g].position = win[g].position;
+    }
+    return GDX_OK;
+}
+
 int FmIndex::rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const
 {
     if (m == 0) return GDX_OK;

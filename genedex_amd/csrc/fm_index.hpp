@@ -174,6 +174,14 @@ public:
                        uint32_t *out_win_query, uint32_t *out_win_begin, gdx_hit_t *out_win_hits) const;
     // what both forms of gdx_best_hits_many refuse before they look at the batch
     void check_best_hits(uint64_t n_groups, uint32_t group_slots, uint32_t max_dist) const;
+    // gdx_pair_hits_many: staged like best_hits_many; cand_hits narrowed to 32 bits, win_hits widened; end may be null
+    int pair_hits_many(uint64_t n_pairs, uint32_t mate_slots, const uint32_t *cand_query, const uint32_t *cand_begin,
+                       const gdx_hit_t *cand_hits, const uint32_t *dist, const uint32_t *end, uint32_t max_dist, uint32_t min_insert,
+                       uint32_t max_insert, uint32_t *out_n_proper, uint32_t *out_n_best, uint32_t *out_pair_dist,
+                       uint32_t *out_sub_dist, uint32_t *out_mapq, uint32_t *out_pair_span, uint32_t *out_mate_slot,
+                       uint32_t *out_mate_dist, uint32_t *out_win_query, uint32_t *out_win_begin, gdx_hit_t *out_win_hits) const;
+    // what both forms of gdx_pair_hits_many refuse before they look at the batch
+    void check_pair_hits(uint64_t n_pairs, uint32_t mate_slots, uint32_t max_dist, uint32_t min_insert, uint32_t max_insert) const;
     int rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const;
     int symbol_at_many(const uint64_t *idx, uint64_t m, uint8_t *out) const;
 

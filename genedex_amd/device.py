@@ -611,6 +611,70 @@ class DeviceEngine:
                 "dist": best["best_dist"], "sub_dist": best["sub_dist"], "n_best": best["n_best"], "mapq": best["mapq"],
                 "n_cigar": aligned["n_cigar"], "cigar": aligned["cigar"]}
 
+    # ---- paired-end pairing (gdx_pair_hits_many_dev) -----------------------------------------------------------
+    def alloc_pair_hits(self, n_pairs: int):
+        d = self.dev
+        n = max(n_pairs, 1)
+        out = {name: torch.empty(n, dtype=torch.int32, device=d)
+               for name in ("n_proper", "n_best", "pair_dist", "sub_dist", "mapq", "pair_span")}
+        out.update({name: torch.empty(2 * n, dtype=torch.int32, device=d) for name in ("mate_slot", "mate_dist", "win_query", "win_begin")})
+        out["win_hits"] = torch.empty((2 * n, 2), dtype=torch.int32, device=d)
+        return out
+
+    def pair_hits(self, cands: dict, dist: torch.Tensor, end, n_pairs: int, mate_slots: int, max_dist: int, min_insert: int,
+                  max_insert: int, out: dict = None):
+        """One launch: the slots are 2 * n_pairs mates of mate_slots consecutive candidate slots, mates 2p and 2p + 1 making pair
+        p; per pair the best combination of one live slot of each mate on one text, on opposite strands and with min_insert <=
+        span <= max_insert, in `out` (alloc_pair_hits; made here when None) -> out.  cands, dist, end as best_hits() takes them;
+        after with_strands(mode="both") on a batch with the mates interleaved mate_slots = 2 * max_candidates.  Per pair
+        "n_proper", "n_best", "pair_dist", "sub_dist", "mapq" (255, GDX_PAIR_MAPQ_NONE, without a proper combination) and
+        "pair_span"; per mate "mate_slot" (-1, GDX_PAIR_NONE, without a live slot), "mate_dist" and the winner "win_query",
+        "win_begin", "win_hits" -- the pair's slot, or the mate's single-end best when the pair has no proper combination --
+        which go straight into align() as 2 * n_pairs candidates."""
+        m = _check_candidates(cands["cand_query"], cands["cand_begin"], cands["cand_hits"])
+        n_pairs, mate_slots = int(n_pairs), int(mate_slots)
+        slots = 2 * n_pairs * mate_slots
+        if slots > m or dist.numel() < slots or (end is not None and end.numel() < slots):
+            raise ValueError("candidates, dist and end hold 2 * n_pairs * mate_slots slots")
+        if out is None:
+            out = self.alloc_pair_hits(n_pairs)
+        _lib.check(self.lib.gdx_pair_hits_many_dev(
+            self.h, n_pairs, mate_slots, _ptr(cands["cand_query"]), _ptr(cands["cand_begin"]), _ptr(cands["cand_hits"]), _ptr(dist),
+            _ptr(end) if end is not None else None, int(max_dist), int(min_insert), int(max_insert), _ptr(out["n_proper"]),
+            _ptr(out["n_best"]), _ptr(out["pair_dist"]), _ptr(out["sub_dist"]), _ptr(out["mapq"]), _ptr(out["pair_span"]),
+            _ptr(out["mate_slot"]), _ptr(out["mate_dist"]), _ptr(out["win_query"]), _ptr(out["win_begin"]), _ptr(out["win_hits"]),
+            _stream()))
+        return out
+
+    def map_pairs(self, q: DeviceQueries, reversed_index, *, max_smems: int, min_length: int, max_occ: int, band: int,
+                  max_candidates: int, max_edits: int, min_insert: int, max_insert: int) -> dict:
+        """map_reads for paired reads.  q: a plain batch with the mates interleaved, reads 2p and 2p + 1 being the mates of pair p
+        (an odd q.nq raises ValueError).  with_strands("both") -> smems -> seed_candidates -> edit_distance -> pair_hits ->
+        best_hits per mate (for the single-end figures) -> align over the 2 * n_pairs winners of pair_hits.
+        -> per-mate tensors (u32 values in int32, index 2p + s): "strand", "text_id", "begin", "end", "dist" (the winner's),
+        "n_cigar", "cigar" (int32[mates, 2 max_edits + 1]) and the single-end "mapq", "n_best", "sub_dist" of map_reads;
+        per-pair tensors: "n_proper", "pair_n_best", "pair_dist", "pair_sub_dist", "pair_mapq" (255 without a proper
+        combination), "pair_span".  A mate of a pair without a proper combination is placed as map_reads places it; an unmapped
+        mate has n_cigar 0, begin and end -1 and dist max_edits + 1.  No result crosses to the host in between."""
+        if q.nq % 2:
+            raise ValueError("map_pairs takes the mates interleaved: an even number of reads")
+        n_mates, n_pairs, mc = q.nq, q.nq // 2, int(max_candidates)
+        sq = q.with_strands(self.index, "both")
+        seeds = self.alloc_smems(sq.nq, int(max_smems))
+        self.smems(sq, reversed_index, int(max_smems), int(min_length), seeds)
+        cands = self.seed_candidates(seeds, sq.nq, int(max_smems), max_occ, band, mc)
+        dist, end = self.edit_distance(sq, cands["cand_query"], cands["cand_begin"], cands["cand_hits"], max_edits)
+        pairs = self.pair_hits(cands, dist, end, n_pairs, 2 * mc, max_edits, min_insert, max_insert)
+        single = self.best_hits(cands, dist, end, n_mates, 2 * mc, max_edits)
+        aligned = self.align(sq, pairs["win_query"][:n_mates], pairs["win_begin"][:n_mates], pairs["win_hits"][:n_mates], max_edits)
+        per_mate = {"strand": pairs["win_query"] & 1, "text_id": pairs["win_hits"][:, 0], "begin": aligned["begin"],
+                    "end": aligned["end"], "dist": pairs["mate_dist"], "n_cigar": aligned["n_cigar"], "cigar": aligned["cigar"],
+                    "mapq": single["mapq"], "n_best": single["n_best"], "sub_dist": single["sub_dist"]}
+        per_pair = {"n_proper": pairs["n_proper"], "pair_n_best": pairs["n_best"], "pair_dist": pairs["pair_dist"],
+                    "pair_sub_dist": pairs["sub_dist"], "pair_mapq": pairs["mapq"], "pair_span": pairs["pair_span"]}
+        # (the buffers hold at least one entry: an empty batch gets empty tensors, not that unwritten row)
+        return {**{name: t[:n_mates] for name, t in per_mate.items()}, **{name: t[:n_pairs] for name, t in per_pair.items()}}
+
     def search_step_stats(self, q: DeviceQueries):
         """(LF steps, line fetches of all queries, fetch slots their wavefronts spent)"""
         steps = torch.zeros(3, dtype=torch.int64, device=self.dev)

@@ -608,6 +608,32 @@ class FmIndex:
                                                 *(_p(o, u32p) for o in outs), win.ctypes.data_as(C.POINTER(_lib.HitStruct))))
         return tuple(o[:ng] for o in outs) + (win[:ng, 0], win[:ng, 1])
 
+    # ---- paired-end pairing (gdx_experimental.h "paired-end pairing") -----------------------------------------
+    def pair_hits_raw(self, cand_query, cand_begin, text_ids, positions, dist, end, n_pairs, mate_slots, max_dist, min_insert,
+                      max_insert):
+        """gdx_pair_hits_many -> (n_proper, n_best, pair_dist, sub_dist, mapq, pair_span: u32[n_pairs]; mate_slot, mate_dist,
+        win_query, win_begin: u32[2 n_pairs]; win_text_ids, win_positions: u64[2 n_pairs]): the slots are 2 * n_pairs mates of
+        mate_slots consecutive candidate slots (mates 2p and 2p + 1 make pair p) with the distances a verify call gave them;
+        per pair the best combination of one slot of each mate that lies on one text, on opposite strands and min_insert ..
+        max_insert apart, per mate the winner (its single-end best without such a combination).  `end` as in best_hits_raw."""
+        n, ms = int(n_pairs), int(mate_slots)
+        m = 2 * n * ms
+        cq, cb, dist = (np.ascontiguousarray(x, dtype=np.uint32) for x in (cand_query, cand_begin, dist))
+        end = None if end is None else np.ascontiguousarray(end, dtype=np.uint32)
+        hits = np.ascontiguousarray(np.stack([np.asarray(text_ids, dtype=np.uint64), np.asarray(positions, dtype=np.uint64)], axis=1))
+        for x in (cq, cb, dist, end, hits[:, 0]):
+            if x is not None and x.size != m:
+                raise ValueError("slot arrays hold 2 * n_pairs * mate_slots slots")
+        pairs = [np.zeros(max(n, 1), dtype=np.uint32) for _ in range(6)]
+        mates = [np.zeros(max(2 * n, 1), dtype=np.uint32) for _ in range(4)]
+        win = np.zeros((max(2 * n, 1), 2), dtype=np.uint64)
+        _lib.check(self._lib.gdx_pair_hits_many(self._h, n, ms, _p(cq, u32p), _p(cb, u32p),
+                                                hits.ctypes.data_as(C.POINTER(_lib.HitStruct)), _p(dist, u32p),
+                                                _p(end, u32p) if end is not None else None, int(max_dist), int(min_insert),
+                                                int(max_insert), *(_p(o, u32p) for o in pairs + mates),
+                                                win.ctypes.data_as(C.POINTER(_lib.HitStruct))))
+        return tuple(o[:n] for o in pairs) + tuple(o[:2 * n] for o in mates) + (win[:2 * n, 0], win[:2 * n, 1])
+
     def rank_many(self, symbols, idx):
         """TextWithRankSupport::rank (text_with_rank_support/mod.rs:106-110), batched."""
         sym = np.ascontiguousarray(symbols, dtype=np.uint8)

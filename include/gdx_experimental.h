@@ -3,9 +3,9 @@
  * replaced, hint arrays, compact-result plumbing of the multi-GPU gather) and building blocks the tests and bench.py still
  * drive one by one.  Exported and tested like the core (tests/test_abi.py, tests/test_gpu_*.py), but not what a binding of the
  * reference's API needs (INTEGRATION.md binds gdx.h only), and free to change.  Every call returns the results of the core call
- * it is a part of: lib.rs:155-246 of the reference.  The last two sections, "seed-hit candidates" and "best hit per read", are
- * calls of the seed-and-verify chain that the reference has no counterpart of; they are declared here because the core header
- * keeps to its budget of names (tests/test_abi.py). */
+ * it is a part of: lib.rs:155-246 of the reference.  The last three sections, "seed-hit candidates", "best hit per read" and
+ * "paired-end pairing", are calls of the seed-and-verify chain that the reference has no counterpart of; they are declared here
+ * because the core header keeps to its budget of names (tests/test_abi.py). */
 #ifndef GDX_EXPERIMENTAL_H
 #define GDX_EXPERIMENTAL_H
 
@@ -280,7 +280,8 @@ int gdx_seed_candidates_many(const gdx_index_t *ix, uint64_t nq, uint32_t max_se
  * GDX_ERR_INVALID_ARGUMENT: group_slots == 0 or > GDX_BEST_MAX_GROUP_SLOTS; max_dist > 2^31; n_groups * group_slots does not fit
  * 64 bits; a null required pointer (only d_end / end may be null).  GDX_ERR_UNSUPPORTED: a handle of the 64-bit engine.
  * n_groups == 0 is GDX_OK and writes nothing.  A refused call writes nothing.  gdx_parts_t and gdx_multi_t have no such call.
- * Out of scope: secondary alignments beyond the counts, paired-end pairing, a compacted list of the mapped reads only. */
+ * Out of scope: secondary alignments beyond the counts, a compacted list of the mapped reads only.  Paired-end pairing is
+ * gdx_pair_hits_many below. */
 #define GDX_BEST_NONE            0xFFFFFFFFu  /* best_slot of a group without a live slot       */
 #define GDX_BEST_MAPQ_NONE       255u         /* mapq of such a group (SAM: not available)      */
 #define GDX_BEST_MAX_GROUP_SLOTS 64u          /* the most slots of one group                    */
@@ -295,6 +296,65 @@ int gdx_best_hits_many(const gdx_index_t *ix, uint64_t n_groups, uint32_t group_
                        uint32_t max_dist, uint32_t *out_best_slot, uint32_t *out_best_dist, uint32_t *out_sub_dist,
                        uint32_t *out_n_live, uint32_t *out_n_best, uint32_t *out_mapq, uint32_t *out_win_query,
                        uint32_t *out_win_begin, gdx_hit_t *out_win_hits);
+
+/* ---- paired-end pairing (the reduction beside gdx_best_hits_many for reads that come in pairs) ---------------------------
+ * gdx_best_hits_many treats every read as single-end.  gdx_pair_hits_many picks, per read PAIR, the best properly oriented,
+ * properly spaced combination of one verified slot of each mate, says whether that combination is unique, and writes the two
+ * winners as a candidate list for the traceback: the mate decides a read that falls into a repeat.
+ * Inputs: m = 2 * n_pairs * mate_slots slots, slot j of mate s (0 or 1) of pair p being (2p + s) * mate_slots + j, with
+ * cand_query, cand_begin, cand_hits, dist and end (or NULL) per slot exactly as gdx_best_hits_many takes them.  The intended
+ * producer is a batch with the mates interleaved (reads 2p and 2p + 1 are the mates of pair p) behind gdx_strands_expand_dev with
+ * GDX_STRANDS_BOTH: queries 4p .. 4p + 3 are mate 0 forward, mate 0 reverse complement, mate 1 forward, mate 1 reverse
+ * complement, and mate_slots = 2 * max_candidates.  The call never looks at the queries or at the index's arrays.
+ * Knobs: max_dist = k; min_insert <= max_insert <= 2^31 - 1.
+ * Per slot: strand = cand_query & 1 (the GDX_STRANDS_BOTH numbering); diag = (int64) position - (int64) cand_begin, not wrapped,
+ * possibly negative; right = end[slot] when end is given, otherwise diag.
+ * Per pair p:
+ *  1. Live.  Step 1 of gdx_best_hits_many: cand_query != GDX_CAND_NONE and dist <= k.
+ *  2. Same locus, per mate.  Step 2 of gdx_best_hits_many over the mate_slots slots of each mate separately: the key is
+ *     (cand_query, text_id, e), e = end or the wrapping 32-bit diagonal when end is NULL; only the least (dist, j) of a key stays.
+ *  3. Proper combinations.  A combination is (i, j), i a live slot of mate 0 and j a live slot of mate 1.  It is proper when the
+ *     text_id of both is equal, their strands differ and, with f the strand-0 slot of the two and r the strand-1 slot, span =
+ *     right_r - diag_f (signed 64 bits) has min_insert <= span <= max_insert: the forward/reverse library orientation.  Its score
+ *     is dist_i + dist_j.  With end NULL the span is the distance between the two diagonals: the caller widens the bounds by the
+ *     read length.
+ *  4. Pair results, over the proper combinations.  n_proper = their number.  The best one is the least (score, i, j): pair_dist =
+ *     its score, pair_span = its span as u32.  n_best = the combinations with score == pair_dist.  sub_dist = the least score of
+ *     the other combinations: pair_dist when n_best >= 2, 2k + 2 when there is no other.  mapq = min(60, 60 * (sub_dist -
+ *     pair_dist) / (2k + 2)), in 64 bits with integer division.  A pair without a proper combination gets n_proper = n_best = 0,
+ *     pair_dist = sub_dist = 2k + 2, pair_span = 0 and mapq = GDX_PAIR_MAPQ_NONE.
+ *  5. Winners, per mate, at index 2p + s of arrays of 2 * n_pairs entries.  With n_proper > 0 slot i is the winner of mate 0 and
+ *     slot j that of mate 1.  Otherwise each mate's winner is its single-end best, the least (dist, j) of its slots live after
+ *     step 2: what gdx_best_hits_many gives with n_groups = 2 * n_pairs and group_slots = mate_slots.  mate_slot = the winner's
+ *     slot (GDX_PAIR_NONE without a live slot), mate_dist = its distance (k + 1 without one), win_query, win_begin, win_hits = its
+ *     candidate (GDX_CAND_NONE, 0, {0, 0} without one).  The three winner arrays go straight into gdx_align_many_dev with m =
+ *     2 * n_pairs.
+ * Device form: ONE launch, no synchronisation, no allocation, no copy from pageable memory; returns GDX_OK.  Six outputs are
+ * u32[n_pairs], four u32[2 n_pairs], d_win_hits gdx_hit32_t[2 n_pairs]; none may overlap an input.  Host form: the same arguments
+ * without the stream; cand_hits and win_hits are gdx_hit_t (a text id or a position of 2^32 or more: GDX_ERR_INVALID_ARGUMENT);
+ * staged like gdx_best_hits_many.
+ * GDX_ERR_INVALID_ARGUMENT: mate_slots == 0 or > GDX_PAIR_MAX_MATE_SLOTS; max_dist > 2^30 (2k + 2 fits u32); min_insert >
+ * max_insert or max_insert > 2^31 - 1; 2 * n_pairs * mate_slots does not fit 64 bits; a null required pointer (only d_end / end
+ * may be null).  GDX_ERR_UNSUPPORTED: a handle of the 64-bit engine.  n_pairs == 0 is GDX_OK and writes nothing.  A refused call
+ * writes nothing.  gdx_parts_t and gdx_multi_t have no such call.
+ * Out of scope: mate rescue (aligning the missing mate in the window the found one implies), other library orientations, an
+ * insert-size model beyond the two bounds, preferring among equal scores by span. */
+#define GDX_PAIR_NONE           0xFFFFFFFFu  /* mate_slot of a mate without a live slot        */
+#define GDX_PAIR_MAPQ_NONE      255u         /* mapq of a pair without a proper combination    */
+#define GDX_PAIR_MAX_MATE_SLOTS 32u          /* the most slots of one mate                     */
+int gdx_pair_hits_many_dev(const gdx_index_t *ix, uint64_t n_pairs, uint32_t mate_slots, const void *d_cand_query /*u32[m]*/,
+                           const void *d_cand_begin /*u32[m]*/, const void *d_cand_hits /*gdx_hit32_t[m]*/,
+                           const void *d_dist /*u32[m]*/, const void *d_end /*u32[m] or NULL*/, uint32_t max_dist,
+                           uint32_t min_insert, uint32_t max_insert, void *d_n_proper, void *d_n_best, void *d_pair_dist,
+                           void *d_sub_dist, void *d_mapq, void *d_pair_span /*u32[n_pairs] each*/, void *d_mate_slot,
+                           void *d_mate_dist, void *d_win_query, void *d_win_begin /*u32[2 n_pairs] each*/,
+                           void *d_win_hits /*gdx_hit32_t[2 n_pairs]*/, void *stream);
+int gdx_pair_hits_many(const gdx_index_t *ix, uint64_t n_pairs, uint32_t mate_slots, const uint32_t *cand_query,
+                       const uint32_t *cand_begin, const gdx_hit_t *cand_hits, const uint32_t *dist, const uint32_t *end /*or NULL*/,
+                       uint32_t max_dist, uint32_t min_insert, uint32_t max_insert, uint32_t *out_n_proper, uint32_t *out_n_best,
+                       uint32_t *out_pair_dist, uint32_t *out_sub_dist, uint32_t *out_mapq, uint32_t *out_pair_span,
+                       uint32_t *out_mate_slot, uint32_t *out_mate_dist, uint32_t *out_win_query, uint32_t *out_win_begin,
+                       gdx_hit_t *out_win_hits);
 
 #ifdef __cplusplus
 }
