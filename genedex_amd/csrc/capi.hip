@@ -15,6 +15,7 @@
 #include "fastx.hpp"
 #include "fm_index.hpp"
 #include "kernels.hpp"
+#include "select.hpp"
 #include "synth.hpp"
 
 namespace gdx {
@@ -1742,6 +1743,9 @@ int gdx_locate_many_alloc_strands(const gdx_index_t *ix, const uint8_t *qbuf, co
 
 // ---- Hamming verification of located seeds (hamming.hip) --------------------------------------------------------
 
+static uint32_t *u32(void *p) { return static_cast<uint32_t *>(p); }
+static const uint32_t *u32(const void *p) { return static_cast<const uint32_t *>(p); }
+
 // what the three verify _dev entries refuse once m != 0: a null candidate array, a null d_out (the output the entry has not
 // looked at itself) and a null d_qbuf of a batch with queries
 static void check_verify_pointers(const void *d_qbuf, uint64_t nq, const void *d_cand_query, const void *d_cand_begin,
@@ -1763,9 +1767,8 @@ int gdx_hamming_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *
         if (m == 0) return (int)GDX_OK;
         check_verify_pointers(d_qbuf, nq, d_cand_query, d_cand_begin, d_cand_hits, d_out);
         DeviceGuard guard(f.config().device_id);
-        gdx::launch_hamming(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, static_cast<const uint32_t *>(d_cand_query),
-                            static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits), m,
-                            max_mismatches, static_cast<uint32_t *>(d_out), as_stream(stream));
+        gdx::launch_hamming(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, u32(d_cand_query), u32(d_cand_begin),
+                            static_cast<const gdx_hit32_t *>(d_cand_hits), m, max_mismatches, u32(d_out), as_stream(stream));
         GDX_HIP(hipGetLastError());
         return (int)GDX_OK;
     });
@@ -1791,9 +1794,9 @@ int gdx_edit_distance_many_dev(const gdx_index_t *ix, const void *d_qbuf, const 
         if (m == 0) return (int)GDX_OK;
         check_verify_pointers(d_qbuf, nq, d_cand_query, d_cand_begin, d_cand_hits, d_out_dist);
         DeviceGuard guard(f.config().device_id);
-        gdx::launch_edit_distance(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, static_cast<const uint32_t *>(d_cand_query),
-                                  static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits), m,
-                                  max_edits, static_cast<uint32_t *>(d_out_dist), static_cast<uint32_t *>(d_out_end), as_stream(stream));
+        gdx::launch_edit_distance(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, u32(d_cand_query), u32(d_cand_begin),
+                                  static_cast<const gdx_hit32_t *>(d_cand_hits), m, max_edits, u32(d_out_dist), u32(d_out_end),
+                                  as_stream(stream));
         GDX_HIP(hipGetLastError());
         return (int)GDX_OK;
     });
@@ -1836,11 +1839,9 @@ int gdx_align_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_
         if (m == 0) return (int)GDX_OK;
         check_verify_pointers(d_qbuf, nq, d_cand_query, d_cand_begin, d_cand_hits, d_out_dist);  // (the outputs: checked above)
         DeviceGuard guard(f.config().device_id);
-        gdx::launch_align(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, static_cast<const uint32_t *>(d_cand_query),
-                          static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits), m, max_edits,
-                          static_cast<uint32_t *>(d_out_dist), static_cast<uint32_t *>(d_out_begin), static_cast<uint32_t *>(d_out_end),
-                          static_cast<uint32_t *>(d_out_n_cigar), static_cast<uint32_t *>(d_out_cigar), d_workspace, workspace_bytes,
-                          as_stream(stream));
+        gdx::launch_align(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, u32(d_cand_query), u32(d_cand_begin),
+                          static_cast<const gdx_hit32_t *>(d_cand_hits), m, max_edits, u32(d_out_dist), u32(d_out_begin), u32(d_out_end),
+                          u32(d_out_n_cigar), u32(d_out_cigar), d_workspace, workspace_bytes, as_stream(stream));
         GDX_HIP(hipGetLastError());
         return (int)GDX_OK;
     });
@@ -1869,17 +1870,14 @@ int gdx_seed_candidates_many_dev(const gdx_index_t *ix, uint64_t nq, uint32_t ma
         f.check_seed_candidates(max_seeds, max_occ, max_candidates);
         if (nq == 0) return (int)GDX_OK;
         if (nq >= 0xffffffffull) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "more than 2^32 - 2 queries (cand_query is 32 bits wide)");
-        if (!d_n_seeds || !d_begin || !d_length || !d_start || !d_end || !d_n_candidates || !d_n_groups || !d_n_skipped ||
-            !d_cand_query || !d_cand_begin || !d_cand_hits || !d_cand_weight)
+        if (gdx::any_null({d_n_seeds, d_begin, d_length, d_start, d_end, d_n_candidates, d_n_groups, d_n_skipped, d_cand_query, d_cand_begin,
+                      d_cand_hits, d_cand_weight}))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
         DeviceGuard guard(f.config().device_id);
-        gdx::launch_seed_candidates(f.view(), nq, max_seeds, static_cast<const uint32_t *>(d_n_seeds),
-                                    static_cast<const uint32_t *>(d_begin), static_cast<const uint32_t *>(d_length),
-                                    static_cast<const uint32_t *>(d_start), static_cast<const uint32_t *>(d_end), max_occ, band,
-                                    max_candidates, static_cast<uint32_t *>(d_n_candidates), static_cast<uint32_t *>(d_n_groups),
-                                    static_cast<uint32_t *>(d_n_skipped), static_cast<uint32_t *>(d_cand_query),
-                                    static_cast<uint32_t *>(d_cand_begin), static_cast<gdx_hit32_t *>(d_cand_hits),
-                                    static_cast<uint32_t *>(d_cand_weight), static_cast<uint8_t *>(d_status), as_stream(stream));
+        gdx::launch_seed_candidates(f.view(), nq, max_seeds, u32(d_n_seeds), u32(d_begin), u32(d_length), u32(d_start), u32(d_end),
+                                    max_occ, band, max_candidates, u32(d_n_candidates), u32(d_n_groups), u32(d_n_skipped),
+                                    u32(d_cand_query), u32(d_cand_begin), static_cast<gdx_hit32_t *>(d_cand_hits), u32(d_cand_weight),
+                                    static_cast<uint8_t *>(d_status), as_stream(stream));
         GDX_HIP(hipGetLastError());
         return (int)GDX_OK;
     });
@@ -1900,6 +1898,14 @@ int gdx_seed_candidates_many(const gdx_index_t *ix, uint64_t nq, uint32_t max_se
 
 // ---- best hit per read (best_hits.hip) ---------------------------------------------------------------------------
 
+// what the two selection _dev entries have in common (select.hpp): the candidate slots, their distances, the winner triple
+static gdx::SlotArgs slot_args(const void *d_cand_query, const void *d_cand_begin, const void *d_cand_hits, const void *d_dist,
+                               const void *d_end, uint32_t max_dist, void *d_win_query, void *d_win_begin, void *d_win_hits)
+{
+    return {u32(d_cand_query), u32(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits), u32(d_dist), u32(d_end), max_dist,
+            u32(d_win_query), u32(d_win_begin), static_cast<gdx_hit32_t *>(d_win_hits)};
+}
+
 int gdx_best_hits_many_dev(const gdx_index_t *ix, uint64_t n_groups, uint32_t group_slots, const void *d_cand_query,
                            const void *d_cand_begin, const void *d_cand_hits, const void *d_dist, const void *d_end, uint32_t max_dist,
                            void *d_best_slot, void *d_best_dist, void *d_sub_dist, void *d_n_live, void *d_n_best, void *d_mapq,
@@ -1909,17 +1915,14 @@ int gdx_best_hits_many_dev(const gdx_index_t *ix, uint64_t n_groups, uint32_t gr
         const gdx::FmIndex &f = deref(ix);
         f.check_best_hits(n_groups, group_slots, max_dist);
         if (n_groups == 0) return (int)GDX_OK;
-        if (!d_cand_query || !d_cand_begin || !d_cand_hits || !d_dist || !d_best_slot || !d_best_dist || !d_sub_dist || !d_n_live ||
-            !d_n_best || !d_mapq || !d_win_query || !d_win_begin || !d_win_hits)
+        if (gdx::any_null({d_cand_query, d_cand_begin, d_cand_hits, d_dist, d_best_slot, d_best_dist, d_sub_dist, d_n_live, d_n_best, d_mapq,
+                      d_win_query, d_win_begin, d_win_hits}))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
         DeviceGuard guard(f.config().device_id);
-        gdx::launch_best_hits(n_groups, group_slots, static_cast<const uint32_t *>(d_cand_query),
-                              static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits),
-                              static_cast<const uint32_t *>(d_dist), static_cast<const uint32_t *>(d_end), max_dist,
-                              static_cast<uint32_t *>(d_best_slot), static_cast<uint32_t *>(d_best_dist),
-                              static_cast<uint32_t *>(d_sub_dist), static_cast<uint32_t *>(d_n_live), static_cast<uint32_t *>(d_n_best),
-                              static_cast<uint32_t *>(d_mapq), static_cast<uint32_t *>(d_win_query),
-                              static_cast<uint32_t *>(d_win_begin), static_cast<gdx_hit32_t *>(d_win_hits), as_stream(stream));
+        const gdx::BestArgs a = {
+            slot_args(d_cand_query, d_cand_begin, d_cand_hits, d_dist, d_end, max_dist, d_win_query, d_win_begin, d_win_hits), n_groups,
+            group_slots, u32(d_best_slot), u32(d_best_dist), u32(d_sub_dist), u32(d_n_live), u32(d_n_best), u32(d_mapq)};
+        gdx::launch_best_hits(a, as_stream(stream));
         GDX_HIP(hipGetLastError());
         return (int)GDX_OK;
     });
@@ -1950,18 +1953,15 @@ int gdx_pair_hits_many_dev(const gdx_index_t *ix, uint64_t n_pairs, uint32_t mat
         const gdx::FmIndex &f = deref(ix);
         f.check_pair_hits(n_pairs, mate_slots, max_dist, min_insert, max_insert);
         if (n_pairs == 0) return (int)GDX_OK;
-        if (!d_cand_query || !d_cand_begin || !d_cand_hits || !d_dist || !d_n_proper || !d_n_best || !d_pair_dist || !d_sub_dist ||
-            !d_mapq || !d_pair_span || !d_mate_slot || !d_mate_dist || !d_win_query || !d_win_begin || !d_win_hits)
+        if (gdx::any_null({d_cand_query, d_cand_begin, d_cand_hits, d_dist, d_n_proper, d_n_best, d_pair_dist, d_sub_dist, d_mapq, d_pair_span,
+                      d_mate_slot, d_mate_dist, d_win_query, d_win_begin, d_win_hits}))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
         DeviceGuard guard(f.config().device_id);
-        gdx::launch_pair_hits(n_pairs, mate_slots, static_cast<const uint32_t *>(d_cand_query),
-                              static_cast<const uint32_t *>(d_cand_begin), static_cast<const gdx_hit32_t *>(d_cand_hits),
-                              static_cast<const uint32_t *>(d_dist), static_cast<const uint32_t *>(d_end), max_dist, min_insert,
-                              max_insert, static_cast<uint32_t *>(d_n_proper), static_cast<uint32_t *>(d_n_best),
-                              static_cast<uint32_t *>(d_pair_dist), static_cast<uint32_t *>(d_sub_dist), static_cast<uint32_t *>(d_mapq),
-                              static_cast<uint32_t *>(d_pair_span), static_cast<uint32_t *>(d_mate_slot),
-                              static_cast<uint32_t *>(d_mate_dist), static_cast<uint32_t *>(d_win_query),
-                              static_cast<uint32_t *>(d_win_begin), static_cast<gdx_hit32_t *>(d_win_hits), as_stream(stream));
+        const gdx::PairArgs a = {
+            slot_args(d_cand_query, d_cand_begin, d_cand_hits, d_dist, d_end, max_dist, d_win_query, d_win_begin, d_win_hits), n_pairs,
+            mate_slots, min_insert, max_insert, u32(d_n_proper), u32(d_n_best), u32(d_pair_dist), u32(d_sub_dist), u32(d_mapq),
+            u32(d_pair_span), u32(d_mate_slot), u32(d_mate_dist)};
+        gdx::launch_pair_hits(a, as_stream(stream));
         GDX_HIP(hipGetLastError());
         return (int)GDX_OK;
     });

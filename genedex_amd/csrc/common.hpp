@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/gdx.h"
@@ -62,6 +63,14 @@ struct DeviceBuffer {
 };
 
 inline uint64_t div_ceil(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
+
+// the required pointers of a call: is one of them null?
+inline bool any_null(std::initializer_list<const void *> pointers)
+{
+    for (const void *p : pointers)
+        if (!p) return true;
+    return false;
+}
 
 // Grow-only scratch memory for the `_dev` entry points, one arena per (calling thread, stream, slot).
 // Work on one stream is ordered, so a later call may reuse the bytes of an earlier one without waiting;

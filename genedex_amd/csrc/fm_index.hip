@@ -14,6 +14,7 @@
 
 #include "index_file.hpp"
 #include "kernels.hpp"
+#include "select.hpp"
 
 namespace gdx {
 
@@ -1995,6 +1996,18 @@ void check_query_lengths(const uint64_t *qoff, uint64_t nq)
             fail(GDX_ERR_INVALID_ARGUMENT, "query %llu is longer than 2^32 - 1 symbols", (unsigned long long)i);
 }
 
+// m hits narrowed to 32 bits; check(i) refuses, before hit i is narrowed, what the call does not take
+template <class Check>
+std::vector<gdx_hit32_t> narrow_hits(const gdx_hit_t *hits, uint64_t m, Check &&check)
+{
+    std::vector<gdx_hit32_t> narrow(m);
+    for (uint64_t i = 0; i < m; i++) {
+        check(i);
+        narrow[i] = {static_cast<uint32_t>(hits[i].text_id), static_cast<uint32_t>(hits[i].position)};
+    }
+    return narrow;
+}
+
 // the m candidates of a verify call (hamming_many, edit_distance_many, align_many) on the index's device: checked against the
 // batch and the index, the hits narrowed to 32 bits, uploaded on `stream` of the current device
 struct DeviceCandidates {
@@ -2003,27 +2016,56 @@ struct DeviceCandidates {
     std::vector<gdx_hit32_t> narrow;  // the source of an asynchronous copy: lives until the call has synchronised
     DeviceCandidates(uint64_t n_texts, uint64_t nq, const uint32_t *cand_query, const uint32_t *cand_begin, const gdx_hit_t *cand_hits,
                      uint64_t m, hipStream_t stream)
-        : narrow(m)
+        : narrow(narrow_hits(cand_hits, m, [&](uint64_t c) {
+              if (cand_query[c] >= nq)
+                  fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu belongs to query %u of %llu", (unsigned long long)c, cand_query[c],
+                       (unsigned long long)nq);
+              if (cand_hits[c].text_id >= n_texts)
+                  fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu lies in text %llu of %llu", (unsigned long long)c,
+                       (unsigned long long)cand_hits[c].text_id, (unsigned long long)n_texts);
+              if (cand_hits[c].position > 0xffffffffull)
+                  fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu: position %llu does not fit 32 bits", (unsigned long long)c,
+                       (unsigned long long)cand_hits[c].position);
+          }))
     {
-        for (uint64_t c = 0; c < m; c++) {
-            if (cand_query[c] >= nq)
-                fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu belongs to query %u of %llu", (unsigned long long)c, cand_query[c],
-                     (unsigned long long)nq);
-            if (cand_hits[c].text_id >= n_texts)
-                fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu lies in text %llu of %llu", (unsigned long long)c,
-                     (unsigned long long)cand_hits[c].text_id, (unsigned long long)n_texts);
-            if (cand_hits[c].position > 0xffffffffull)
-                fail(GDX_ERR_INVALID_ARGUMENT, "candidate %llu: position %llu does not fit 32 bits", (unsigned long long)c,
-                     (unsigned long long)cand_hits[c].position);
-            narrow[c].text_id = static_cast<uint32_t>(cand_hits[c].text_id);
-            narrow[c].position = static_cast<uint32_t>(cand_hits[c].position);
-        }
         query.alloc(m);
         begin.alloc(m);
         hits.alloc(m);
         GDX_HIP(hipMemcpyAsync(query.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         GDX_HIP(hipMemcpyAsync(begin.get(), cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         GDX_HIP(hipMemcpyAsync(hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
+    }
+};
+
+// the m slots of best_hits_many / pair_hits_many with their verify results: both words of a hit must fit 32 bits, every cand_query
+// passes (GDX_CAND_NONE marks an unused slot); then the index's device is made current and the slots are uploaded on `stream`
+struct DeviceSlots {
+    std::vector<gdx_hit32_t> narrow;  // (as in DeviceCandidates)
+    DeviceBuffer<uint32_t> in;        // query, begin, dist, end
+    DeviceBuffer<gdx_hit32_t> hits;
+    const bool has_end;
+    DeviceSlots(const FmIndex &ix, const uint32_t *cand_query, const uint32_t *cand_begin, const gdx_hit_t *cand_hits,
+                const uint32_t *dist, const uint32_t *end, uint64_t m, hipStream_t stream)
+        : narrow(narrow_hits(cand_hits, m, [&](uint64_t s) {
+              if (cand_hits[s].position > 0xffffffffull || cand_hits[s].text_id > 0xffffffffull)
+                  fail(GDX_ERR_INVALID_ARGUMENT, "slot %llu: hit (%llu, %llu) does not fit 32 bits", (unsigned long long)s,
+                       (unsigned long long)cand_hits[s].text_id, (unsigned long long)cand_hits[s].position);
+          })), has_end(end != nullptr)
+    {
+        ix.make_current();
+        const uint32_t *columns[4] = {cand_query, cand_begin, dist, end};
+        in.alloc((has_end ? 4 : 3) * m);
+        hits.alloc(m);
+        for (int x = 0; x < (has_end ? 4 : 3); x++)
+            GDX_HIP(hipMemcpyAsync(in.get() + x * m, columns[x], m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        GDX_HIP(hipMemcpyAsync(hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
+    }
+    // the shared part of a stage's argument block: the slots, and the winner triple the caller has made room for
+    SlotArgs args(uint32_t max_dist, uint32_t *win_query, uint32_t *win_begin, gdx_hit32_t *win_hits) const
+    {
+        const uint64_t m = narrow.size();
+        return {in.get(), in.get() + m, hits.get(), in.get() + 2 * m, has_end ? in.get() + 3 * m : nullptr, max_dist, win_query, win_begin,
+                win_hits};
     }
 };
 
@@ -2050,6 +2092,24 @@ void download_widened(const uint32_t *d_in, uint64_t *h_out, uint64_t m, hipStre
     hipLaunchKernelGGL(widen_u32_kernel, dim3(grid_for_items(m)), dim3(kBlock), 0, stream, d_in, wide.get(), m);
     GDX_HIP(hipMemcpyAsync(h_out, wide.get(), m * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     GDX_HIP(hipStreamSynchronize(stream));
+}
+
+// consecutive columns of n words each, from d_in on, into the host arrays `outs` (asynchronous: the caller synchronises)
+void download_columns(std::initializer_list<uint32_t *> outs, const uint32_t *d_in, uint64_t n, hipStream_t stream)
+{
+    for (uint32_t *out : outs) {
+        GDX_HIP(hipMemcpyAsync(out, d_in, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        d_in += n;
+    }
+}
+
+// n narrow hits of the device widened into `out`; the stream has run dry when it returns
+void widen_hits(gdx_hit_t *out, uint64_t n, const gdx_hit32_t *d_hits, hipStream_t stream)
+{
+    std::vector<gdx_hit32_t> hits(n);
+    GDX_HIP(hipMemcpyAsync(hits.data(), d_hits, n * sizeof(gdx_hit32_t), hipMemcpyDeviceToHost, stream));
+    GDX_HIP(hipStreamSynchronize(stream));
+    for (uint64_t i = 0; i < n; i++) out[i] = {hits[i].text_id, hits[i].position};
 }
 
 }  // namespace
@@ -2438,10 +2498,7 @@ int FmIndex::align_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, 
     launch_align(view_, dq.qbuf.get(), dq.qoff.get(), nq, false, 0, dc.query.get(), dc.begin.get(), dc.hits.get(), m, max_edits,
                  d_out.get(), d_out.get() + m, d_out.get() + 2 * m, d_out.get() + 3 * m, d_cigar.get(), d_ws.get(), ws_bytes[1], stream);
     GDX_HIP(hipGetLastError());
-    GDX_HIP(hipMemcpyAsync(out_dist, d_out.get(), m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipMemcpyAsync(out_begin, d_out.get() + m, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipMemcpyAsync(out_end, d_out.get() + 2 * m, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipMemcpyAsync(out_n_cigar, d_out.get() + 3 * m, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    download_columns({out_dist, out_begin, out_end, out_n_cigar}, d_out.get(), m, stream);
     GDX_HIP(hipStreamSynchronize(stream));
     // only the words below n_cigar are the call's: the words behind them stay as the caller left them
     std::vector<uint32_t> cigar(m * stride);
@@ -2472,8 +2529,8 @@ int FmIndex::seed_candidates_many(uint64_t nq, uint32_t max_seeds, const uint32_
     check_seed_candidates(max_seeds, max_occ, max_candidates);
     if (nq == 0) return GDX_OK;
     if (nq >= 0xffffffffull) fail(GDX_ERR_INVALID_ARGUMENT, "more than 2^32 - 2 queries (cand_query is 32 bits wide)");
-    if (!n_seeds || !begin || !length || !start || !end || !out_n_candidates || !out_n_groups || !out_n_skipped || !out_cand_query ||
-        !out_cand_begin || !out_cand_hits || !out_cand_weight)
+    if (any_null({n_seeds, begin, length, start, end, out_n_candidates, out_n_groups, out_n_skipped, out_cand_query, out_cand_begin,
+                  out_cand_hits, out_cand_weight}))
         fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
     const uint64_t slots = nq * max_seeds, outs = nq * max_candidates;
     std::vector<uint32_t> narrow(2 * slots);  // start, end
@@ -2498,21 +2555,11 @@ int FmIndex::seed_candidates_many(uint64_t nq, uint32_t max_seeds, const uint32_
                            max_candidates, d_per.get(), d_per.get() + nq, d_per.get() + 2 * nq, d_out.get(), d_out.get() + outs,
                            d_hits.get(), d_out.get() + 2 * outs, d_status.get(), stream);
     GDX_HIP(hipGetLastError());
-    std::vector<gdx_hit32_t> hits(outs);
     std::vector<uint8_t> st(nq);
-    GDX_HIP(hipMemcpyAsync(out_n_candidates, d_per.get(), nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipMemcpyAsync(out_n_groups, d_per.get() + nq, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipMemcpyAsync(out_n_skipped, d_per.get() + 2 * nq, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipMemcpyAsync(out_cand_query, d_out.get(), outs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipMemcpyAsync(out_cand_begin, d_out.get() + outs, outs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipMemcpyAsync(out_cand_weight, d_out.get() + 2 * outs, outs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipMemcpyAsync(hits.data(), d_hits.get(), outs * sizeof(gdx_hit32_t), hipMemcpyDeviceToHost, stream));
+    download_columns({out_n_candidates, out_n_groups, out_n_skipped}, d_per.get(), nq, stream);
+    download_columns({out_cand_query, out_cand_begin, out_cand_weight}, d_out.get(), outs, stream);
     GDX_HIP(hipMemcpyAsync(st.data(), d_status.get(), nq, hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipStreamSynchronize(stream));
-    for (uint64_t c = 0; c < outs; c++) {
-        out_cand_hits[c].text_id = hits[c].text_id;
-        out_cand_hits[c].position = hits[c].position;
-    }
+    widen_hits(out_cand_hits, outs, d_hits.get(), stream);
     if (out_status) std::memcpy(out_status, st.data(), nq);
     return any_status(st.data(), nq);
 }
@@ -2535,43 +2582,21 @@ int FmIndex::best_hits_many(uint64_t n_groups, uint32_t group_slots, const uint3
 {
     check_best_hits(n_groups, group_slots, max_dist);
     if (n_groups == 0) return GDX_OK;
-    if (!cand_query || !cand_begin || !cand_hits || !dist || !out_best_slot || !out_best_dist || !out_sub_dist || !out_n_live ||
-        !out_n_best || !out_mapq || !out_win_query || !out_win_begin || !out_win_hits)
+    if (any_null({cand_query, cand_begin, cand_hits, dist, out_best_slot, out_best_dist, out_sub_dist, out_n_live, out_n_best, out_mapq,
+                  out_win_query, out_win_begin, out_win_hits}))
         fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-    const uint64_t m = n_groups * group_slots;
-    std::vector<gdx_hit32_t> narrow(m);
-    for (uint64_t s = 0; s < m; s++) {
-        if (cand_hits[s].position > 0xffffffffull || cand_hits[s].text_id > 0xffffffffull)
-            fail(GDX_ERR_INVALID_ARGUMENT, "slot %llu: hit (%llu, %llu) does not fit 32 bits", (unsigned long long)s,
-                 (unsigned long long)cand_hits[s].text_id, (unsigned long long)cand_hits[s].position);
-        narrow[s].text_id = static_cast<uint32_t>(cand_hits[s].text_id);
-        narrow[s].position = static_cast<uint32_t>(cand_hits[s].position);
-    }
-    make_current();
     hipStream_t stream = hipStreamPerThread;
-    DeviceBuffer<uint32_t> d_in((end ? 4 : 3) * m);  // query, begin, dist, end
-    DeviceBuffer<uint32_t> d_out(8 * n_groups);      // the six results, win_query, win_begin
-    DeviceBuffer<gdx_hit32_t> d_hits(m), d_win(n_groups);
-    GDX_HIP(hipMemcpyAsync(d_in.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_in.get() + m, cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_in.get() + 2 * m, dist, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    if (end) GDX_HIP(hipMemcpyAsync(d_in.get() + 3 * m, end, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
+    DeviceSlots slots(*this, cand_query, cand_begin, cand_hits, dist, end, n_groups * group_slots, stream);
+    DeviceBuffer<uint32_t> d_out(8 * n_groups);  // the six results, win_query, win_begin
+    DeviceBuffer<gdx_hit32_t> d_win(n_groups);
     uint32_t *o = d_out.get();
-    launch_best_hits(n_groups, group_slots, d_in.get(), d_in.get() + m, d_hits.get(), d_in.get() + 2 * m,
-                     end ? d_in.get() + 3 * m : nullptr, max_dist, o, o + n_groups, o + 2 * n_groups, o + 3 * n_groups, o + 4 * n_groups,
-                     o + 5 * n_groups, o + 6 * n_groups, o + 7 * n_groups, d_win.get(), stream);
+    const BestArgs a = {slots.args(max_dist, o + 6 * n_groups, o + 7 * n_groups, d_win.get()), n_groups, group_slots, o, o + n_groups,
+                        o + 2 * n_groups, o + 3 * n_groups, o + 4 * n_groups, o + 5 * n_groups};
+    launch_best_hits(a, stream);
     GDX_HIP(hipGetLastError());
-    std::vector<gdx_hit32_t> win(n_groups);
-    uint32_t *outs[8] = {out_best_slot, out_best_dist, out_sub_dist, out_n_live, out_n_best, out_mapq, out_win_query, out_win_begin};
-    for (int x = 0; x < 8; x++)
-        GDX_HIP(hipMemcpyAsync(outs[x], o + x * n_groups, n_groups * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipMemcpyAsync(win.data(), d_win.get(), n_groups * sizeof(gdx_hit32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipStreamSynchronize(stream));
-    for (uint64_t g = 0; g < n_groups; g++) {
-        out_win_hits[g].text_id = win[g].text_id;
-        out_win_hits[g].position = win[g].position;
-    }
+    download_columns({out_best_slot, out_best_dist, out_sub_dist, out_n_live, out_n_best, out_mapq, out_win_query, out_win_begin}, o,
+                     n_groups, stream);
+    widen_hits(out_win_hits, n_groups, d_win.get(), stream);
     return GDX_OK;
 }
 
@@ -2596,47 +2621,22 @@ int FmIndex::pair_hits_many(uint64_t n_pairs, uint32_t mate_slots, const uint32_
 {
     check_pair_hits(n_pairs, mate_slots, max_dist, min_insert, max_insert);
     if (n_pairs == 0) return GDX_OK;
-    if (!cand_query || !cand_begin || !cand_hits || !dist || !out_n_proper || !out_n_best || !out_pair_dist || !out_sub_dist ||
-        !out_mapq || !out_pair_span || !out_mate_slot || !out_mate_dist || !out_win_query || !out_win_begin || !out_win_hits)
+    if (any_null({cand_query, cand_begin, cand_hits, dist, out_n_proper, out_n_best, out_pair_dist, out_sub_dist, out_mapq, out_pair_span,
+                  out_mate_slot, out_mate_dist, out_win_query, out_win_begin, out_win_hits}))
         fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-    const uint64_t n_mates = 2 * n_pairs, m = n_mates * mate_slots;
-    std::vector<gdx_hit32_t> narrow(m);
-    for (uint64_t s = 0; s < m; s++) {
-        if (cand_hits[s].position > 0xffffffffull || cand_hits[s].text_id > 0xffffffffull)
-            fail(GDX_ERR_INVALID_ARGUMENT, "slot %llu: hit (%llu, %llu) does not fit 32 bits", (unsigned long long)s,
-                 (unsigned long long)cand_hits[s].text_id, (unsigned long long)cand_hits[s].position);
-        narrow[s].text_id = static_cast<uint32_t>(cand_hits[s].text_id);
-        narrow[s].position = static_cast<uint32_t>(cand_hits[s].position);
-    }
-    make_current();
+    const uint64_t n_mates = 2 * n_pairs;
     hipStream_t stream = hipStreamPerThread;
-    DeviceBuffer<uint32_t> d_in((end ? 4 : 3) * m);  // query, begin, dist, end
-    DeviceBuffer<uint32_t> d_out(14 * n_pairs);      // six per pair, then four per mate
-    DeviceBuffer<gdx_hit32_t> d_hits(m), d_win(n_mates);
-    GDX_HIP(hipMemcpyAsync(d_in.get(), cand_query, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_in.get() + m, cand_begin, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_in.get() + 2 * m, dist, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    if (end) GDX_HIP(hipMemcpyAsync(d_in.get() + 3 * m, end, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    GDX_HIP(hipMemcpyAsync(d_hits.get(), narrow.data(), m * sizeof(gdx_hit32_t), hipMemcpyHostToDevice, stream));
+    DeviceSlots slots(*this, cand_query, cand_begin, cand_hits, dist, end, n_mates * mate_slots, stream);
+    DeviceBuffer<uint32_t> d_out(14 * n_pairs);  // six per pair, then four per mate
+    DeviceBuffer<gdx_hit32_t> d_win(n_mates);
     uint32_t *o = d_out.get(), *w = o + 6 * n_pairs;
-    launch_pair_hits(n_pairs, mate_slots, d_in.get(), d_in.get() + m, d_hits.get(), d_in.get() + 2 * m,
-                     end ? d_in.get() + 3 * m : nullptr, max_dist, min_insert, max_insert, o, o + n_pairs, o + 2 * n_pairs,
-                     o + 3 * n_pairs, o + 4 * n_pairs, o + 5 * n_pairs, w, w + n_mates, w + 2 * n_mates, w + 3 * n_mates, d_win.get(),
-                     stream);
+    const PairArgs a = {slots.args(max_dist, w + 2 * n_mates, w + 3 * n_mates, d_win.get()), n_pairs, mate_slots, min_insert, max_insert,
+                        o, o + n_pairs, o + 2 * n_pairs, o + 3 * n_pairs, o + 4 * n_pairs, o + 5 * n_pairs, w, w + n_mates};
+    launch_pair_hits(a, stream);
     GDX_HIP(hipGetLastError());
-    std::vector<gdx_hit32_t> win(n_mates);
-    uint32_t *per_pair[6] = {out_n_proper, out_n_best, out_pair_dist, out_sub_dist, out_mapq, out_pair_span};
-    uint32_t *per_mate[4] = {out_mate_slot, out_mate_dist, out_win_query, out_win_begin};
-    for (int x = 0; x < 6; x++)
-        GDX_HIP(hipMemcpyAsync(per_pair[x], o + x * n_pairs, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    for (int x = 0; x < 4; x++)
-        GDX_HIP(hipMemcpyAsync(per_mate[x], w + x * n_mates, n_mates * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipMemcpyAsync(win.data(), d_win.get(), n_mates * sizeof(gdx_hit32_t), hipMemcpyDeviceToHost, stream));
-    GDX_HIP(hipStreamSynchronize(stream));
-    for (uint64_t g = 0; g < n_mates; g++) {
-        out_win_hits[g].text_id = win[g].text_id;
-        out_win_hits[g].position = win[g].position;
-    }
+    download_columns({out_n_proper, out_n_best, out_pair_dist, out_sub_dist, out_mapq, out_pair_span}, o, n_pairs, stream);
+    download_columns({out_mate_slot, out_mate_dist, out_win_query, out_win_begin}, w, n_mates, stream);
+    widen_hits(out_win_hits, n_mates, d_win.get(), stream);
     return GDX_OK;
 }
 

@@ -216,23 +216,18 @@ void launch_seed_candidates(const IndexView &ix, uint64_t nq, uint32_t max_seeds
 // gdx_best_hits_many_dev: n_groups groups of group_slots consecutive candidate slots and their distances from a verify call ->
 // per group the best slot, its distance, the runner-up's, the two counts, the mapping quality and the winner as a one-slot
 // candidate (the none pattern for a group without a live slot).  The caller has checked 1 <= group_slots <=
-// GDX_BEST_MAX_GROUP_SLOTS, max_dist <= 2^31 and that n_groups * group_slots fits 64 bits.  d_end may be null.  One launch.
-void launch_best_hits(uint64_t n_groups, uint32_t group_slots, const uint32_t *d_cand_query, const uint32_t *d_cand_begin,
-                      const gdx_hit32_t *d_cand_hits, const uint32_t *d_dist, const uint32_t *d_end, uint32_t max_dist,
-                      uint32_t *d_best_slot, uint32_t *d_best_dist, uint32_t *d_sub_dist, uint32_t *d_n_live, uint32_t *d_n_best,
-                      uint32_t *d_mapq, uint32_t *d_win_query, uint32_t *d_win_begin, gdx_hit32_t *d_win_hits, hipStream_t stream);
+// GDX_BEST_MAX_GROUP_SLOTS, max_dist <= 2^31 and that n_groups * group_slots fits 64 bits.  end may be null.  One launch.
+struct BestArgs;  // (select.hpp, as PairArgs)
+void launch_best_hits(const BestArgs &a, hipStream_t stream);
 
 // ---- pair_hits.hip ------------------------------------------------------------------------
 // gdx_pair_hits_many_dev: n_pairs pairs of two mates of mate_slots consecutive candidate slots each and their distances from a
 // verify call -> per pair the best proper combination's six words, per mate the winner's five (the single-end best without a
 // proper combination, the none pattern without a live slot).  The caller has checked 1 <= mate_slots <= GDX_PAIR_MAX_MATE_SLOTS,
-// max_dist <= 2^30, min_insert <= max_insert <= 2^31 - 1 and that 2 * n_pairs * mate_slots fits 64 bits.  d_end may be null.  One
+// max_dist <= 2^30, min_insert <= max_insert <= 2^31 - 1 and that 2 * n_pairs * mate_slots fits 64 bits.  end may be null.  One
 // launch.
-void launch_pair_hits(uint64_t n_pairs, uint32_t mate_slots, const uint32_t *d_cand_query, const uint32_t *d_cand_begin,
-                      const gdx_hit32_t *d_cand_hits, const uint32_t *d_dist, const uint32_t *d_end, uint32_t max_dist,
-                      uint32_t min_insert, uint32_t max_insert, uint32_t *d_n_proper, uint32_t *d_n_best, uint32_t *d_pair_dist,
-                      uint32_t *d_sub_dist, uint32_t *d_mapq, uint32_t *d_pair_span, uint32_t *d_mate_slot, uint32_t *d_mate_dist,
-                      uint32_t *d_win_query, uint32_t *d_win_begin, gdx_hit32_t *d_win_hits, hipStream_t stream);
+struct PairArgs;
+void launch_pair_hits(const PairArgs &a, hipStream_t stream);
 
 // ---- locate.hip ---------------------------------------------------------------------------
 size_t hit_offsets_temp_bytes(uint64_t m);

@@ -1,49 +1,34 @@
 // pair_hits.hip -- paired-end pairing of verified candidate slots: per read pair the best properly oriented, properly spaced
 // combination of one slot of each mate, whether it is unique, and the two winners as a candidate list for the traceback
-// (gdx_pair_hits_many[_dev]; the definition is in include/gdx_experimental.h "paired-end pairing").
+// (gdx_pair_hits_many[_dev]; the definition is in include/gdx_experimental.h "paired-end pairing").  Steps 1 and 2, the
+// butterfly of the least key, the mapq rule, the winner store and the dispatch are select.hpp's, shared with best_hits.hip.
 //
 //   pair_hits_kernel<P>  P = the next power of two >= mate_slots: a pair is 2P adjacent lanes, mate 0 on the lower P and mate 1 on
 //                        the upper, a wavefront holds 64 / 2P pairs of consecutive numbers, so the slots a wavefront loads from
 //                        each of the five input arrays are one contiguous run (lanes j >= mate_slots of a mate idle).  Blocks of
 //                        four wavefronts, grid-stride over tiles of 64 / 2P pairs with a bound that is uniform in the wavefront.
-//   1. live              as in best_hits_kernel; a dead lane carries distance 2^32 - 1 from here on
-//   2. same locus        best_hits_kernel's rotation pass at width P, inside each mate
+//   1. live              load_slot: a dead lane carries distance 2^32 - 1 from here on
+//   2. same locus        same_locus_pass at width P, inside each mate
 //   3. combinations      P rotations across the halves (__shfl of width 2P): lane i of one mate meets every lane of the other.
 //                        A slot ships its distance, its text and ONE signed 64-bit word -- twice its diagonal when it is on
 //                        strand 0, twice its right end when on strand 1, the strand in bit 0 -- so span = right_r - diag_f
 //                        whichever side the lane is on.
 //                        Each lane keeps its least score and the least partner that has it, that partner's span, how often the
 //                        score occurs, its second-least score and its count of proper partners.  Both halves run the pass.
-//   4. results           xor butterflies over the half: the least (score, i, j) as one 64-bit value (the same value in both
-//                        halves, so each mate's winning lane knows itself), the sums of the proper and tied counts in one word,
-//                        and sub_dist as the least of the best lane's second-least and the other lanes' least.
-//   5. winners           without a proper combination the least (dist, j) of each half, best_hits_kernel's reduction, carried
-//                        by the same butterfly under a flag bit.  Each mate's winning lane stores its five words, mate 0's the
-//                        six words of the pair (it holds the span).
+//   4. results           xor butterflies over the half: the least (score, i, j) as one 64-bit value (butterfly_min; the same
+//                        value in both halves, so each mate's winning lane knows itself), the sums of the proper and tied counts
+//                        in one word, and sub_dist as the least of the best lane's second-least and the other lanes' least.
+//   5. winners           without a proper combination the least (dist, j) of each half, carried by the same butterfly under a flag
+//                        bit.  Each mate's winning lane stores its five words, mate 0's the six words of the pair (it holds the
+//                        span).
 // No LDS, no atomics, no second launch.  Slot and pair numbers are 64 bits wide throughout; diagonals are signed 64-bit values.
-#include "../../include/gdx_experimental.h"
-#include "common.hpp"
-#include "kernels.hpp"
+#include "select.hpp"
 
 namespace gdx {
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kBlock = 256;
-constexpr uint32_t kMaxGrid = 256u * 16u;
-constexpr uint32_t kDead = 0xFFFFFFFFu;  // the distance a dead lane and the score a missing combination carry: above 2 * 2^30
-
-struct PairArgs {
-    uint64_t n_pairs;
-    uint32_t mate_slots, max_dist, min_insert, max_insert;
-    const uint32_t *cand_query, *cand_begin;
-    const gdx_hit32_t *cand_hits;
-    const uint32_t *dist, *end;  // end: or null
-    uint32_t *n_proper, *n_best, *pair_dist, *sub_dist, *mapq, *pair_span;
-    uint32_t *mate_slot, *mate_dist, *win_query, *win_begin;
-    gdx_hit32_t *win_hits;
-};
+using namespace select;
 
 template <int P>
 __global__ __launch_bounds__(kBlock) void pair_hits_kernel(const PairArgs a)
@@ -58,34 +43,12 @@ __global__ __launch_bounds__(kBlock) void pair_hits_kernel(const PairArgs a)
 
     for (uint64_t g0 = wave * kPairs; g0 < a.n_pairs; g0 += stride) {  // (uniform in the wavefront: every lane shuffles)
         const uint64_t g = g0 + lane / W, mate = 2 * g + h;
-        const bool in_pair = g < a.n_pairs && j < a.mate_slots;
-        uint32_t cq = GDX_CAND_NONE, cb = 0, e = 0, d = kDead;
-        uint32_t tid = 0, pos = 0;
-        int64_t coord = 0, diag = 0, right = 0;
-        if (in_pair) {
-            const uint64_t s = mate * a.mate_slots + j;
-            cq = a.cand_query[s];
-            cb = a.cand_begin[s];
-            tid = a.cand_hits[s].text_id;
-            pos = a.cand_hits[s].position;
-            const uint32_t ds = a.dist[s];
-            diag = static_cast<int64_t>(pos) - static_cast<int64_t>(cb);
-            right = a.end != nullptr ? static_cast<int64_t>(a.end[s]) : diag;
-            e = a.end != nullptr ? a.end[s] : pos - cb;
-            if (cq != GDX_CAND_NONE && ds <= k) d = ds;
-        }
-        const uint32_t strand = cq & 1u;
-        coord = (strand ? right : diag) * 2 + strand;  // (34 bits and a sign: the strand travels in bit 0)
-
-        // 2. a live slot of this mate with this lane's key and a smaller (dist, slot) takes the lane out
-        bool live = d != kDead;
-#pragma unroll
-        for (int r = 1; r < P; r++) {
-            const int src = static_cast<int>((j + r) & (P - 1));
-            const uint32_t oq = __shfl(cq, src, P), ot = __shfl(tid, src, P), oe = __shfl(e, src, P), od = __shfl(d, src, P);
-            const bool same = od != kDead && oq == cq && ot == tid && oe == e;
-            if (same && (od < d || (od == d && static_cast<uint32_t>(src) < j))) live = false;
-        }
+        const Slot x = load_slot(a, g < a.n_pairs && j < a.mate_slots, mate, a.mate_slots, j);
+        const uint32_t d = x.d, tid = x.tid, strand = x.cq & 1u;
+        const int64_t diag = static_cast<int64_t>(x.pos) - static_cast<int64_t>(x.cb);
+        const int64_t right = a.end != nullptr ? static_cast<int64_t>(x.e) : diag;
+        const int64_t coord = (strand ? right : diag) * 2 + strand;  // (34 bits and a sign: the strand travels in bit 0)
+        const bool live = same_locus_pass<P>(x, j);
         const uint32_t dl = live ? d : kDead;
 
         // 3. every slot of the other mate: least score and its least partner, the tie count, the second-least, the proper count
@@ -127,14 +90,9 @@ __global__ __launch_bounds__(kBlock) void pair_hits_kernel(const PairArgs a)
         // proper combination
         const uint32_t ci = h ? part : j, cj = h ? j : part;  // the combination (slot of mate 0, slot of mate 1)
         constexpr uint64_t kAlone = 1ull << 63;
-        uint64_t best = m1 != kDead ? (static_cast<uint64_t>(m1) << 16) | (ci << 8) | cj
-                        : live      ? kAlone | (static_cast<uint64_t>(d) << 8) | j
-                                    : ~0ull;
-#pragma unroll
-        for (int o = P / 2; o > 0; o >>= 1) {
-            const uint64_t w = __shfl_xor(best, o, P);
-            best = w < best ? w : best;
-        }
+        const uint64_t best = butterfly_min<P>(m1 != kDead ? (static_cast<uint64_t>(m1) << 16) | (ci << 8) | cj
+                                               : live      ? kAlone | (static_cast<uint64_t>(d) << 8) | j
+                                                           : ~0ull);
         const bool any = best < kAlone, mapped = best != ~0ull;
         const uint32_t pd = any ? static_cast<uint32_t>(best >> 16) : 2u * k + 2u;
         const uint32_t mine = h || !any ? static_cast<uint32_t>(best) & 0xFFu : (static_cast<uint32_t>(best) >> 8) & 0xFFu;
@@ -142,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void pair_hits_kernel(const PairArgs a)
         uint32_t counts = (n_prop << 16) | (any && m1 == pd ? cnt : 0u);  // (both sums are at most 32 * 32)
         uint32_t sub = winner ? m2 : m1;
 #pragma unroll
-        for (int o = P / 2; o > 0; o >>= 1) {
+        for (int o = P / 2; o > 0; o >>= 1) {  // (butterfly_min's steps with the sum of the counts between them)
             counts += __shfl_xor(counts, o, P);
             const uint32_t w = __shfl_xor(sub, o, P);
             sub = w < sub ? w : sub;
@@ -155,16 +113,9 @@ __global__ __launch_bounds__(kBlock) void pair_hits_kernel(const PairArgs a)
         if (g < a.n_pairs && writer) {  // (without a live slot: lane 0 of the mate writes the pattern)
             a.mate_slot[mate] = mapped ? j : GDX_PAIR_NONE;
             a.mate_dist[mate] = mapped ? d : k + 1u;
-            a.win_query[mate] = mapped ? cq : GDX_CAND_NONE;
-            a.win_begin[mate] = mapped ? cb : 0u;
-            a.win_hits[mate].text_id = mapped ? tid : 0u;
-            a.win_hits[mate].position = mapped ? pos : 0u;
+            store_winner(a, mate, mapped, x);
             if (h == 0u) {
-                uint32_t mapq = GDX_PAIR_MAPQ_NONE;
-                if (any) {
-                    const uint64_t q = 60ull * (sub - pd) / (2ull * k + 2ull);
-                    mapq = q < 60ull ? static_cast<uint32_t>(q) : 60u;
-                }
+                const uint32_t mapq = any ? mapq_of(sub, pd, 2ull * k + 2ull) : GDX_PAIR_MAPQ_NONE;
                 a.n_proper[g] = n_prop;
                 a.n_best[g] = n_best;
                 a.pair_dist[g] = pd;
@@ -176,52 +127,16 @@ __global__ __launch_bounds__(kBlock) void pair_hits_kernel(const PairArgs a)
     }
 }
 
-template <int P>
-void launch_instance(const PairArgs &a, hipStream_t stream)
-{
-    constexpr uint64_t per_block = static_cast<uint64_t>(kBlock) / (2 * P);  // pairs a block takes in one stride
-    const uint64_t blocks = (a.n_pairs + per_block - 1) / per_block;
-    const unsigned grid = static_cast<unsigned>(blocks < kMaxGrid ? blocks : kMaxGrid);
-    hipLaunchKernelGGL(pair_hits_kernel<P>, dim3(grid), dim3(kBlock), 0, stream, a);
-}
-
 }  // namespace
 
-void launch_pair_hits(uint64_t n_pairs, uint32_t mate_slots, const uint32_t *d_cand_query, const uint32_t *d_cand_begin,
-                      const gdx_hit32_t *d_cand_hits, const uint32_t *d_dist, const uint32_t *d_end, uint32_t max_dist,
-                      uint32_t min_insert, uint32_t max_insert, uint32_t *d_n_proper, uint32_t *d_n_best, uint32_t *d_pair_dist,
-                      uint32_t *d_sub_dist, uint32_t *d_mapq, uint32_t *d_pair_span, uint32_t *d_mate_slot, uint32_t *d_mate_dist,
-                      uint32_t *d_win_query, uint32_t *d_win_begin, gdx_hit32_t *d_win_hits, hipStream_t stream)
+void launch_pair_hits(const PairArgs &a, hipStream_t stream)
 {
-    if (n_pairs == 0) return;
-    PairArgs a;
-    a.n_pairs = n_pairs;
-    a.mate_slots = mate_slots;
-    a.max_dist = max_dist;
-    a.min_insert = min_insert;
-    a.max_insert = max_insert;
-    a.cand_query = d_cand_query;
-    a.cand_begin = d_cand_begin;
-    a.cand_hits = d_cand_hits;
-    a.dist = d_dist;
-    a.end = d_end;
-    a.n_proper = d_n_proper;
-    a.n_best = d_n_best;
-    a.pair_dist = d_pair_dist;
-    a.sub_dist = d_sub_dist;
-    a.mapq = d_mapq;
-    a.pair_span = d_pair_span;
-    a.mate_slot = d_mate_slot;
-    a.mate_dist = d_mate_dist;
-    a.win_query = d_win_query;
-    a.win_begin = d_win_begin;
-    a.win_hits = d_win_hits;
-    if (mate_slots <= 1u) launch_instance<1>(a, stream);
-    else if (mate_slots <= 2u) launch_instance<2>(a, stream);
-    else if (mate_slots <= 4u) launch_instance<4>(a, stream);
-    else if (mate_slots <= 8u) launch_instance<8>(a, stream);
-    else if (mate_slots <= 16u) launch_instance<16>(a, stream);
-    else launch_instance<32>(a, stream);  // (mate_slots <= GDX_PAIR_MAX_MATE_SLOTS = 32: checked by the caller)
+    if (a.n_pairs == 0) return;
+    dispatch_slots<GDX_PAIR_MAX_MATE_SLOTS>(a.mate_slots, [&](auto p) {  // (mate_slots <= 32: checked by the caller)
+        constexpr int P = decltype(p)::value;
+        const unsigned grid = grid_for(a.n_pairs, kBlock / (2 * P), kMaxGrid);  // (a block takes kBlock / 2P pairs in one stride)
+        hipLaunchKernelGGL(pair_hits_kernel<P>, dim3(grid), dim3(kBlock), 0, stream, a);
+    });
 }
 
 }  // namespace gdx

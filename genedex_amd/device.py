@@ -40,6 +40,13 @@ def _check_candidates(cand_query: torch.Tensor, cand_begin: torch.Tensor, cand_h
     return m
 
 
+def _check_slots(cands: dict, dist: torch.Tensor, end, slots: int, what: str) -> None:
+    """the candidate dict, dist and end (or None) of best_hits / pair_hits hold at least `slots` slots (`what` in words)"""
+    m = _check_candidates(cands["cand_query"], cands["cand_begin"], cands["cand_hits"])
+    if slots > m or dist.numel() < slots or (end is not None and end.numel() < slots):
+        raise ValueError(f"candidates, dist and end hold {what} slots")
+
+
 def _stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -458,14 +465,19 @@ class DeviceEngine:
             _ptr(out["remaining"]), _ptr(out["begin"]), _ptr(out["length"]), _ptr(out["start"]), _ptr(out["end"]),
             _ptr(out["status"]) if out.get("status") is not None else None, _stream()))
 
+    def _alloc_u32(self, *columns, hits=None):
+        """{name: int32[max(n, 1)]} for every (n, names) of columns, and int32[max(n, 1), 2] under hits = (n, name)"""
+        out = {name: torch.empty(max(n, 1), dtype=torch.int32, device=self.dev) for n, names in columns for name in names}
+        if hits is not None:
+            out[hits[1]] = torch.empty((max(hits[0], 1), 2), dtype=torch.int32, device=self.dev)
+        return out
+
     # ---- seed-hit candidates (gdx_seed_candidates_many_dev) --------------------------------------------------
     def alloc_seed_candidates(self, nq: int, max_candidates: int):
-        d = self.dev
-        slots = max(nq * max_candidates, 1)
-        out = {name: torch.empty(max(nq, 1), dtype=torch.int32, device=d) for name in ("n_candidates", "n_groups", "n_skipped")}
-        out.update({name: torch.empty(slots, dtype=torch.int32, device=d) for name in ("cand_query", "cand_begin", "cand_weight")})
-        out["cand_hits"] = torch.empty((slots, 2), dtype=torch.int32, device=d)
-        out["status"] = torch.empty(max(nq, 1), dtype=torch.uint8, device=d)
+        slots = nq * max_candidates
+        out = self._alloc_u32((nq, ("n_candidates", "n_groups", "n_skipped")), (slots, ("cand_query", "cand_begin", "cand_weight")),
+                              hits=(slots, "cand_hits"))
+        out["status"] = torch.empty(max(nq, 1), dtype=torch.uint8, device=self.dev)
         return out
 
     def seed_candidates(self, seeds: dict, nq: int, max_seeds: int, max_occ: int, band: int, max_candidates: int, out: dict = None):
@@ -559,12 +571,8 @@ class DeviceEngine:
 
     # ---- best hit per read (gdx_best_hits_many_dev) -----------------------------------------------------------
     def alloc_best_hits(self, n_groups: int):
-        d = self.dev
-        n = max(n_groups, 1)
-        out = {name: torch.empty(n, dtype=torch.int32, device=d)
-               for name in ("best_slot", "best_dist", "sub_dist", "n_live", "n_best", "mapq", "win_query", "win_begin")}
-        out["win_hits"] = torch.empty((n, 2), dtype=torch.int32, device=d)
-        return out
+        return self._alloc_u32((n_groups, ("best_slot", "best_dist", "sub_dist", "n_live", "n_best", "mapq", "win_query", "win_begin")),
+                               hits=(n_groups, "win_hits"))
 
     def best_hits(self, cands: dict, dist: torch.Tensor, end, n_groups: int, group_slots: int, max_dist: int, out: dict = None):
         """One launch: every group of group_slots consecutive candidate slots and the distances a verify call gave them -> the
@@ -574,10 +582,8 @@ class DeviceEngine:
         2 * max_candidates makes it a read.  out["win_query"], ["win_begin"] and ["win_hits"] go straight into align() /
         edit_distance() / hamming() as n_groups candidates: an unmapped read (best_slot -1, GDX_BEST_NONE; mapq 255) has
         win_query -1 (GDX_CAND_NONE) and gets the verify call's INVALID marker."""
-        m = _check_candidates(cands["cand_query"], cands["cand_begin"], cands["cand_hits"])
         n_groups, group_slots = int(n_groups), int(group_slots)
-        if n_groups * group_slots > m or dist.numel() < n_groups * group_slots or (end is not None and end.numel() < n_groups * group_slots):
-            raise ValueError("candidates, dist and end hold n_groups * group_slots slots")
+        _check_slots(cands, dist, end, n_groups * group_slots, "n_groups * group_slots")
         if out is None:
             out = self.alloc_best_hits(n_groups)
         _lib.check(self.lib.gdx_best_hits_many_dev(
@@ -613,13 +619,9 @@ class DeviceEngine:
 
     # ---- paired-end pairing (gdx_pair_hits_many_dev) -----------------------------------------------------------
     def alloc_pair_hits(self, n_pairs: int):
-        d = self.dev
-        n = max(n_pairs, 1)
-        out = {name: torch.empty(n, dtype=torch.int32, device=d)
-               for name in ("n_proper", "n_best", "pair_dist", "sub_dist", "mapq", "pair_span")}
-        out.update({name: torch.empty(2 * n, dtype=torch.int32, device=d) for name in ("mate_slot", "mate_dist", "win_query", "win_begin")})
-        out["win_hits"] = torch.empty((2 * n, 2), dtype=torch.int32, device=d)
-        return out
+        n_mates = 2 * max(n_pairs, 1)
+        return self._alloc_u32((n_pairs, ("n_proper", "n_best", "pair_dist", "sub_dist", "mapq", "pair_span")),
+                               (n_mates, ("mate_slot", "mate_dist", "win_query", "win_begin")), hits=(n_mates, "win_hits"))
 
     def pair_hits(self, cands: dict, dist: torch.Tensor, end, n_pairs: int, mate_slots: int, max_dist: int, min_insert: int,
                   max_insert: int, out: dict = None):
@@ -631,11 +633,8 @@ class DeviceEngine:
         "pair_span"; per mate "mate_slot" (-1, GDX_PAIR_NONE, without a live slot), "mate_dist" and the winner "win_query",
         "win_begin", "win_hits" -- the pair's slot, or the mate's single-end best when the pair has no proper combination --
         which go straight into align() as 2 * n_pairs candidates."""
-        m = _check_candidates(cands["cand_query"], cands["cand_begin"], cands["cand_hits"])
         n_pairs, mate_slots = int(n_pairs), int(mate_slots)
-        slots = 2 * n_pairs * mate_slots
-        if slots > m or dist.numel() < slots or (end is not None and end.numel() < slots):
-            raise ValueError("candidates, dist and end hold 2 * n_pairs * mate_slots slots")
+        _check_slots(cands, dist, end, 2 * n_pairs * mate_slots, "2 * n_pairs * mate_slots")
         if out is None:
             out = self.alloc_pair_hits(n_pairs)
         _lib.check(self.lib.gdx_pair_hits_many_dev(

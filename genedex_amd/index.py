@@ -585,6 +585,16 @@ class FmIndex:
         return [[SeedCandidate(int(cb[k]), int(t[k]), int(p[k]), int(cw[k])) for k in range(i * mc, i * mc + int(n_cand[i]))]
                 for i in range(nq)]
 
+    @staticmethod
+    def _slot_arrays(cand_query, cand_begin, text_ids, positions, dist, end, m, what):
+        """the inputs of best_hits_raw / pair_hits_raw as contiguous arrays of m (`what`) slots: u32, end or None, hits u64[m, 2]"""
+        cq, cb, dist = (np.ascontiguousarray(x, dtype=np.uint32) for x in (cand_query, cand_begin, dist))
+        end = None if end is None else np.ascontiguousarray(end, dtype=np.uint32)
+        hits = np.ascontiguousarray(np.stack([np.asarray(text_ids, dtype=np.uint64), np.asarray(positions, dtype=np.uint64)], axis=1))
+        if any(x is not None and x.size != m for x in (cq, cb, dist, end, hits[:, 0])):
+            raise ValueError(f"slot arrays hold {what} slots")
+        return cq, cb, dist, end, hits
+
     # ---- best hit per read (gdx_experimental.h "best hit per read") ------------------------------------------
     def best_hits_raw(self, cand_query, cand_begin, text_ids, positions, dist, end, n_groups, group_slots, max_dist):
         """gdx_best_hits_many -> (best_slot, best_dist, sub_dist, n_live, n_best, mapq, win_query, win_begin: u32[n_groups];
@@ -593,13 +603,8 @@ class FmIndex:
         edit-distance call, or None (the Hamming case: the diagonal tells loci apart).  A group without a live slot has
         best_slot GDX_BEST_NONE, mapq GDX_BEST_MAPQ_NONE and the none pattern as its winner."""
         ng, gs = int(n_groups), int(group_slots)
-        m = ng * gs
-        cq, cb, dist = (np.ascontiguousarray(x, dtype=np.uint32) for x in (cand_query, cand_begin, dist))
-        end = None if end is None else np.ascontiguousarray(end, dtype=np.uint32)
-        hits = np.ascontiguousarray(np.stack([np.asarray(text_ids, dtype=np.uint64), np.asarray(positions, dtype=np.uint64)], axis=1))
-        for x in (cq, cb, dist, end, hits[:, 0]):
-            if x is not None and x.size != m:
-                raise ValueError("slot arrays hold n_groups * group_slots slots")
+        cq, cb, dist, end, hits = self._slot_arrays(cand_query, cand_begin, text_ids, positions, dist, end, ng * gs,
+                                                    "n_groups * group_slots")
         outs = [np.zeros(max(ng, 1), dtype=np.uint32) for _ in range(8)]
         win = np.zeros((max(ng, 1), 2), dtype=np.uint64)
         _lib.check(self._lib.gdx_best_hits_many(self._h, ng, gs, _p(cq, u32p), _p(cb, u32p),
@@ -617,13 +622,8 @@ class FmIndex:
         per pair the best combination of one slot of each mate that lies on one text, on opposite strands and min_insert ..
         max_insert apart, per mate the winner (its single-end best without such a combination).  `end` as in best_hits_raw."""
         n, ms = int(n_pairs), int(mate_slots)
-        m = 2 * n * ms
-        cq, cb, dist = (np.ascontiguousarray(x, dtype=np.uint32) for x in (cand_query, cand_begin, dist))
-        end = None if end is None else np.ascontiguousarray(end, dtype=np.uint32)
-        hits = np.ascontiguousarray(np.stack([np.asarray(text_ids, dtype=np.uint64), np.asarray(positions, dtype=np.uint64)], axis=1))
-        for x in (cq, cb, dist, end, hits[:, 0]):
-            if x is not None and x.size != m:
-                raise ValueError("slot arrays hold 2 * n_pairs * mate_slots slots")
+        cq, cb, dist, end, hits = self._slot_arrays(cand_query, cand_begin, text_ids, positions, dist, end, 2 * n * ms,
+                                                    "2 * n_pairs * mate_slots")
         pairs = [np.zeros(max(n, 1), dtype=np.uint32) for _ in range(6)]
         mates = [np.zeros(max(2 * n, 1), dtype=np.uint32) for _ in range(4)]
         win = np.zeros((max(2 * n, 1), 2), dtype=np.uint64)
