@@ -5,6 +5,7 @@
 #include <cstring>
 #include <map>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -152,6 +153,17 @@ bool wants_wide(const uint64_t *text_offsets, uint64_t n_texts, int index_width)
 }
 
 hipStream_t as_stream(void *s) { return static_cast<hipStream_t>(s); }
+uint32_t *u32(void *p) { return static_cast<uint32_t *>(p); }
+const uint32_t *u32(const void *p) { return static_cast<const uint32_t *>(p); }
+
+// struct_size lets a struct of the ABI grow: a caller compiled against an older header passes a shorter struct, whose
+// missing tail keeps the defaults `full` was initialised with; a longer one (newer caller) is read up to what this library
+// knows.  (The caller has checked its own minimum -- and the layout, which refuses a longer struct, its maximum.)
+template <class T>
+void copy_struct_prefix(T &full, const T *given)
+{
+    std::memcpy(&full, given, given->struct_size < sizeof(T) ? given->struct_size : sizeof(T));
+}
 
 // makes the handle's device current for the duration of a call and restores the caller's afterwards
 struct DeviceGuard {
@@ -173,17 +185,105 @@ struct DeviceGuard {
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
 
+// A host entry that both engines serve: call(index) on whichever of the two the handle holds, the wide one on its device
+// (FmIndex's host methods make their device current themselves).
+template <class Call>
+int on_either_index(const gdx_index_t *ix, Call &&call)
+{
+    if (ix && ix->wide) {
+        DeviceGuard guard(ix->wide->config().device_id);
+        return call(*ix->wide);
+    }
+    return call(deref(ix));
+}
+
+// A device entry: the handle, then body(d) -- the entry's own argument checks in their order, d.enter(), the launches on d.st
+// -- and, once the device was entered, whatever error the launches left.  A body that returns before d.enter() had nothing to do.
+struct DeviceCall {
+    const gdx::FmIndex &f;
+    hipStream_t st;
+    std::optional<DeviceGuard> guard;
+    void enter()
+    {
+        if (!guard) guard.emplace(f.config().device_id);
+    }
+    void search(const gdx::SearchCall &c)  // enter() and the search launch most entries end with
+    {
+        enter();
+        gdx::launch_search_call(f.view(), c, st, f.query_options());
+    }
+};
+template <class Body>
+int device_call(const gdx_index_t *ix, void *stream, Body &&body)
+{
+    return guarded([&] {
+        DeviceCall d{deref(ix), as_stream(stream), std::nullopt};
+        body(d);
+        if (d.guard) GDX_HIP(hipGetLastError());
+        return (int)GDX_OK;
+    });
+}
+
+// ---- checks that several entries make in the same words ----
+void aligned(const void *p, uintptr_t mask, const char *message)
+{
+    if ((reinterpret_cast<uintptr_t>(p) & mask) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "%s", message);
+}
+void check_qbuf(const void *d_qbuf) { aligned(d_qbuf, 7u, "d_qbuf must be 8-byte aligned"); }
+void check_records(const void *d_records)
+{
+    if (!d_records || (reinterpret_cast<uintptr_t>(d_records) & 15u) != 0)
+        gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_records must be a non-null 16-byte aligned device pointer");
+}
+void check_narrow_offsets(bool narrow, uint64_t hits)
+{
+    if (narrow && hits >= (1ull << 32)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "32-bit hit offsets need fewer than 2^32 hits");
+}
+
+// ---- query layouts: packed and / or uniform batches through one description (gdx.h) ----
+gdx_query_layout_t parse_layout(const gdx_query_layout_t *layout)  // (null = ASCII with offsets: the plain calls)
+{
+    gdx_query_layout_t l;
+    gdx_query_layout_init(&l);
+    if (layout) {
+        if (layout->struct_size < 16 || layout->struct_size > sizeof(l)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_query_layout_t.struct_size");
+        copy_struct_prefix(l, layout);
+    }
+    if (l.packed != 0 && l.packed != 1) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_query_layout_t.packed must be 0 or 1");
+    if (l.uniform_len >= (1ull << 21)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_query_layout_t.uniform_len must be below 2^21");
+    return l;
+}
+
+// the query side of a SearchCall from a batch on the device in a layout; the entry sets its outputs and the mode
+gdx::SearchCall query_side(const void *d_qbuf, const void *d_qoff, uint64_t nq, const gdx_query_layout_t *layout)
+{
+    const gdx_query_layout_t l = parse_layout(layout);
+    if (l.packed)
+        aligned(d_qbuf, 1u, "d_qbuf (packed) must be 2-byte aligned");
+    else
+        check_qbuf(d_qbuf);
+    if (l.uniform_len == 0 && !d_qoff && nq != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qoff is null and the layout is not uniform");
+    gdx::SearchCall c;
+    c.d_qbuf = static_cast<const uint8_t *>(d_qbuf);
+    c.nq = nq;
+    c.packed = l.packed != 0;
+    c.uniform_len = static_cast<uint32_t>(l.uniform_len);
+    if (l.uniform_len == 0) {
+        c.d_qbeg = static_cast<const uint64_t *>(d_qoff);
+        c.d_qend = c.d_qbeg + 1;
+    }
+    return c;
+}
+
 gdx::BuildOptions make_build_options(const gdx_build_options_t *o)
 {
     gdx::BuildOptions b;
     if (!o) return b;
-    // struct_size lets the struct grow: a caller compiled against an older header passes a shorter struct, whose
-    // missing tail takes the defaults; a longer one (newer caller) is read up to what this library knows
     gdx_build_options_t full;
     gdx_build_options_init(&full);
     if (o->struct_size < 2 * sizeof(uint32_t))
         gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_build_options_t.struct_size is %u (use gdx_build_options_init)", o->struct_size);
-    std::memcpy(&full, o, o->struct_size < sizeof(full) ? o->struct_size : sizeof(full));
+    copy_struct_prefix(full, o);
     o = &full;
     if (o->pair_lines < -1 || o->pair_lines > 1) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "pair_lines must be -1, 0 or 1");
     if (o->jump_entry_bytes != -1 && o->jump_entry_bytes != 0 && o->jump_entry_bytes != 8 && o->jump_entry_bytes != 16 &&
@@ -218,11 +318,10 @@ gdx::QueryOptions parse_query_options(const gdx_query_options_t *opts)
     gdx::QueryOptions q;
     gdx_query_options_t full;
     if (opts) {
-        // (struct_size: as in make_build_options -- a shorter struct of an older caller keeps defaults for the rest)
         gdx_query_options_init(&full);
         if (opts->struct_size < 2 * sizeof(uint32_t))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_query_options_t.struct_size is too small (use gdx_query_options_init)");
-        std::memcpy(&full, opts, opts->struct_size < sizeof(full) ? opts->struct_size : sizeof(full));
+        copy_struct_prefix(full, opts);
         opts = &full;
         if (opts->search_kernel < -1 || opts->search_kernel > 2 ||
             (opts->search_lanes != 0 && opts->search_lanes != 4 && opts->search_lanes != 8) || opts->load_policy < -1 ||
@@ -664,11 +763,9 @@ int gdx_count_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *q
 {
     return guarded([&] {
         if (!out_counts && nq) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "out_counts is null");
-        if (ix && ix->wide) {
-            DeviceGuard guard(ix->wide->config().device_id);
-            return ix->wide->cursors_for_many_queries(qbuf, qoff, nq, nullptr, nullptr, out_counts, out_status);
-        }
-        return deref(ix).cursors_for_many_queries(qbuf, qoff, nq, nullptr, nullptr, out_counts, out_status);
+        return on_either_index(ix, [&](const auto &x) {
+            return x.cursors_for_many_queries(qbuf, qoff, nq, nullptr, nullptr, out_counts, out_status);
+        });
     });
 }
 
@@ -677,11 +774,9 @@ int gdx_cursors_for_many_queries(const gdx_index_t *ix, const uint8_t *qbuf, con
 {
     return guarded([&] {
         if ((!out_start || !out_end) && nq) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "out_start / out_end is null");
-        if (ix && ix->wide) {
-            DeviceGuard guard(ix->wide->config().device_id);
-            return ix->wide->cursors_for_many_queries(qbuf, qoff, nq, out_start, out_end, nullptr, out_status);
-        }
-        return deref(ix).cursors_for_many_queries(qbuf, qoff, nq, out_start, out_end, nullptr, out_status);
+        return on_either_index(ix, [&](const auto &x) {
+            return x.cursors_for_many_queries(qbuf, qoff, nq, out_start, out_end, nullptr, out_status);
+        });
     });
 }
 
@@ -690,11 +785,10 @@ int gdx_locate_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *
                     uint8_t *out_status)
 {
     return guarded([&] {
-        if (ix && ix->wide) {
-            DeviceGuard guard(ix->wide->config().device_id);
-            return ix->wide->locate_many(qbuf, qoff, nq, out_hit_offsets, hits, hits ? hits_capacity : 0, out_total, out_status);
-        }
-        return deref(ix).locate_many(qbuf, qoff, nq, out_hit_offsets, hits, hits_capacity, out_total, out_status);
+        return on_either_index(ix, [&](const auto &x) {
+            constexpr bool wide = std::is_same_v<std::decay_t<decltype(x)>, gdx::WideIndex>;  // (takes a capacity without hits amiss)
+            return x.locate_many(qbuf, qoff, nq, out_hit_offsets, hits, wide && !hits ? 0 : hits_capacity, out_total, out_status);
+        });
     });
 }
 
@@ -702,11 +796,9 @@ int gdx_locate_many_alloc(const gdx_index_t *ix, const uint8_t *qbuf, const uint
                           uint64_t *out_hit_offsets, gdx_hit_t **out_hits, uint64_t *out_total, uint8_t *out_status)
 {
     return guarded([&] {
-        if (ix && ix->wide) {
-            DeviceGuard guard(ix->wide->config().device_id);
-            return ix->wide->locate_many_alloc(qbuf, qoff, nq, out_hit_offsets, out_hits, out_total, out_status);
-        }
-        return deref(ix).locate_many_alloc(qbuf, qoff, nq, out_hit_offsets, out_hits, out_total, out_status);
+        return on_either_index(ix, [&](const auto &x) {
+            return x.locate_many_alloc(qbuf, qoff, nq, out_hit_offsets, out_hits, out_total, out_status);
+        });
     });
 }
 
@@ -732,11 +824,7 @@ int gdx_cursor_extend_front_many(const gdx_index_t *ix, uint64_t *start, uint64_
                                  uint64_t m, uint8_t *out_status)
 {
     return guarded([&] {
-        if (ix && ix->wide) {
-            DeviceGuard guard(ix->wide->config().device_id);
-            return ix->wide->cursor_extend_front_many(start, end, io_symbols, m, out_status);
-        }
-        return deref(ix).cursor_extend_front_many(start, end, io_symbols, m, out_status);
+        return on_either_index(ix, [&](const auto &x) { return x.cursor_extend_front_many(start, end, io_symbols, m, out_status); });
     });
 }
 
@@ -744,11 +832,9 @@ int gdx_cursor_locate_many(const gdx_index_t *ix, const uint64_t *start, const u
                            uint64_t *out_hit_offsets, gdx_hit_t *hits, uint64_t hits_capacity, uint64_t *out_total)
 {
     return guarded([&] {
-        if (ix && ix->wide) {
-            DeviceGuard guard(ix->wide->config().device_id);
-            return ix->wide->cursor_locate_many(start, end, m, out_hit_offsets, hits, hits_capacity, out_total);
-        }
-        return deref(ix).cursor_locate_many(start, end, m, out_hit_offsets, hits, hits_capacity, out_total);
+        return on_either_index(ix, [&](const auto &x) {
+            return x.cursor_locate_many(start, end, m, out_hit_offsets, hits, hits_capacity, out_total);
+        });
     });
 }
 
@@ -757,68 +843,38 @@ int gdx_cursor_locate_many(const gdx_index_t *ix, const uint64_t *start, const u
 int gdx_cursors_for_many_queries_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
                                      void *d_out_start, void *d_out_end, void *d_out_status, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        if ((reinterpret_cast<uintptr_t>(d_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf must be 8-byte aligned");
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_search(f.view(), static_cast<const uint8_t *>(d_qbuf), static_cast<const uint64_t *>(d_qoff), nq,
-                           static_cast<uint32_t *>(d_out_start), static_cast<uint32_t *>(d_out_end), nullptr,
-                           static_cast<uint8_t *>(d_out_status), as_stream(stream), nullptr, nullptr, f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
-    });
+    return gdx_cursors_for_many_queries_layout_dev(ix, d_qbuf, d_qoff, nq, nullptr, d_out_start, d_out_end, d_out_status, stream);
 }
 
 int gdx_cursors_for_many_queries_hint_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
                                           void *d_out_start, void *d_out_end, void *d_out_status, void *d_hint,
                                           void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        if ((reinterpret_cast<uintptr_t>(d_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf must be 8-byte aligned");
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, nullptr);
         if (!d_hint || (reinterpret_cast<uintptr_t>(d_hint) & 7u) != 0)
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_hint must be a non-null 8-byte aligned device pointer");
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_search(f.view(), static_cast<const uint8_t *>(d_qbuf), static_cast<const uint64_t *>(d_qoff), nq,
-                           static_cast<uint32_t *>(d_out_start), static_cast<uint32_t *>(d_out_end), nullptr,
-                           static_cast<uint8_t *>(d_out_status), as_stream(stream), nullptr,
-                           static_cast<uint2 *>(d_hint), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        c.d_start = u32(d_out_start);
+        c.d_end = u32(d_out_end);
+        c.d_status = static_cast<uint8_t *>(d_out_status);
+        c.d_hint = static_cast<uint2 *>(d_hint);
+        d.search(c);
     });
 }
 
 int gdx_count_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq, void *d_out_counts,
                        void *d_out_status, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        if ((reinterpret_cast<uintptr_t>(d_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf must be 8-byte aligned");
-        DeviceGuard guard(f.config().device_id);
-        gdx::SearchCall c;  // counts only: the search may end with the lazy tail (mode 1)
-        c.d_qbuf = static_cast<const uint8_t *>(d_qbuf);
-        c.d_qbeg = static_cast<const uint64_t *>(d_qoff);
-        c.d_qend = c.d_qbeg + 1;
-        c.nq = nq;
-        c.d_count = static_cast<uint32_t *>(d_out_counts);
-        c.d_status = static_cast<uint8_t *>(d_out_status);
-        c.mode = 1;
-        gdx::launch_search_call(f.view(), c, as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
-    });
+    return gdx_count_many_layout_dev(ix, d_qbuf, d_qoff, nq, nullptr, d_out_counts, d_out_status, stream);
 }
 
 int gdx_cursor_extend_front_many_dev(const gdx_index_t *ix, void *d_start, void *d_end, const void *d_io_symbols,
                                      uint64_t m, void *d_out_status, void *stream)
 {
-    return guarded([&] {
-        DeviceGuard guard(deref(ix).config().device_id);
-        gdx::launch_extend_front(deref(ix).view(), static_cast<uint32_t *>(d_start), static_cast<uint32_t *>(d_end),
-                                 static_cast<const uint8_t *>(d_io_symbols), m, static_cast<uint8_t *>(d_out_status),
-                                 as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        d.enter();
+        gdx::launch_extend_front(d.f.view(), u32(d_start), u32(d_end), static_cast<const uint8_t *>(d_io_symbols), m,
+                                 static_cast<uint8_t *>(d_out_status), d.st);
     });
 }
 
@@ -841,29 +897,32 @@ int gdx_locate_intervals_dev(const gdx_index_t *ix, const void *d_start, const v
                              const void *d_hit_offsets, uint64_t total_hits, void *d_hits, void *d_workspace,
                              void *stream)
 {
-    return guarded([&] {
-        DeviceGuard guard(deref(ix).config().device_id);
-        gdx::launch_locate(deref(ix).view(), static_cast<const uint32_t *>(d_start),
-                           static_cast<const uint32_t *>(d_end), m, static_cast<const uint64_t *>(d_hit_offsets),
-                           total_hits, d_hits, false, d_workspace, as_stream(stream), nullptr, nullptr,
-                           deref(ix).query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
-    });
+    return gdx_locate_intervals_hint_dev(ix, d_start, d_end, m, d_hit_offsets, total_hits, d_hits, d_workspace, nullptr, stream);
+}
+
+// a locate of 8-byte hits into total_hits slots: the entries name where their intervals come from
+static gdx::LocateCall locate_into(uint64_t m, const void *d_hit_offsets, uint64_t total_hits, void *d_hits, void *d_workspace)
+{
+    gdx::LocateCall c;
+    c.m = m;
+    c.d_hit_offsets = d_hit_offsets;
+    c.total_hits = total_hits;
+    c.d_hits = d_hits;
+    c.d_workspace = d_workspace;
+    return c;
 }
 
 int gdx_locate_intervals_hint_dev(const gdx_index_t *ix, const void *d_start, const void *d_end, uint64_t m,
                                   const void *d_hit_offsets, uint64_t total_hits, void *d_hits, void *d_workspace,
                                   const void *d_hint, void *stream)
 {
-    return guarded([&] {
-        DeviceGuard guard(deref(ix).config().device_id);
-        gdx::launch_locate(deref(ix).view(), static_cast<const uint32_t *>(d_start),
-                           static_cast<const uint32_t *>(d_end), m, static_cast<const uint64_t *>(d_hit_offsets),
-                           total_hits, d_hits, false, d_workspace, as_stream(stream), nullptr,
-                           static_cast<const uint2 *>(d_hint), deref(ix).query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::LocateCall c = locate_into(m, d_hit_offsets, total_hits, d_hits, d_workspace);
+        c.d_start = u32(d_start);
+        c.d_end = u32(d_end);
+        c.d_hint = static_cast<const uint2 *>(d_hint);
+        d.enter();
+        gdx::launch_locate(d.f.view(), c, d.st, d.f.query_options());
     });
 }
 
@@ -878,32 +937,17 @@ __global__ __launch_bounds__(256) void unpack_records_kernel(const uint4 *__rest
         if (status) status[q] = static_cast<uint8_t>(r.w >> 24);
     }
 }
-
-void check_records(const void *d_records)
-{
-    if (!d_records || (reinterpret_cast<uintptr_t>(d_records) & 15u) != 0)
-        gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_records must be a non-null 16-byte aligned device pointer");
-}
 }  // namespace
 
 int gdx_locate_many_search_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
                                void *d_records, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        if ((reinterpret_cast<uintptr_t>(d_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf must be 8-byte aligned");
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, nullptr);
         check_records(d_records);
-        DeviceGuard guard(f.config().device_id);
-        gdx::SearchCall c;
-        c.d_qbuf = static_cast<const uint8_t *>(d_qbuf);
-        c.d_qbeg = static_cast<const uint64_t *>(d_qoff);
-        c.d_qend = c.d_qbeg + 1;
-        c.nq = nq;
         c.d_rec = static_cast<uint4 *>(d_records);
         c.mode = 1;
-        gdx::launch_search_call(f.view(), c, as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.search(c);
     });
 }
 
@@ -931,32 +975,19 @@ int gdx_locate_many_offsets_capped_dev(const gdx_index_t *ix, const void *d_reco
 int gdx_locate_many_hits_dev(const gdx_index_t *ix, const void *d_records, uint64_t nq, const void *d_hit_offsets,
                              uint64_t total_hits, void *d_hits, void *d_workspace, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        check_records(d_records);
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_locate(f.view(), nullptr, nullptr, nq, static_cast<const uint64_t *>(d_hit_offsets), total_hits,
-                           d_hits, false, d_workspace, as_stream(stream), nullptr, nullptr, f.query_options(),
-                           static_cast<const uint4 *>(d_records));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
-    });
+    return gdx_locate_many_hits_compact_dev(ix, d_records, nullptr, nq, d_hit_offsets, total_hits, d_hits, d_workspace, stream);
 }
 
 int gdx_locate_many_unpack_dev(const gdx_index_t *ix, const void *d_records, uint64_t nq, void *d_out_counts,
                                void *d_out_status, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         check_records(d_records);
-        if (nq == 0) return (int)GDX_OK;
-        DeviceGuard guard(f.config().device_id);
+        if (nq == 0) return;
+        d.enter();
         const uint64_t blocks = (nq + 255) / 256;
-        hipLaunchKernelGGL(unpack_records_kernel, dim3(static_cast<unsigned>(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                           as_stream(stream), static_cast<const uint4 *>(d_records), nq,
-                           static_cast<uint32_t *>(d_out_counts), static_cast<uint8_t *>(d_out_status));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        hipLaunchKernelGGL(unpack_records_kernel, dim3(static_cast<unsigned>(blocks < 4096 ? blocks : 4096)), dim3(256), 0, d.st,
+                           static_cast<const uint4 *>(d_records), nq, u32(d_out_counts), static_cast<uint8_t *>(d_out_status));
     });
 }
 
@@ -965,23 +996,14 @@ int gdx_locate_many_unpack_dev(const gdx_index_t *ix, const void *d_records, uin
 int gdx_locate_many_search_compact_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
                                        void *d_records, void *d_compact, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        if ((reinterpret_cast<uintptr_t>(d_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf must be 8-byte aligned");
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, nullptr);
         check_records(d_records);
         if (!d_compact && nq != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_compact is null");
-        DeviceGuard guard(f.config().device_id);
-        gdx::SearchCall c;
-        c.d_qbuf = static_cast<const uint8_t *>(d_qbuf);
-        c.d_qbeg = static_cast<const uint64_t *>(d_qoff);
-        c.d_qend = c.d_qbeg + 1;
-        c.nq = nq;
         c.d_rec = static_cast<uint4 *>(d_records);
-        c.d_compact = static_cast<uint32_t *>(d_compact);
+        c.d_compact = u32(d_compact);
         c.mode = 1;
-        gdx::launch_search_call(f.view(), c, as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.search(c);
     });
 }
 
@@ -1003,15 +1025,13 @@ int gdx_locate_many_offsets_compact_dev(const gdx_index_t *ix, const void *d_rec
 int gdx_locate_many_hits_compact_dev(const gdx_index_t *ix, const void *d_records, const void *d_compact, uint64_t nq,
                                      const void *d_hit_offsets, uint64_t total_hits, void *d_hits, void *d_workspace, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         check_records(d_records);
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_locate(f.view(), nullptr, nullptr, nq, static_cast<const uint64_t *>(d_hit_offsets), total_hits,
-                           d_hits, false, d_workspace, as_stream(stream), nullptr, nullptr, f.query_options(),
-                           static_cast<const uint4 *>(d_records), false, static_cast<const uint32_t *>(d_compact));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        gdx::LocateCall c = locate_into(nq, d_hit_offsets, total_hits, d_hits, d_workspace);
+        c.d_rec = static_cast<const uint4 *>(d_records);
+        c.d_compact = u32(d_compact);
+        d.enter();
+        gdx::launch_locate(d.f.view(), c, d.st, d.f.query_options());
     });
 }
 
@@ -1020,15 +1040,12 @@ uint64_t gdx_locate_many_totals_workspace_bytes(uint64_t nq) { return gdx::scan_
 int gdx_locate_many_totals_compact_dev(const gdx_index_t *ix, const void *d_records, const void *d_compact, uint64_t nq,
                                        uint32_t max_hits, void *d_scan_workspace, void *d_totals, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         check_records(d_records);
         if (!d_scan_workspace || !d_totals) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_locate_many_totals_compact_dev: null argument");
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_scan_totals(static_cast<const uint4 *>(d_records), static_cast<const uint32_t *>(d_compact), nq, max_hits,
-                                false, d_scan_workspace, static_cast<unsigned long long *>(d_totals), as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.enter();
+        gdx::launch_scan_totals(static_cast<const uint4 *>(d_records), u32(d_compact), nq, max_hits, false, d_scan_workspace,
+                                static_cast<unsigned long long *>(d_totals), d.st);
     });
 }
 
@@ -1036,20 +1053,16 @@ static int offsets_hits_compact(bool narrow, const gdx_index_t *ix, const void *
                                              uint32_t max_hits, const void *d_scan_workspace, void *d_hit_offsets,
                                              uint64_t total_hits, uint64_t rest_hits, void *d_hits, void *d_workspace, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         check_records(d_records);
         if (!d_scan_workspace || !d_hit_offsets || (total_hits != 0 && !d_hits))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_locate_many_offsets_hits_compact_dev: null argument");
-        if (narrow && total_hits >= (1ull << 32)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "32-bit hit offsets need fewer than 2^32 hits");
+        check_narrow_offsets(narrow, total_hits);
         if ((rest_hits != 0 || d_compact == nullptr) && total_hits != 0 && !d_workspace)
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_locate_many_offsets_hits_compact_dev: d_workspace is null");
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_offsets_hits(f.view(), static_cast<const uint4 *>(d_records), static_cast<const uint32_t *>(d_compact), nq, max_hits,
-                                 false, d_scan_workspace, d_hit_offsets, narrow, total_hits, rest_hits, d_hits, d_workspace,
-                                 as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.enter();
+        gdx::launch_offsets_hits(d.f.view(), static_cast<const uint4 *>(d_records), u32(d_compact), nq, max_hits, false, d_scan_workspace,
+                                 d_hit_offsets, narrow, total_hits, rest_hits, d_hits, d_workspace, d.st, d.f.query_options());
     });
 }
 
@@ -1072,52 +1085,43 @@ int gdx_locate_many_offsets32_hits_compact_dev(const gdx_index_t *ix, const void
 int gdx_locate_many_unpack_compact_dev(const gdx_index_t *ix, const void *d_records, const void *d_compact, uint64_t nq,
                                        void *d_out_counts, void *d_out_status, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         check_records(d_records);
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_unpack_records(static_cast<const uint4 *>(d_records), nq, static_cast<uint32_t *>(d_out_counts),
-                                   static_cast<uint8_t *>(d_out_status), as_stream(stream), static_cast<const uint32_t *>(d_compact));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.enter();
+        gdx::launch_unpack_records(static_cast<const uint4 *>(d_records), nq, u32(d_out_counts), static_cast<uint8_t *>(d_out_status), d.st,
+                                   u32(d_compact));
     });
 }
 
 int gdx_compact_split_hits_dev(const gdx_index_t *ix, const void *d_compact, uint64_t nq, void *d_out_text_ids,
                                void *d_out_positions, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         if (d_compact == nullptr || d_out_text_ids == nullptr || d_out_positions == nullptr)
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_compact_split_hits_dev: null buffer");
         if ((reinterpret_cast<uintptr_t>(d_compact) | reinterpret_cast<uintptr_t>(d_out_positions)) % 16 != 0 ||
             reinterpret_cast<uintptr_t>(d_out_text_ids) % 4 != 0)
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_compact_split_hits_dev: buffers must be 16-byte (text ids: 4-byte) aligned");
-        if (f.view().n_texts > 256u)
+        if (d.f.view().n_texts > 256u)
             gdx::fail(GDX_ERR_UNSUPPORTED, "gdx_compact_split_hits_dev: text ids as bytes need a collection of at most 256 texts");
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_compact_split(f.view(), static_cast<const uint32_t *>(d_compact), nq, static_cast<uint8_t *>(d_out_text_ids),
-                                  static_cast<int32_t *>(d_out_positions), as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.enter();
+        gdx::launch_compact_split(d.f.view(), static_cast<const uint32_t *>(d_compact), nq, static_cast<uint8_t *>(d_out_text_ids),
+                                  static_cast<int32_t *>(d_out_positions), d.st);
     });
 }
 
 int gdx_compact_exceptions_dev(const gdx_index_t *ix, const void *d_compact, uint64_t nq, void *d_out_queries,
                                uint64_t capacity, void *d_out_n, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         if (d_compact == nullptr || d_out_n == nullptr || (d_out_queries == nullptr && capacity != 0))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_compact_exceptions_dev: null buffer");
         if (reinterpret_cast<uintptr_t>(d_compact) % 16 != 0 || reinterpret_cast<uintptr_t>(d_out_n) % 8 != 0)
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_compact_exceptions_dev: d_compact must be 16-byte, d_out_n 8-byte aligned");
         if (nq > 0xffffffffull) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_compact_exceptions_dev: more than 2^32 - 1 queries");
-        DeviceGuard guard(f.config().device_id);
+        d.enter();
         gdx::launch_compact_exceptions(static_cast<const uint32_t *>(d_compact), nq, static_cast<uint32_t *>(d_out_queries),
-                                       capacity, static_cast<unsigned long long *>(d_out_n), as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+                                       capacity, static_cast<unsigned long long *>(d_out_n), d.st);
     });
 }
 
@@ -1129,8 +1133,7 @@ int gdx_wire_pack_dev(const gdx_index_t *ix, const void *d_compact, const void *
                       void *d_exc_queries, void *d_exc_counts, uint64_t exc_capacity, void *d_exc_text_ids, void *d_exc_positions,
                       uint64_t exc_hits_capacity, void *d_meta, void *d_workspace, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         if (!d_tile_found || !d_meta || !d_workspace || (nq != 0 && (!d_compact || !d_hit_offsets || !d_bitmap)) ||
             (found_capacity != 0 && !d_found_pos) || (exc_capacity != 0 && (!d_exc_queries || !d_exc_counts)) ||
             (exc_hits_capacity != 0 && (!d_exc_text_ids || !d_exc_positions || !d_hits)))
@@ -1141,16 +1144,14 @@ int gdx_wire_pack_dev(const gdx_index_t *ix, const void *d_compact, const void *
              reinterpret_cast<uintptr_t>(d_exc_counts) | reinterpret_cast<uintptr_t>(d_exc_positions) | reinterpret_cast<uintptr_t>(d_meta)) % 4 != 0)
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_wire_pack_dev: d_compact must be 16-byte, d_workspace 8-byte, the u32 / i32 arrays 4-byte aligned");
         if (nq > 0xffffffffull) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_wire_pack_dev: more than 2^32 - 1 queries");
-        if (f.view().n_texts > 256u) gdx::fail(GDX_ERR_UNSUPPORTED, "gdx_wire_pack_dev: text ids as bytes need a collection of at most 256 texts");
-        DeviceGuard guard(f.config().device_id);
+        if (d.f.view().n_texts > 256u) gdx::fail(GDX_ERR_UNSUPPORTED, "gdx_wire_pack_dev: text ids as bytes need a collection of at most 256 texts");
+        d.enter();
         gdx::launch_wire_pack(static_cast<const uint32_t *>(d_compact), d_hit_offsets, offsets_width == 32u,
                               static_cast<const gdx_hit32_t *>(d_hits), nq, static_cast<uint8_t *>(d_bitmap),
                               static_cast<uint32_t *>(d_tile_found), static_cast<uint32_t *>(d_found_pos), found_capacity,
                               static_cast<uint32_t *>(d_exc_queries), static_cast<uint32_t *>(d_exc_counts), exc_capacity,
                               static_cast<uint8_t *>(d_exc_text_ids), static_cast<int32_t *>(d_exc_positions), exc_hits_capacity,
-                              static_cast<uint32_t *>(d_meta), d_workspace, as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+                              static_cast<uint32_t *>(d_meta), d_workspace, d.st);
     });
 }
 
@@ -1158,8 +1159,7 @@ int gdx_wire_split_dev(const gdx_index_t *ix, const void *d_bitmap, const void *
                        uint64_t found_capacity, uint64_t nq, const void *d_exc_queries, const void *d_meta, uint64_t exc_capacity,
                        void *d_out_text_ids, void *d_out_positions, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         if (!d_tile_found || !d_meta || (nq != 0 && (!d_bitmap || !d_out_text_ids || !d_out_positions)) ||
             (found_capacity != 0 && !d_found_pos) || (exc_capacity != 0 && !d_exc_queries))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_wire_split_dev: null buffer");
@@ -1167,14 +1167,12 @@ int gdx_wire_split_dev(const gdx_index_t *ix, const void *d_bitmap, const void *
             (reinterpret_cast<uintptr_t>(d_tile_found) | reinterpret_cast<uintptr_t>(d_found_pos) | reinterpret_cast<uintptr_t>(d_exc_queries) |
              reinterpret_cast<uintptr_t>(d_meta)) % 4 != 0)
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_wire_split_dev: d_out_positions must be 16-byte, d_out_text_ids 8-byte, the u32 arrays 4-byte aligned");
-        if (f.view().n_texts > 256u) gdx::fail(GDX_ERR_UNSUPPORTED, "gdx_wire_split_dev: text ids as bytes need a collection of at most 256 texts");
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_wire_split(f.view(), static_cast<const uint8_t *>(d_bitmap), static_cast<const uint32_t *>(d_tile_found),
+        if (d.f.view().n_texts > 256u) gdx::fail(GDX_ERR_UNSUPPORTED, "gdx_wire_split_dev: text ids as bytes need a collection of at most 256 texts");
+        d.enter();
+        gdx::launch_wire_split(d.f.view(), static_cast<const uint8_t *>(d_bitmap), static_cast<const uint32_t *>(d_tile_found),
                                static_cast<const uint32_t *>(d_found_pos), found_capacity, nq, static_cast<const uint32_t *>(d_exc_queries),
                                static_cast<const uint32_t *>(d_meta), exc_capacity, static_cast<uint8_t *>(d_out_text_ids),
-                               static_cast<int32_t *>(d_out_positions), as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+                               static_cast<int32_t *>(d_out_positions), d.st);
     });
 }
 
@@ -1208,14 +1206,11 @@ int gdx_pack_queries_table(const uint8_t *io_to_dense, const uint8_t *qbuf, cons
 int gdx_pack_queries_dev(const gdx_index_t *ix, const void *d_qbuf, uint64_t n_symbols, void *d_packed, void *d_bad_flags,
                          void *d_bad_symbols, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_pack_queries(f.view(), static_cast<const uint8_t *>(d_qbuf), n_symbols, static_cast<uint8_t *>(d_packed),
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        d.enter();
+        gdx::launch_pack_queries(d.f.view(), static_cast<const uint8_t *>(d_qbuf), n_symbols, static_cast<uint8_t *>(d_packed),
                                  static_cast<uint8_t *>(d_bad_flags), static_cast<unsigned long long *>(d_bad_symbols),
-                                 as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+                                 d.st);
     });
 }
 
@@ -1237,55 +1232,51 @@ int gdx_cursors_for_many_queries_packed(const gdx_index_t *ix, const uint8_t *pa
     });
 }
 
-// mode 0 = intervals (start, end), 1 = counts, 2 = records
-static int packed_search_dev(const gdx_index_t *ix, const void *d_packed, const void *d_qoff, uint64_t nq, int what,
-                             void *d_a, void *d_b, void *d_status, void *stream)
+// the packed entries: a packed layout under the buffer's older name
+static gdx::SearchCall packed_query_side(const void *d_packed, const void *d_qoff, uint64_t nq)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        if ((reinterpret_cast<uintptr_t>(d_packed) & 1u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_packed must be 2-byte aligned");
-        DeviceGuard guard(f.config().device_id);
-        gdx::SearchCall c;
-        c.d_qbuf = static_cast<const uint8_t *>(d_packed);
-        c.d_qbeg = static_cast<const uint64_t *>(d_qoff);
-        c.d_qend = c.d_qbeg + 1;
-        c.nq = nq;
-        c.packed = true;
-        c.d_status = static_cast<uint8_t *>(d_status);
-        if (what == 0) {
-            c.d_start = static_cast<uint32_t *>(d_a);
-            c.d_end = static_cast<uint32_t *>(d_b);
-            c.mode = 0;
-        } else if (what == 1) {
-            c.d_count = static_cast<uint32_t *>(d_a);
-            c.mode = 1;
-        } else {
-            check_records(d_a);
-            c.d_rec = static_cast<uint4 *>(d_a);
-            c.mode = 1;
-        }
-        gdx::launch_search_call(f.view(), c, as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
-    });
+    aligned(d_packed, 1u, "d_packed must be 2-byte aligned");
+    gdx_query_layout_t l;
+    gdx_query_layout_init(&l);
+    l.packed = 1;
+    return query_side(d_packed, d_qoff, nq, &l);
 }
 
 int gdx_cursors_for_many_queries_packed_dev(const gdx_index_t *ix, const void *d_packed, const void *d_qoff, uint64_t nq,
                                             void *d_out_start, void *d_out_end, void *d_out_status, void *stream)
 {
-    return packed_search_dev(ix, d_packed, d_qoff, nq, 0, d_out_start, d_out_end, d_out_status, stream);
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::SearchCall c = packed_query_side(d_packed, d_qoff, nq);
+        c.d_start = u32(d_out_start);
+        c.d_end = u32(d_out_end);
+        c.d_status = static_cast<uint8_t *>(d_out_status);
+        c.mode = 0;
+        d.search(c);
+    });
 }
 
 int gdx_count_many_packed_dev(const gdx_index_t *ix, const void *d_packed, const void *d_qoff, uint64_t nq,
                               void *d_out_counts, void *d_out_status, void *stream)
 {
-    return packed_search_dev(ix, d_packed, d_qoff, nq, 1, d_out_counts, nullptr, d_out_status, stream);
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::SearchCall c = packed_query_side(d_packed, d_qoff, nq);
+        c.d_count = u32(d_out_counts);
+        c.d_status = static_cast<uint8_t *>(d_out_status);
+        c.mode = 1;
+        d.search(c);
+    });
 }
 
 int gdx_locate_many_search_packed_dev(const gdx_index_t *ix, const void *d_packed, const void *d_qoff, uint64_t nq,
                                       void *d_records, void *stream)
 {
-    return packed_search_dev(ix, d_packed, d_qoff, nq, 2, d_records, nullptr, nullptr, stream);
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::SearchCall c = packed_query_side(d_packed, d_qoff, nq);
+        check_records(d_records);
+        c.d_rec = static_cast<uint4 *>(d_records);
+        c.mode = 1;
+        d.search(c);
+    });
 }
 
 // ---- query layouts: packed and / or uniform batches through one description (gdx.h) ------------------------------
@@ -1297,59 +1288,15 @@ void gdx_query_layout_init(gdx_query_layout_t *layout)
     layout->struct_size = sizeof(*layout);
 }
 
-namespace {
-// fills the query side of a SearchCall from a layout (null = ASCII with offsets: the plain calls)
-void apply_layout(gdx::SearchCall &c, const void *d_qbuf, const void *d_qoff, uint64_t nq, const gdx_query_layout_t *layout)
-{
-    gdx_query_layout_t l;
-    gdx_query_layout_init(&l);
-    if (layout) {
-        if (layout->struct_size < 16 || layout->struct_size > sizeof(l)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_query_layout_t.struct_size");
-        std::memcpy(&l, layout, layout->struct_size);
-    }
-    if (l.packed != 0 && l.packed != 1) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_query_layout_t.packed must be 0 or 1");
-    if (l.uniform_len >= (1ull << 21)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_query_layout_t.uniform_len must be below 2^21");
-    const uintptr_t align = l.packed ? 1u : 7u;
-    if ((reinterpret_cast<uintptr_t>(d_qbuf) & align) != 0)
-        gdx::fail(GDX_ERR_INVALID_ARGUMENT, l.packed ? "d_qbuf (packed) must be 2-byte aligned" : "d_qbuf must be 8-byte aligned");
-    if (l.uniform_len == 0 && !d_qoff && nq != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qoff is null and the layout is not uniform");
-    c.d_qbuf = static_cast<const uint8_t *>(d_qbuf);
-    c.nq = nq;
-    c.packed = l.packed != 0;
-    c.uniform_len = static_cast<uint32_t>(l.uniform_len);
-    if (l.uniform_len == 0) {
-        c.d_qbeg = static_cast<const uint64_t *>(d_qoff);
-        c.d_qend = c.d_qbeg + 1;
-    }
-}
-}  // namespace
-
 // host-pointer calls on a batch in a layout (the chunked pipeline of host_api.hip)
-namespace {
-void host_layout(const gdx_query_layout_t *layout, bool &packed, uint64_t &uniform_len)
-{
-    gdx_query_layout_t l;
-    gdx_query_layout_init(&l);
-    if (layout) {
-        if (layout->struct_size < 16 || layout->struct_size > sizeof(l)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_query_layout_t.struct_size");
-        std::memcpy(&l, layout, layout->struct_size);
-    }
-    if (l.packed != 0 && l.packed != 1) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_query_layout_t.packed must be 0 or 1");
-    if (l.uniform_len >= (1ull << 21)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_query_layout_t.uniform_len must be below 2^21");
-    packed = l.packed != 0;
-    uniform_len = l.uniform_len;
-}
-}  // namespace
 
 int gdx_count_many_layout(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq,
                           const gdx_query_layout_t *layout, uint64_t *out_counts, uint8_t *out_status)
 {
     return guarded([&] {
-        bool packed;
-        uint64_t ulen;
-        host_layout(layout, packed, ulen);
+        const gdx_query_layout_t l = parse_layout(layout);
         if (!out_counts && nq != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "out_counts is null");
-        return deref(ix).cursors_for_many_queries(qbuf, qoff, nq, nullptr, nullptr, out_counts, out_status, packed, ulen);
+        return deref(ix).cursors_for_many_queries(qbuf, qoff, nq, nullptr, nullptr, out_counts, out_status, l.packed != 0, l.uniform_len);
     });
 }
 
@@ -1358,11 +1305,9 @@ int gdx_cursors_for_many_queries_layout(const gdx_index_t *ix, const uint8_t *qb
                                         uint8_t *out_status)
 {
     return guarded([&] {
-        bool packed;
-        uint64_t ulen;
-        host_layout(layout, packed, ulen);
+        const gdx_query_layout_t l = parse_layout(layout);
         if ((!out_start || !out_end) && nq != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "out_start / out_end is null");
-        return deref(ix).cursors_for_many_queries(qbuf, qoff, nq, out_start, out_end, nullptr, out_status, packed, ulen);
+        return deref(ix).cursors_for_many_queries(qbuf, qoff, nq, out_start, out_end, nullptr, out_status, l.packed != 0, l.uniform_len);
     });
 }
 
@@ -1371,10 +1316,8 @@ int gdx_locate_many_alloc_layout(const gdx_index_t *ix, const uint8_t *qbuf, con
                                  uint64_t *out_total, uint8_t *out_status)
 {
     return guarded([&] {
-        bool packed;
-        uint64_t ulen;
-        host_layout(layout, packed, ulen);
-        return deref(ix).locate_many_alloc(qbuf, qoff, nq, out_hit_offsets, out_hits, out_total, out_status, packed, ulen);
+        const gdx_query_layout_t l = parse_layout(layout);
+        return deref(ix).locate_many_alloc(qbuf, qoff, nq, out_hit_offsets, out_hits, out_total, out_status, l.packed != 0, l.uniform_len);
     });
 }
 
@@ -1382,10 +1325,8 @@ int gdx_locate_many_alloc_layout32(const gdx_index_t *ix, const uint8_t *qbuf, c
                                    const gdx_query_layout_t *layout, gdx_hits32_t *out_results, uint8_t *out_status)
 {
     return guarded([&] {
-        bool packed;
-        uint64_t ulen;
-        host_layout(layout, packed, ulen);
-        return deref(ix).locate_many_alloc32(qbuf, qoff, nq, out_results, out_status, packed, ulen);
+        const gdx_query_layout_t l = parse_layout(layout);
+        return deref(ix).locate_many_alloc32(qbuf, qoff, nq, out_results, out_status, l.packed != 0, l.uniform_len);
     });
 }
 
@@ -1395,19 +1336,14 @@ void gdx_release_cached_hits(void) { gdx::release_cached_hits(); }
 int gdx_locate_many_search_compact_layout_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
                                               const gdx_query_layout_t *layout, void *d_records, void *d_compact, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         check_records(d_records);
         if (!d_compact && nq != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_compact is null");
-        DeviceGuard guard(f.config().device_id);
-        gdx::SearchCall c;
-        apply_layout(c, d_qbuf, d_qoff, nq, layout);
+        gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, layout);
         c.d_rec = static_cast<uint4 *>(d_records);
-        c.d_compact = static_cast<uint32_t *>(d_compact);
+        c.d_compact = u32(d_compact);
         c.mode = 1;
-        gdx::launch_search_call(f.view(), c, as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.search(c);
     });
 }
 
@@ -1415,33 +1351,29 @@ int gdx_locate_many_search_totals_compact_layout_dev(const gdx_index_t *ix, cons
                                                      const gdx_query_layout_t *layout, uint32_t max_hits, void *d_records,
                                                      void *d_compact, void *d_scan_workspace, void *d_totals, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         check_records(d_records);
         if (!d_compact && nq != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_compact is null");
         if (!d_scan_workspace || !d_totals) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_locate_many_search_totals_compact_layout_dev: null argument");
-        DeviceGuard guard(f.config().device_id);
+        d.enter();
         unsigned long long *totals = static_cast<unsigned long long *>(d_totals);
-        GDX_HIP(hipMemsetAsync(totals, 0, 2 * sizeof(unsigned long long), as_stream(stream)));
-        gdx::SearchCall c;
-        apply_layout(c, d_qbuf, d_qoff, nq, layout);
+        GDX_HIP(hipMemsetAsync(totals, 0, 2 * sizeof(unsigned long long), d.st));
+        gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, layout);
         c.d_rec = static_cast<uint4 *>(d_records);
-        c.d_compact = static_cast<uint32_t *>(d_compact);
+        c.d_compact = u32(d_compact);
         c.mode = 1;
         bool folded = false;
         c.d_tile_sums = static_cast<unsigned long long *>(d_scan_workspace);
         c.d_tile_rest = totals + 1;
         c.tile_max_hits = max_hits;
         c.tile_sums_done = &folded;
-        gdx::launch_search_call(f.view(), c, as_stream(stream), f.query_options());
+        d.search(c);
         GDX_HIP(hipGetLastError());
         if (folded)  // the search counted the hits per tile itself: only the scan of the tile sums is left
-            gdx::launch_scan_totals_finish(d_scan_workspace, nq, totals, as_stream(stream));
+            gdx::launch_scan_totals_finish(d_scan_workspace, nq, totals, d.st);
         else
-            gdx::launch_scan_totals(static_cast<const uint4 *>(d_records), static_cast<const uint32_t *>(d_compact), nq, max_hits,
-                                    false, d_scan_workspace, totals, as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+            gdx::launch_scan_totals(static_cast<const uint4 *>(d_records), u32(d_compact), nq, max_hits, false, d_scan_workspace, totals,
+                                    d.st);
     });
 }
 
@@ -1451,20 +1383,18 @@ int gdx_locate_many_step_compact_layout_dev(const gdx_index_t *ix, const void *d
                                             void *d_hits, uint64_t hits_capacity, void *d_workspace, void *event_after_search,
                                             void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         check_records(d_records);
         if (!d_scan_workspace || !d_totals || !d_hit_offsets || (hits_capacity != 0 && (!d_hits || !d_workspace)))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_locate_many_step_compact_layout_dev: null argument");
         if (offsets_width != 32u && offsets_width != 64u) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "offsets_width must be 32 or 64");
         const bool narrow = offsets_width == 32u;
-        if (narrow && hits_capacity >= (1ull << 32)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "32-bit hit offsets need fewer than 2^32 hits");
-        if ((reinterpret_cast<uintptr_t>(d_totals) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_totals must be 8-byte aligned");
-        DeviceGuard guard(f.config().device_id);
+        check_narrow_offsets(narrow, hits_capacity);
+        aligned(d_totals, 7u, "d_totals must be 8-byte aligned");
         gdx::LocateStep step;
-        apply_layout(step.call, d_qbuf, d_qoff, nq, layout);
+        step.call = query_side(d_qbuf, d_qoff, nq, layout);
         step.call.d_rec = static_cast<uint4 *>(d_records);
-        step.call.d_compact = static_cast<uint32_t *>(d_compact);
+        step.call.d_compact = u32(d_compact);
         step.max_hits = max_hits;
         step.d_scan_workspace = d_scan_workspace;
         step.d_totals = static_cast<unsigned long long *>(d_totals);
@@ -1474,43 +1404,32 @@ int gdx_locate_many_step_compact_layout_dev(const gdx_index_t *ix, const void *d
         step.hits_capacity = hits_capacity;
         step.d_workspace = d_workspace;
         step.event_after_search = static_cast<hipEvent_t>(event_after_search);
-        gdx::launch_locate_step(f.view(), step, as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.enter();
+        gdx::launch_locate_step(d.f.view(), step, d.st, d.f.query_options());
     });
 }
 
 int gdx_locate_many_search_layout_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
                                       const gdx_query_layout_t *layout, void *d_records, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         check_records(d_records);
-        DeviceGuard guard(f.config().device_id);
-        gdx::SearchCall c;
-        apply_layout(c, d_qbuf, d_qoff, nq, layout);
+        gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, layout);
         c.d_rec = static_cast<uint4 *>(d_records);
         c.mode = 1;
-        gdx::launch_search_call(f.view(), c, as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.search(c);
     });
 }
 
 int gdx_count_many_layout_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
                               const gdx_query_layout_t *layout, void *d_out_counts, void *d_out_status, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        DeviceGuard guard(f.config().device_id);
-        gdx::SearchCall c;
-        apply_layout(c, d_qbuf, d_qoff, nq, layout);
-        c.d_count = static_cast<uint32_t *>(d_out_counts);
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, layout);  // counts only: the search may end with the lazy tail (mode 1)
+        c.d_count = u32(d_out_counts);
         c.d_status = static_cast<uint8_t *>(d_out_status);
         c.mode = 1;
-        gdx::launch_search_call(f.view(), c, as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.search(c);
     });
 }
 
@@ -1518,18 +1437,48 @@ int gdx_cursors_for_many_queries_layout_dev(const gdx_index_t *ix, const void *d
                                             const gdx_query_layout_t *layout, void *d_out_start, void *d_out_end,
                                             void *d_out_status, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        DeviceGuard guard(f.config().device_id);
-        gdx::SearchCall c;
-        apply_layout(c, d_qbuf, d_qoff, nq, layout);
-        c.d_start = static_cast<uint32_t *>(d_out_start);
-        c.d_end = static_cast<uint32_t *>(d_out_end);
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, layout);
+        c.d_start = u32(d_out_start);
+        c.d_end = u32(d_out_end);
         c.d_status = static_cast<uint8_t *>(d_out_status);
         c.mode = 0;
-        gdx::launch_search_call(f.view(), c, as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.search(c);
+    });
+}
+
+// the two cursor extensions by strings: query i of cursor i is d_qbuf[d_qbeg[i] .. d_qend[i]), whole (chunk_symbols == 0) or
+// its chunk chunk_index.  `pointers`: the arrays a call with cursors cannot do without.
+static int cursor_extend_strings_dev(const gdx_index_t *ix, void *d_start, void *d_end, const void *d_qbuf, const void *d_qbeg,
+                                     const void *d_qend, uint64_t m, bool pointers, const uint32_t *chunk_symbols, uint32_t chunk_index,
+                                     void *d_status, const void *d_active_in, const void *d_n_active_in, void *d_active_out,
+                                     void *d_n_active_out, void *stream)
+{
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        check_qbuf(d_qbuf);
+        if (m && !pointers) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+        if (chunk_symbols && *chunk_symbols == 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "chunk_symbols must be positive");
+        if ((d_active_out == nullptr) != (d_n_active_out == nullptr) || (d_active_in != nullptr && d_n_active_in == nullptr))
+            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "active lists need their counters");
+        if (m >= 0xffffffffull) gdx::fail(GDX_ERR_UNSUPPORTED, "more than 2^32-2 cursors in one call");
+        d.enter();
+        if (d_n_active_out) GDX_HIP(hipMemsetAsync(d_n_active_out, 0, sizeof(uint32_t), d.st));
+        gdx::SearchCall c;
+        c.d_qbuf = static_cast<const uint8_t *>(d_qbuf);
+        c.d_qbeg = static_cast<const uint64_t *>(d_qbeg);
+        c.d_qend = static_cast<const uint64_t *>(d_qend);
+        c.nq = m;
+        c.d_start = u32(d_start);
+        c.d_end = u32(d_end);
+        c.d_status = static_cast<uint8_t *>(d_status);
+        c.mode = 2;
+        c.cursors.active_in = u32(d_active_in);
+        c.cursors.n_active_in = u32(d_n_active_in);
+        c.cursors.active_out = u32(d_active_out);
+        c.cursors.n_active_out = u32(d_n_active_out);
+        if (chunk_symbols) c.cursors.chunk_symbols = *chunk_symbols;
+        c.cursors.chunk_index = chunk_index;
+        d.search(c);
     });
 }
 
@@ -1538,32 +1487,8 @@ int gdx_cursor_extend_front_strings_dev(const gdx_index_t *ix, void *d_start, vo
                                         const void *d_active_in, const void *d_n_active_in, void *d_active_out,
                                         void *d_n_active_out, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        if ((reinterpret_cast<uintptr_t>(d_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf must be 8-byte aligned");
-        if (m && (!d_start || !d_end || !d_qbeg || !d_qend)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-        if ((d_active_out == nullptr) != (d_n_active_out == nullptr) || (d_active_in != nullptr && d_n_active_in == nullptr))
-            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "active lists need their counters");
-        if (m >= 0xffffffffull) gdx::fail(GDX_ERR_UNSUPPORTED, "more than 2^32-2 cursors in one call");
-        DeviceGuard guard(f.config().device_id);
-        if (d_n_active_out) GDX_HIP(hipMemsetAsync(d_n_active_out, 0, sizeof(uint32_t), as_stream(stream)));
-        gdx::SearchCall c;
-        c.d_qbuf = static_cast<const uint8_t *>(d_qbuf);
-        c.d_qbeg = static_cast<const uint64_t *>(d_qbeg);
-        c.d_qend = static_cast<const uint64_t *>(d_qend);
-        c.nq = m;
-        c.d_start = static_cast<uint32_t *>(d_start);
-        c.d_end = static_cast<uint32_t *>(d_end);
-        c.d_status = static_cast<uint8_t *>(d_status);
-        c.mode = 2;
-        c.cursors.active_in = static_cast<const uint32_t *>(d_active_in);
-        c.cursors.n_active_in = static_cast<const uint32_t *>(d_n_active_in);
-        c.cursors.active_out = static_cast<uint32_t *>(d_active_out);
-        c.cursors.n_active_out = static_cast<uint32_t *>(d_n_active_out);
-        gdx::launch_search_call(f.view(), c, as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
-    });
+    return cursor_extend_strings_dev(ix, d_start, d_end, d_qbuf, d_qbeg, d_qend, m, d_start && d_end && d_qbeg && d_qend, nullptr, 0,
+                                     d_status, d_active_in, d_n_active_in, d_active_out, d_n_active_out, stream);
 }
 
 int gdx_cursor_extend_front_chunk_dev(const gdx_index_t *ix, void *d_start, void *d_end, const void *d_qbuf,
@@ -1571,35 +1496,9 @@ int gdx_cursor_extend_front_chunk_dev(const gdx_index_t *ix, void *d_start, void
                                       void *d_status, const void *d_active_in, const void *d_n_active_in,
                                       void *d_active_out, void *d_n_active_out, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        if ((reinterpret_cast<uintptr_t>(d_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf must be 8-byte aligned");
-        if (m && (!d_start || !d_end || !d_qoff)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-        if (chunk_symbols == 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "chunk_symbols must be positive");
-        if ((d_active_out == nullptr) != (d_n_active_out == nullptr) || (d_active_in != nullptr && d_n_active_in == nullptr))
-            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "active lists need their counters");
-        if (m >= 0xffffffffull) gdx::fail(GDX_ERR_UNSUPPORTED, "more than 2^32-2 cursors in one call");
-        DeviceGuard guard(f.config().device_id);
-        if (d_n_active_out) GDX_HIP(hipMemsetAsync(d_n_active_out, 0, sizeof(uint32_t), as_stream(stream)));
-        gdx::SearchCall c;
-        c.d_qbuf = static_cast<const uint8_t *>(d_qbuf);
-        c.d_qbeg = static_cast<const uint64_t *>(d_qoff);
-        c.d_qend = static_cast<const uint64_t *>(d_qoff) + 1;
-        c.nq = m;
-        c.d_start = static_cast<uint32_t *>(d_start);
-        c.d_end = static_cast<uint32_t *>(d_end);
-        c.d_status = static_cast<uint8_t *>(d_status);
-        c.mode = 2;
-        c.cursors.active_in = static_cast<const uint32_t *>(d_active_in);
-        c.cursors.n_active_in = static_cast<const uint32_t *>(d_n_active_in);
-        c.cursors.active_out = static_cast<uint32_t *>(d_active_out);
-        c.cursors.n_active_out = static_cast<uint32_t *>(d_n_active_out);
-        c.cursors.chunk_symbols = chunk_symbols;
-        c.cursors.chunk_index = chunk_index;
-        gdx::launch_search_call(f.view(), c, as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
-    });
+    return cursor_extend_strings_dev(ix, d_start, d_end, d_qbuf, d_qoff, static_cast<const uint64_t *>(d_qoff) + 1, m,
+                                     d_start && d_end && d_qoff, &chunk_symbols, chunk_index, d_status, d_active_in, d_n_active_in,
+                                     d_active_out, d_n_active_out, stream);
 }
 
 int gdx_cursor_extend_front_strings(const gdx_index_t *ix, uint64_t *start, uint64_t *end, const uint8_t *qbuf,
@@ -1622,22 +1521,19 @@ int gdx_suffix_segments_many_dev(const gdx_index_t *ix, const void *d_qbuf, cons
                                  uint32_t flags, void *d_n_segments, void *d_remaining, void *d_length, void *d_start, void *d_end,
                                  void *d_status, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         if (max_segments == 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "max_segments must be at least 1");
         if ((flags & ~static_cast<uint32_t>(GDX_SEGMENTS_LF_ONLY)) != 0u) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "unknown bit in flags");
-        if (nq == 0) return (int)GDX_OK;
-        if ((reinterpret_cast<uintptr_t>(d_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf must be 8-byte aligned");
+        if (nq == 0) return;
+        check_qbuf(d_qbuf);
         if (!d_qbuf || !d_qoff || !d_n_segments || !d_remaining || !d_length || !d_start || !d_end)
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_suffix_segments(f.view(), static_cast<const uint8_t *>(d_qbuf), static_cast<const uint64_t *>(d_qoff), nq,
+        d.enter();
+        gdx::launch_suffix_segments(d.f.view(), static_cast<const uint8_t *>(d_qbuf), static_cast<const uint64_t *>(d_qoff), nq,
                                     max_segments, (flags & GDX_SEGMENTS_LF_ONLY) != 0u, static_cast<uint32_t *>(d_n_segments),
                                     static_cast<uint32_t *>(d_remaining), static_cast<uint32_t *>(d_length),
                                     static_cast<uint32_t *>(d_start), static_cast<uint32_t *>(d_end),
-                                    static_cast<uint8_t *>(d_status), as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+                                    static_cast<uint8_t *>(d_status), d.st, d.f.query_options());
     });
 }
 
@@ -1656,23 +1552,19 @@ int gdx_smems_many_dev(const gdx_index_t *ix, const gdx_index_t *ix_reversed, co
                        uint32_t max_smems, uint32_t min_length, void *d_n_smems, void *d_remaining, void *d_begin, void *d_length,
                        void *d_start, void *d_end, void *d_status, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         const gdx::FmIndex &r = deref(ix_reversed);
         if (max_smems == 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "max_smems must be at least 1");
         if (min_length == 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "min_length must be at least 1");
-        f.check_companion(r);
-        if (nq == 0) return (int)GDX_OK;
-        if ((reinterpret_cast<uintptr_t>(d_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_qbuf must be 8-byte aligned");
+        d.f.check_companion(r);
+        if (nq == 0) return;
+        check_qbuf(d_qbuf);
         if (!d_qbuf || !d_qoff || !d_n_smems || !d_remaining || !d_begin || !d_length || !d_start || !d_end)
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_smems(f.view(), r.view(), static_cast<const uint8_t *>(d_qbuf), static_cast<const uint64_t *>(d_qoff), nq,
-                          max_smems, min_length, static_cast<uint32_t *>(d_n_smems), static_cast<uint32_t *>(d_remaining),
-                          static_cast<uint32_t *>(d_begin), static_cast<uint32_t *>(d_length), static_cast<uint32_t *>(d_start),
-                          static_cast<uint32_t *>(d_end), static_cast<uint8_t *>(d_status), as_stream(stream), f.query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.enter();
+        gdx::launch_smems(d.f.view(), r.view(), static_cast<const uint8_t *>(d_qbuf), static_cast<const uint64_t *>(d_qoff), nq, max_smems,
+                          min_length, u32(d_n_smems), u32(d_remaining), u32(d_begin), u32(d_length), u32(d_start), u32(d_end),
+                          static_cast<uint8_t *>(d_status), d.st, d.f.query_options());
     });
 }
 
@@ -1692,20 +1584,19 @@ int gdx_strands_expand_dev(const gdx_index_t *ix, const void *d_qbuf, const void
                            const gdx_query_layout_t *layout, uint64_t total_symbols, const uint8_t *complement, uint32_t mode,
                            void *d_out_qbuf, void *d_out_qoff, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         if (mode != GDX_STRANDS_REVERSE && mode != GDX_STRANDS_BOTH)
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "mode must be GDX_STRANDS_REVERSE or GDX_STRANDS_BOTH");
-        gdx::SearchCall c;  // (the layout's checks: struct size, alignment of d_qbuf, offsets of a batch that is not uniform)
-        apply_layout(c, d_qbuf, d_qoff, nq, layout);
-        if (c.packed && (f.view().layout != 0 || f.view().n_searchable < 4))
+        // (the layout's checks: struct size, alignment of d_qbuf, offsets of a batch that is not uniform)
+        const gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, layout);
+        if (c.packed && (d.f.view().layout != 0 || d.f.view().n_searchable < 4))
             gdx::fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
         uint8_t stock[256];
         if (!complement) {
             gdx::dna_complement_table(stock);
             complement = stock;
         }
-        gdx::check_complement(f.config().io_to_dense, complement, c.packed);
+        gdx::check_complement(d.f.config().io_to_dense, complement, c.packed);
         const bool writes_offsets = mode == GDX_STRANDS_BOTH && c.uniform_len == 0;
         if (!d_out_qbuf || (writes_offsets && !d_out_qoff)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null output");
         if ((reinterpret_cast<uintptr_t>(d_out_qbuf) & 7u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_out_qbuf must be 8-byte aligned");
@@ -1717,11 +1608,9 @@ int gdx_strands_expand_dev(const gdx_index_t *ix, const void *d_qbuf, const void
         const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_qbuf), out0 = reinterpret_cast<uintptr_t>(d_out_qbuf);
         if (nq != 0 && in0 < out0 + out_bytes && out0 < in0 + gdx::strands_out_bytes(total_symbols, c.packed, 1))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_out_qbuf overlaps d_qbuf");
-        DeviceGuard guard(f.config().device_id);
+        d.enter();
         gdx::launch_strands_expand(c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, total_symbols, complement, mode, d_out_qbuf,
-                                   static_cast<uint64_t *>(d_out_qoff), as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+                                   static_cast<uint64_t *>(d_out_qoff), d.st);
     });
 }
 
@@ -1743,9 +1632,6 @@ int gdx_locate_many_alloc_strands(const gdx_index_t *ix, const uint8_t *qbuf, co
 
 // ---- Hamming verification of located seeds (hamming.hip) --------------------------------------------------------
 
-static uint32_t *u32(void *p) { return static_cast<uint32_t *>(p); }
-static const uint32_t *u32(const void *p) { return static_cast<const uint32_t *>(p); }
-
 // what the three verify _dev entries refuse once m != 0: a null candidate array, a null d_out (the output the entry has not
 // looked at itself) and a null d_qbuf of a batch with queries
 static void check_verify_pointers(const void *d_qbuf, uint64_t nq, const void *d_cand_query, const void *d_cand_begin,
@@ -1759,18 +1645,15 @@ int gdx_hamming_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *
                          const void *d_cand_query, const void *d_cand_begin, const void *d_cand_hits, uint64_t m,
                          uint32_t max_mismatches, void *d_out, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        gdx::SearchCall c;  // (the layout's checks: struct size, alignment of d_qbuf, offsets of a batch that is not uniform)
-        apply_layout(c, d_qbuf, d_qoff, nq, layout);
-        f.check_hamming(c.packed, max_mismatches);
-        if (m == 0) return (int)GDX_OK;
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        // (the layout's checks: struct size, alignment of d_qbuf, offsets of a batch that is not uniform)
+        const gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, layout);
+        d.f.check_hamming(c.packed, max_mismatches);
+        if (m == 0) return;
         check_verify_pointers(d_qbuf, nq, d_cand_query, d_cand_begin, d_cand_hits, d_out);
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_hamming(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, u32(d_cand_query), u32(d_cand_begin),
-                            static_cast<const gdx_hit32_t *>(d_cand_hits), m, max_mismatches, u32(d_out), as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.enter();
+        gdx::launch_hamming(d.f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, u32(d_cand_query), u32(d_cand_begin),
+                            static_cast<const gdx_hit32_t *>(d_cand_hits), m, max_mismatches, u32(d_out), d.st);
     });
 }
 
@@ -1786,19 +1669,16 @@ int gdx_edit_distance_many_dev(const gdx_index_t *ix, const void *d_qbuf, const 
                                const gdx_query_layout_t *layout, const void *d_cand_query, const void *d_cand_begin,
                                const void *d_cand_hits, uint64_t m, uint32_t max_edits, void *d_out_dist, void *d_out_end, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        gdx::SearchCall c;  // (the layout's checks: struct size, alignment of d_qbuf, offsets of a batch that is not uniform)
-        apply_layout(c, d_qbuf, d_qoff, nq, layout);
-        f.check_edit_distance(c.packed, max_edits);
-        if (m == 0) return (int)GDX_OK;
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        // (the layout's checks: struct size, alignment of d_qbuf, offsets of a batch that is not uniform)
+        const gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, layout);
+        d.f.check_edit_distance(c.packed, max_edits);
+        if (m == 0) return;
         check_verify_pointers(d_qbuf, nq, d_cand_query, d_cand_begin, d_cand_hits, d_out_dist);
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_edit_distance(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, u32(d_cand_query), u32(d_cand_begin),
+        d.enter();
+        gdx::launch_edit_distance(d.f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, u32(d_cand_query), u32(d_cand_begin),
                                   static_cast<const gdx_hit32_t *>(d_cand_hits), m, max_edits, u32(d_out_dist), u32(d_out_end),
-                                  as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+                                  d.st);
     });
 }
 
@@ -1818,17 +1698,16 @@ int gdx_align_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_
                        void *d_out_dist, void *d_out_begin, void *d_out_end, void *d_out_n_cigar, void *d_out_cigar,
                        void *d_workspace, uint64_t workspace_bytes, uint64_t *out_workspace_bytes, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         gdx::SearchCall c;
         if (!d_workspace) {  // the size query: of the batch only the layout counts, no device pointer is looked at
-            apply_layout(c, nullptr, nullptr, 0, layout);
-            f.check_align(c.packed, max_edits);
+            c = query_side(nullptr, nullptr, 0, layout);
+            d.f.check_align(c.packed, max_edits);
             if (out_workspace_bytes) gdx::align_workspace_bytes(c.uniform_len, m, max_edits, out_workspace_bytes);
-            return (int)GDX_OK;
+            return;
         }
-        apply_layout(c, d_qbuf, d_qoff, nq, layout);
-        f.check_align(c.packed, max_edits);
+        c = query_side(d_qbuf, d_qoff, nq, layout);
+        d.f.check_align(c.packed, max_edits);
         uint64_t need[2];
         gdx::align_workspace_bytes(c.uniform_len, m, max_edits, need);
         if (workspace_bytes < need[0])
@@ -1836,14 +1715,12 @@ int gdx_align_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_
                       (unsigned long long)need[0]);
         if ((reinterpret_cast<uintptr_t>(d_workspace) & 15u) != 0) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "d_workspace must be 16-byte aligned");
         if (!d_out_dist || !d_out_begin || !d_out_end || !d_out_n_cigar || !d_out_cigar) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null output");
-        if (m == 0) return (int)GDX_OK;
+        if (m == 0) return;
         check_verify_pointers(d_qbuf, nq, d_cand_query, d_cand_begin, d_cand_hits, d_out_dist);  // (the outputs: checked above)
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_align(f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, u32(d_cand_query), u32(d_cand_begin),
+        d.enter();
+        gdx::launch_align(d.f.view(), c.d_qbuf, c.d_qbeg, nq, c.packed, c.uniform_len, u32(d_cand_query), u32(d_cand_begin),
                           static_cast<const gdx_hit32_t *>(d_cand_hits), m, max_edits, u32(d_out_dist), u32(d_out_begin), u32(d_out_end),
-                          u32(d_out_n_cigar), u32(d_out_cigar), d_workspace, workspace_bytes, as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+                          u32(d_out_n_cigar), u32(d_out_cigar), d_workspace, workspace_bytes, d.st);
     });
 }
 
@@ -1865,21 +1742,18 @@ int gdx_seed_candidates_many_dev(const gdx_index_t *ix, uint64_t nq, uint32_t ma
                                  void *d_cand_query, void *d_cand_begin, void *d_cand_hits, void *d_cand_weight, void *d_status,
                                  void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        f.check_seed_candidates(max_seeds, max_occ, max_candidates);
-        if (nq == 0) return (int)GDX_OK;
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        d.f.check_seed_candidates(max_seeds, max_occ, max_candidates);
+        if (nq == 0) return;
         if (nq >= 0xffffffffull) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "more than 2^32 - 2 queries (cand_query is 32 bits wide)");
         if (gdx::any_null({d_n_seeds, d_begin, d_length, d_start, d_end, d_n_candidates, d_n_groups, d_n_skipped, d_cand_query, d_cand_begin,
                       d_cand_hits, d_cand_weight}))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_seed_candidates(f.view(), nq, max_seeds, u32(d_n_seeds), u32(d_begin), u32(d_length), u32(d_start), u32(d_end),
+        d.enter();
+        gdx::launch_seed_candidates(d.f.view(), nq, max_seeds, u32(d_n_seeds), u32(d_begin), u32(d_length), u32(d_start), u32(d_end),
                                     max_occ, band, max_candidates, u32(d_n_candidates), u32(d_n_groups), u32(d_n_skipped),
                                     u32(d_cand_query), u32(d_cand_begin), static_cast<gdx_hit32_t *>(d_cand_hits), u32(d_cand_weight),
-                                    static_cast<uint8_t *>(d_status), as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+                                    static_cast<uint8_t *>(d_status), d.st);
     });
 }
 
@@ -1911,20 +1785,17 @@ int gdx_best_hits_many_dev(const gdx_index_t *ix, uint64_t n_groups, uint32_t gr
                            void *d_best_slot, void *d_best_dist, void *d_sub_dist, void *d_n_live, void *d_n_best, void *d_mapq,
                            void *d_win_query, void *d_win_begin, void *d_win_hits, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        f.check_best_hits(n_groups, group_slots, max_dist);
-        if (n_groups == 0) return (int)GDX_OK;
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        d.f.check_best_hits(n_groups, group_slots, max_dist);
+        if (n_groups == 0) return;
         if (gdx::any_null({d_cand_query, d_cand_begin, d_cand_hits, d_dist, d_best_slot, d_best_dist, d_sub_dist, d_n_live, d_n_best, d_mapq,
                       d_win_query, d_win_begin, d_win_hits}))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-        DeviceGuard guard(f.config().device_id);
+        d.enter();
         const gdx::BestArgs a = {
             slot_args(d_cand_query, d_cand_begin, d_cand_hits, d_dist, d_end, max_dist, d_win_query, d_win_begin, d_win_hits), n_groups,
             group_slots, u32(d_best_slot), u32(d_best_dist), u32(d_sub_dist), u32(d_n_live), u32(d_n_best), u32(d_mapq)};
-        gdx::launch_best_hits(a, as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        gdx::launch_best_hits(a, d.st);
     });
 }
 
@@ -1949,21 +1820,18 @@ int gdx_pair_hits_many_dev(const gdx_index_t *ix, uint64_t n_pairs, uint32_t mat
                            void *d_sub_dist, void *d_mapq, void *d_pair_span, void *d_mate_slot, void *d_mate_dist, void *d_win_query,
                            void *d_win_begin, void *d_win_hits, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        f.check_pair_hits(n_pairs, mate_slots, max_dist, min_insert, max_insert);
-        if (n_pairs == 0) return (int)GDX_OK;
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        d.f.check_pair_hits(n_pairs, mate_slots, max_dist, min_insert, max_insert);
+        if (n_pairs == 0) return;
         if (gdx::any_null({d_cand_query, d_cand_begin, d_cand_hits, d_dist, d_n_proper, d_n_best, d_pair_dist, d_sub_dist, d_mapq, d_pair_span,
                       d_mate_slot, d_mate_dist, d_win_query, d_win_begin, d_win_hits}))
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
-        DeviceGuard guard(f.config().device_id);
+        d.enter();
         const gdx::PairArgs a = {
             slot_args(d_cand_query, d_cand_begin, d_cand_hits, d_dist, d_end, max_dist, d_win_query, d_win_begin, d_win_hits), n_pairs,
             mate_slots, min_insert, max_insert, u32(d_n_proper), u32(d_n_best), u32(d_pair_dist), u32(d_sub_dist), u32(d_mapq),
             u32(d_pair_span), u32(d_mate_slot), u32(d_mate_dist)};
-        gdx::launch_pair_hits(a, as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        gdx::launch_pair_hits(a, d.st);
     });
 }
 
@@ -1984,15 +1852,12 @@ int gdx_pair_hits_many(const gdx_index_t *ix, uint64_t n_pairs, uint32_t mate_sl
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        DeviceGuard guard(f.config().device_id);
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        d.enter();
         uint32_t *d_err = static_cast<uint32_t *>(d_error);
-        if (!d_err) d_err = static_cast<uint32_t *>(gdx::stream_scratch(as_stream(stream), 9, sizeof(uint32_t)));
-        gdx::launch_rank_many(f.view(), static_cast<const uint8_t *>(d_symbols), static_cast<const uint32_t *>(d_idx),
-                              m, static_cast<uint32_t *>(d_out), d_err, as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        if (!d_err) d_err = static_cast<uint32_t *>(gdx::stream_scratch(d.st, 9, sizeof(uint32_t)));
+        gdx::launch_rank_many(d.f.view(), static_cast<const uint8_t *>(d_symbols), static_cast<const uint32_t *>(d_idx),
+                              m, static_cast<uint32_t *>(d_out), d_err, d.st);
     });
 }
 
@@ -2064,27 +1929,20 @@ int gdx_bench_random_gather(const void *d_src, uint64_t n_lines, uint32_t line_b
 int gdx_search_step_stats_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
                               void *d_steps, void *stream)
 {
-    return guarded([&] {
-        DeviceGuard guard(deref(ix).config().device_id);
-        gdx::launch_search(deref(ix).view(), static_cast<const uint8_t *>(d_qbuf),
-                           static_cast<const uint64_t *>(d_qoff), nq, nullptr, nullptr, nullptr, nullptr,
-                           as_stream(stream), static_cast<unsigned long long *>(d_steps), nullptr,
-                           deref(ix).query_options());
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, nullptr);
+        c.d_step_stats = static_cast<unsigned long long *>(d_steps);
+        d.search(c);
     });
 }
 
 int gdx_bench_lf_walk_dev(const gdx_index_t *ix, const void *d_rows, uint64_t m, uint32_t steps, void *d_symbols,
                           void *d_end_rows, void *stream)
 {
-    return guarded([&] {
-        DeviceGuard guard(deref(ix).config().device_id);
+    return device_call(ix, stream, [&](DeviceCall &d) {
         if (m != 0 && (!d_rows || !d_symbols)) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "gdx_bench_lf_walk_dev: null argument");
-        gdx::launch_lf_walk(deref(ix).view(), static_cast<const uint32_t *>(d_rows), m, steps,
-                            static_cast<uint8_t *>(d_symbols), static_cast<uint32_t *>(d_end_rows), as_stream(stream));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+        d.enter();
+        gdx::launch_lf_walk(d.f.view(), u32(d_rows), m, steps, static_cast<uint8_t *>(d_symbols), u32(d_end_rows), d.st);
     });
 }
 
@@ -2111,29 +1969,26 @@ int gdx_locate_step_stats_dev(const gdx_index_t *ix, const void *d_start, const 
                               const void *d_hit_offsets, uint64_t total_hits, void *d_hits, void *d_workspace,
                               void *d_steps, void *stream)
 {
-    return guarded([&] {
-        DeviceGuard guard(deref(ix).config().device_id);
-        gdx::launch_locate(deref(ix).view(), static_cast<const uint32_t *>(d_start),
-                           static_cast<const uint32_t *>(d_end), m, static_cast<const uint64_t *>(d_hit_offsets),
-                           total_hits, d_hits, false, d_workspace, as_stream(stream),
-                           static_cast<unsigned long long *>(d_steps), nullptr, deref(ix).query_options(), nullptr,
-                           true);
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::LocateCall c = locate_into(m, d_hit_offsets, total_hits, d_hits, d_workspace);
+        c.d_start = u32(d_start);
+        c.d_end = u32(d_end);
+        c.reference_walk = true;
+        c.d_step_stats = static_cast<unsigned long long *>(d_steps);
+        d.enter();
+        gdx::launch_locate(d.f.view(), c, d.st, d.f.query_options());
     });
 }
 
 int gdx_locate_many_hits_stats_dev(const gdx_index_t *ix, const void *d_records, uint64_t nq, const void *d_hit_offsets,
                                    uint64_t total_hits, void *d_hits, void *d_workspace, void *d_steps, void *stream)
 {
-    return guarded([&] {
-        const gdx::FmIndex &f = deref(ix);
-        DeviceGuard guard(f.config().device_id);
-        gdx::launch_locate(f.view(), nullptr, nullptr, nq, static_cast<const uint64_t *>(d_hit_offsets), total_hits,
-                           d_hits, false, d_workspace, as_stream(stream), static_cast<unsigned long long *>(d_steps),
-                           nullptr, f.query_options(), static_cast<const uint4 *>(d_records));
-        GDX_HIP(hipGetLastError());
-        return (int)GDX_OK;
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        gdx::LocateCall c = locate_into(nq, d_hit_offsets, total_hits, d_hits, d_workspace);
+        c.d_rec = static_cast<const uint4 *>(d_records);
+        c.d_step_stats = static_cast<unsigned long long *>(d_steps);
+        d.enter();
+        gdx::launch_locate(d.f.view(), c, d.st, d.f.query_options());
     });
 }
 

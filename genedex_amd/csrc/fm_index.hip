@@ -2143,8 +2143,17 @@ void FmIndex::locate_device(const uint32_t *d_start, const uint32_t *d_end, uint
     }
     DeviceBuffer<gdx_hit_t> d_hits(total);
     DeviceBuffer<uint8_t> ws(locate_workspace_bytes(total));
-    launch_locate(view_, d_start, d_end, m, d_off.get(), total, d_hits.get(), true, ws.get(), stream, nullptr, nullptr,
-                  query_options(), d_rec);
+    LocateCall loc;
+    loc.d_start = d_start;
+    loc.d_end = d_end;
+    loc.d_rec = d_rec;
+    loc.m = m;
+    loc.d_hit_offsets = d_off.get();
+    loc.total_hits = total;
+    loc.d_hits = d_hits.get();
+    loc.wide = true;
+    loc.d_workspace = ws.get();
+    launch_locate(view_, loc, stream, query_options());
     GDX_HIP(hipGetLastError());
     GDX_HIP(hipMemcpyAsync(hits, d_hits.get(), total * sizeof(gdx_hit_t), hipMemcpyDeviceToHost, stream));
     GDX_HIP(hipStreamSynchronize(stream));

@@ -704,8 +704,15 @@ int FmIndex::host_pipeline(int kind_i, const uint8_t *qbuf, const uint64_t *qoff
                 d_hits[s] = device_buf<uint8_t>(dev, s * 16 + 8, c.total * hit_bytes);
                 h_hits[s] = pinned_buf<uint8_t>(dev, s * 16 + 6, c.total * hit_bytes);
                 d_ws[s] = device_buf<uint8_t>(dev, s * 16 + 9, locate_workspace_bytes(c.total));
-                launch_locate(view_, nullptr, nullptr, c.nq, d_off[s], c.total, d_hits[s], wide_hits, d_ws[s], st.k, nullptr,
-                              nullptr, qo, d_rec[s]);
+                LocateCall loc;
+                loc.d_rec = d_rec[s];
+                loc.m = c.nq;
+                loc.d_hit_offsets = d_off[s];
+                loc.total_hits = c.total;
+                loc.d_hits = d_hits[s];
+                loc.wide = wide_hits;
+                loc.d_workspace = d_ws[s];
+                launch_locate(view_, loc, st.k, qo);
                 GDX_HIP(hipGetLastError());
             }
             GDX_HIP(hipEventRecord(st.ev_k[s], st.k));

@@ -90,7 +90,8 @@ struct SearchCall {
     uint64_t nq = 0;
     uint32_t *d_start = nullptr, *d_end = nullptr, *d_count = nullptr;
     uint8_t *d_status = nullptr;
-    uint2 *d_hint = nullptr;
+    uint2 *d_hint = nullptr;  // uint2[nq]: locate hints for launch_locate of exactly these intervals ({0xffffffff, 0} = none; see
+                              // locate_queue_kernel)
     uint4 *d_rec = nullptr;
     uint32_t *d_compact = nullptr;  // mode 1 with d_rec: compact results (above)
     unsigned long long *d_step_stats = nullptr;
@@ -114,13 +115,6 @@ void launch_search_call(const IndexView &ix, const SearchCall &call, hipStream_t
                         const QueryOptions &qo = QueryOptions());
 
 // ---- search.hip ---------------------------------------------------------------------------
-// Backward search of nq queries (lookup jump + LF loop), one lane per query.
-// Any of out_start/out_end/out_count/out_status may be null.  d_hint (optional, uint2[nq]): locate hints for
-// launch_locate of exactly these intervals ({0xffffffff, 0} = none; see locate_queue_kernel).
-void launch_search(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq,
-                   uint32_t *d_out_start, uint32_t *d_out_end, uint32_t *d_out_count, uint8_t *d_out_status,
-                   hipStream_t stream, unsigned long long *d_step_stats = nullptr, uint2 *d_hint = nullptr,
-                   const QueryOptions &qo = QueryOptions());
 void set_search_variant(int v);  // 0 quad, 1 lane, 2 pair (default), -1 re-read the environment
 // ASCII -> 2-bit packed queries on the device (include/gdx.h "packed queries")
 void launch_pack_queries(const IndexView &ix, const uint8_t *d_qbuf, uint64_t n_symbols, uint8_t *d_packed,
@@ -274,30 +268,62 @@ void launch_wire_split(const IndexView &ix, const uint8_t *d_bitmap, const uint3
                        uint64_t found_cap, uint64_t m, const uint32_t *d_exc_q, const uint32_t *d_meta, uint64_t exc_cap, uint8_t *d_ids,
                        int32_t *d_pos, hipStream_t stream);
 size_t locate_workspace_bytes(uint64_t total_hits);
-// HitT = gdx_hit32_t (wide == false) or gdx_hit_t (wide == true)
-void launch_locate(const IndexView &ix, const uint32_t *d_start, const uint32_t *d_end, uint64_t m,
-                   const uint64_t *d_hit_offsets, uint64_t total_hits, void *d_hits, bool wide,
-                   void *d_workspace, hipStream_t stream, unsigned long long *d_step_stats = nullptr,
-                   const uint2 *d_hint = nullptr, const QueryOptions &qo = QueryOptions(),
-                   const uint4 *d_rec = nullptr, bool reference_walk = false,
-                   const uint32_t *d_compact = nullptr, bool compact_stored = false, const uint8_t *d_chunk_flags = nullptr,
-                   bool narrow_offsets = false,  // d_hit_offsets is u32[m + 1] (records path only)
-                   const unsigned long long *d_total = nullptr);  // != null: the number of hit slots is read on the device (no host
-                                                                  // round trip); total_hits is then the hit buffer's capacity
+// One locate launch: the hits of m intervals (or records) into the slots their hit offsets name.
+struct LocateCall {
+    // where the intervals come from: d_start / d_end with the optional d_hint of the search that made them, or -- d_rec !=
+    // null -- start / hint come from the search records instead of d_start / d_hint (d_start, d_end unused), with the
+    // optional compact results beside them
+    const uint32_t *d_start = nullptr, *d_end = nullptr;
+    const uint2 *d_hint = nullptr;
+    const uint4 *d_rec = nullptr;
+    const uint32_t *d_compact = nullptr;
+    uint64_t m = 0;
+    const void *d_hit_offsets = nullptr;  // u64[m + 1]
+    bool narrow_offsets = false;          // d_hit_offsets is u32[m + 1] (records path only)
+    uint64_t total_hits = 0;
+    const unsigned long long *d_total = nullptr;  // != null: the number of hit slots is read on the device (no host round trip);
+                                                  // total_hits is then the hit buffer's capacity
+    // where the hits go and how the call behaves
+    void *d_hits = nullptr;  // HitT = gdx_hit32_t (wide == false) or gdx_hit_t (wide == true)
+    bool wide = false;
+    void *d_workspace = nullptr;  // locate_workspace_bytes(total_hits)
+    // d_chunk_flags (inside the locate workspace at locate_chunk_flags_offset(total_hits), filled by the store pass):
+    // launch_locate then only visits the chunks of hit slots in which that pass left something open
+    const uint8_t *d_chunk_flags = nullptr;
+    bool compact_stored = false;  // the store pass has written the hits the compact results answer: fill what is left
+    // reference_walk: walk one LF step at a time (sampled_suffix_array.rs:118-131) so that the steps counted through
+    // d_step_stats are the reference's
+    bool reference_walk = false;
+    unsigned long long *d_step_stats = nullptr;
+};
+void launch_locate(const IndexView &ix, const LocateCall &call, hipStream_t stream, const QueryOptions &qo);
 // Offsets scan in two steps with the one host round trip between them: launch_scan_totals leaves d_totals (u64[2]) = {all
 // hit slots, the slots of queries whose compact result says "see the record"} and the tile bases in d_scan_workspace
 // (scan_totals_workspace_bytes); launch_scan_offsets_store then writes the offsets and, in the same pass, the hit of every
-// query whose compact result is its position.  launch_locate(..., compact_stored = true) fills what is left (totals[1]).
+// query whose compact result is its position.  launch_locate with compact_stored fills what is left (totals[1]).
 size_t scan_totals_workspace_bytes(uint64_t m);
 void launch_scan_totals_finish(void *d_scan_workspace, uint64_t m, unsigned long long *d_totals, hipStream_t stream);
 void launch_scan_totals(const uint4 *d_rec, const uint32_t *d_compact, uint64_t m, uint32_t max_hits, bool take,
                         void *d_scan_workspace, unsigned long long *d_totals, hipStream_t stream);
-void launch_scan_offsets_store(const IndexView &ix, const uint4 *d_rec, const uint32_t *d_compact, uint64_t m, uint32_t max_hits,
-                               bool take, const void *d_scan_workspace, uint64_t *d_hit_offsets, void *d_hits,
-                               uint64_t hits_capacity, bool wide, hipStream_t stream, bool store = true,
-                               uint8_t *d_chunk_flags = nullptr, bool narrow_offsets = false, bool flags_zeroed = false,
-                               bool entry_sa = false,  // locate_entry_sa(ix, qo): the pass may locate small "see the record" queries itself
-                               const unsigned long long *d_totals = nullptr);  // != null: ... only if the totals say they are few
+struct OffsetsStore {  // (launch_offsets_hits and launch_locate_step fill it)
+    const uint4 *d_rec = nullptr;
+    const uint32_t *d_compact = nullptr;
+    uint64_t m = 0;
+    uint32_t max_hits = 0;
+    bool take = false;
+    const void *d_scan_workspace = nullptr;
+    void *d_hit_offsets = nullptr;  // u64[m + 1], or u32[m + 1] with narrow_offsets
+    bool narrow_offsets = false;
+    void *d_hits = nullptr;
+    uint64_t hits_capacity = 0;
+    bool wide = false;
+    bool store = true;  // store == false: offsets only
+    uint8_t *d_chunk_flags = nullptr;  // (LocateCall::d_chunk_flags)
+    bool flags_zeroed = false;
+    bool entry_sa = false;  // locate_entry_sa(ix, qo): the pass may locate small "see the record" queries itself
+    const unsigned long long *d_totals = nullptr;  // != null: ... only if the totals say they are few
+};
+void launch_scan_offsets_store(const IndexView &ix, const OffsetsStore &call, hipStream_t stream);
 bool locate_entry_sa(const IndexView &ix, const QueryOptions &qo);
 // The whole count + locate step of a batch, enqueued without a host round trip (gdx_locate_many_step_compact_layout_dev, and
 // every chunk of the host-pointer call gdx_locate_many_alloc_layout32): search (+ hit totals), offsets scan + the hits the
@@ -324,11 +350,6 @@ void launch_offsets_hits(const IndexView &ix, const uint4 *d_rec, const uint32_t
 size_t locate_chunk_flags_bytes(uint64_t total_hits);
 void *locate_flags_region(uint8_t *d_chunk_flags);          // what is zeroed before the store pass: an "any flagged" word + the flags
 size_t locate_flags_region_bytes(uint64_t total_hits);
-// store == false: offsets only.  d_chunk_flags (inside the locate workspace at locate_chunk_flags_offset(total_hits), filled by
-// the store pass): launch_locate then only visits the chunks of hit slots in which that pass left something open
 size_t locate_chunk_flags_offset(uint64_t total_hits);
-// reference_walk: walk one LF step at a time (sampled_suffix_array.rs:118-131) so that the steps counted through
-// d_step_stats are the reference's
-// d_rec != null: start / hint come from the search records instead of d_start / d_hint (d_start, d_end unused)
 
 }  // namespace gdx

@@ -1219,27 +1219,26 @@ void launch_scan_totals_finish(void *d_scan_workspace, uint64_t m, unsigned long
     hipLaunchKernelGGL(scan2_sums_kernel, dim3(1), dim3(1024), 0, stream, sums, n_tiles, d_totals);
 }
 
-void launch_scan_offsets_store(const IndexView &ix, const uint4 *d_rec, const uint32_t *d_compact, uint64_t m, uint32_t max_hits,
-                               bool take, const void *d_scan_workspace, uint64_t *d_hit_offsets, void *d_hits,
-                               uint64_t hits_capacity, bool wide, hipStream_t stream, bool store, uint8_t *d_chunk_flags,
-                               bool narrow_offsets, bool flags_zeroed, bool entry_sa, const unsigned long long *d_totals)
+void launch_scan_offsets_store(const IndexView &ix, const OffsetsStore &c, hipStream_t stream)
 {
-    const uint32_t narrow = narrow_offsets ? 1u : 0u;
+    const uint64_t m = c.m;
+    const uint32_t narrow = c.narrow_offsets ? 1u : 0u;
+    uint64_t *d_hit_offsets = static_cast<uint64_t *>(c.d_hit_offsets);
     if (m == 0) {
         GDX_HIP(hipMemsetAsync(d_hit_offsets, 0, narrow ? sizeof(uint32_t) : sizeof(uint64_t), stream));
         return;
     }
-    const RecordSize f{d_rec, d_compact, m, max_hits, take};
+    const RecordSize f{c.d_rec, c.d_compact, m, c.max_hits, c.take};
     const uint64_t n_tiles = (m + kScan2Tile - 1) / kScan2Tile;
-    const unsigned long long *sums = static_cast<const unsigned long long *>(d_scan_workspace);
-    if (d_chunk_flags != nullptr && !flags_zeroed)
-        GDX_HIP(hipMemsetAsync(locate_flags_region(d_chunk_flags), 0, locate_flags_region_bytes(hits_capacity), stream));
+    const unsigned long long *sums = static_cast<const unsigned long long *>(c.d_scan_workspace);
+    if (c.d_chunk_flags != nullptr && !c.flags_zeroed)
+        GDX_HIP(hipMemsetAsync(locate_flags_region(c.d_chunk_flags), 0, locate_flags_region_bytes(c.hits_capacity), stream));
     // (grids the chip holds at once: every block strides over many tiles)
     static const unsigned cap_plain = resident_blocks(scan2_tile_scan_kernel<false, false>);
     static const unsigned cap_store = resident_blocks(scan2_tile_scan_kernel<true, false>);
     static const unsigned cap_wide = resident_blocks(scan2_tile_scan_kernel<true, true>);
     auto grid_of = [&](unsigned cap) { return dim3(static_cast<unsigned>(n_tiles < cap ? n_tiles : cap)); };
-    if (!store || d_compact == nullptr || d_hits == nullptr) {
+    if (!c.store || c.d_compact == nullptr || c.d_hits == nullptr) {
         hipLaunchKernelGGL((scan2_tile_scan_kernel<false, false>), grid_of(cap_plain), dim3(kBlock), 0, stream, f, m, sums, d_hit_offsets,
                            ScanStore{}, narrow);
         return;
@@ -1247,10 +1246,10 @@ void launch_scan_offsets_store(const IndexView &ix, const uint4 *d_rec, const ui
     uint32_t shift = 0;
     while ((static_cast<uint64_t>(ix.n) >> shift) >= kTextTab) shift++;
     // (inline location of the few "see the record" queries: only where SA[row] is one fetch, launch_locate's entry_sa)
-    const uint32_t *jump32 = entry_sa && ix.sa_full == nullptr && ix.jump != nullptr && ix.jump_bytes == 32 ? static_cast<const uint32_t *>(ix.jump) : nullptr;
-    const ScanStore ss{ix.sentinels, ix.n_texts, shift, d_hits, hits_capacity, d_chunk_flags, entry_sa ? ix.sa_full : nullptr, jump32,
-                       d_totals, entry_sa ? kScanInlineMax : 0u};
-    if (wide)
+    const uint32_t *jump32 = c.entry_sa && ix.sa_full == nullptr && ix.jump != nullptr && ix.jump_bytes == 32 ? static_cast<const uint32_t *>(ix.jump) : nullptr;
+    const ScanStore ss{ix.sentinels, ix.n_texts, shift, c.d_hits, c.hits_capacity, c.d_chunk_flags, c.entry_sa ? ix.sa_full : nullptr, jump32,
+                       c.d_totals, c.entry_sa ? kScanInlineMax : 0u};
+    if (c.wide)
         hipLaunchKernelGGL((scan2_tile_scan_kernel<true, true>), grid_of(cap_wide), dim3(kBlock), 0, stream, f, m, sums, d_hit_offsets, ss, narrow);
     else
         hipLaunchKernelGGL((scan2_tile_scan_kernel<true, false>), grid_of(cap_store), dim3(kBlock), 0, stream, f, m, sums, d_hit_offsets, ss, narrow);
@@ -1695,6 +1694,24 @@ void launch_wire_split(const IndexView &ix, const uint8_t *d_bitmap, const uint3
                        d_tile_found, d_found_pos, found_cap, m, d_exc_q, d_meta, exc_cap, ix.sentinels, ix.n_texts, shift, d_ids, d_pos);
 }
 
+// the locate that follows a store pass: the same records, offsets and hits, filling what that pass left open
+static LocateCall locate_after(const OffsetsStore &scan, void *d_workspace)
+{
+    LocateCall c;
+    c.d_rec = scan.d_rec;
+    c.d_compact = scan.d_compact;
+    c.m = scan.m;
+    c.d_hit_offsets = scan.d_hit_offsets;
+    c.narrow_offsets = scan.narrow_offsets;
+    c.total_hits = scan.hits_capacity;
+    c.d_total = scan.d_totals;
+    c.d_hits = scan.d_hits;
+    c.d_workspace = d_workspace;
+    c.d_chunk_flags = scan.d_chunk_flags;
+    c.compact_stored = scan.store;
+    return c;
+}
+
 void launch_offsets_hits(const IndexView &ix, const uint4 *d_rec, const uint32_t *d_compact, uint64_t nq, uint32_t max_hits, bool take,
                          const void *d_scan_workspace, void *d_hit_offsets, bool narrow, uint64_t total_hits, uint64_t rest_hits,
                          void *d_hits, void *d_workspace, hipStream_t stream, const QueryOptions &qo)
@@ -1703,11 +1720,22 @@ void launch_offsets_hits(const IndexView &ix, const uint4 *d_rec, const uint32_t
     // visits only those; many (reads from repeats, short reads): the scan writes offsets only and locate streams over all slots
     const bool sparse = d_compact != nullptr && rest_hits * 16 <= total_hits;
     uint8_t *flags = (sparse && rest_hits != 0) ? static_cast<uint8_t *>(d_workspace) + locate_chunk_flags_offset(total_hits) : nullptr;
-    launch_scan_offsets_store(ix, d_rec, d_compact, nq, max_hits, take, d_scan_workspace, static_cast<uint64_t *>(d_hit_offsets), d_hits,
-                              total_hits, false, stream, sparse, flags, narrow, false, locate_entry_sa(ix, qo));
-    if (rest_hits != 0 || !sparse)
-        launch_locate(ix, nullptr, nullptr, nq, static_cast<const uint64_t *>(d_hit_offsets), total_hits, d_hits, false, d_workspace,
-                      stream, nullptr, nullptr, qo, d_rec, false, d_compact, sparse, flags, narrow);
+    OffsetsStore scan;
+    scan.d_rec = d_rec;
+    scan.d_compact = d_compact;
+    scan.m = nq;
+    scan.max_hits = max_hits;
+    scan.take = take;
+    scan.d_scan_workspace = d_scan_workspace;
+    scan.d_hit_offsets = d_hit_offsets;
+    scan.narrow_offsets = narrow;
+    scan.d_hits = d_hits;
+    scan.hits_capacity = total_hits;
+    scan.store = sparse;
+    scan.d_chunk_flags = flags;
+    scan.entry_sa = locate_entry_sa(ix, qo);
+    launch_scan_offsets_store(ix, scan, stream);
+    if (rest_hits != 0 || !sparse) launch_locate(ix, locate_after(scan, d_workspace), stream, qo);
 }
 
 void launch_locate_step(const IndexView &ix, const LocateStep &step, hipStream_t st, const QueryOptions &qo)
@@ -1744,12 +1772,24 @@ void launch_locate_step(const IndexView &ix, const LocateStep &step, hipStream_t
     else  // (zeroes the totals again and counts from the results)
         launch_scan_totals(c.d_rec, d_compact, nq, step.max_hits, step.take, step.d_scan_workspace, totals, st);
     if (step.event_after_search) GDX_HIP(hipEventRecord(step.event_after_search, st));
-    launch_scan_offsets_store(ix, c.d_rec, d_compact, nq, step.max_hits, step.take, step.d_scan_workspace,
-                              static_cast<uint64_t *>(step.d_hit_offsets), step.d_hits, step.hits_capacity, false, st, store, flags,
-                              step.narrow, true, locate_entry_sa(ix, qo), totals);
-    if (step.hits_capacity != 0)
-        launch_locate(ix, nullptr, nullptr, nq, static_cast<const uint64_t *>(step.d_hit_offsets), step.hits_capacity, step.d_hits, false,
-                      step.d_workspace, st, nullptr, nullptr, qo, c.d_rec, false, d_compact, store, flags, step.narrow, totals);
+    OffsetsStore scan;
+    scan.d_rec = c.d_rec;
+    scan.d_compact = d_compact;
+    scan.m = nq;
+    scan.max_hits = step.max_hits;
+    scan.take = step.take;
+    scan.d_scan_workspace = step.d_scan_workspace;
+    scan.d_hit_offsets = step.d_hit_offsets;
+    scan.narrow_offsets = step.narrow;
+    scan.d_hits = step.d_hits;
+    scan.hits_capacity = step.hits_capacity;
+    scan.store = store;
+    scan.d_chunk_flags = flags;
+    scan.flags_zeroed = true;
+    scan.entry_sa = locate_entry_sa(ix, qo);
+    scan.d_totals = totals;
+    launch_scan_offsets_store(ix, scan, st);
+    if (step.hits_capacity != 0) launch_locate(ix, locate_after(scan, step.d_workspace), st, qo);
 }
 
 size_t count_offsets_temp_bytes(uint64_t m)
@@ -1783,16 +1823,13 @@ size_t locate_workspace_bytes(uint64_t total_hits)
     return locate_chunk_flags_offset(total_hits) + align_up(locate_chunk_flags_bytes(total_hits) + 4, 256) + 256;  // (+ the ticket: entry n_chunks + 1 of the table)
 }
 
-void launch_locate(const IndexView &ix, const uint32_t *d_start, const uint32_t *d_end, uint64_t m,
-                   const uint64_t *d_hit_offsets, uint64_t total_hits, void *d_hits, bool wide,
-                   void *d_workspace, hipStream_t stream, unsigned long long *d_step_stats, const uint2 *d_hint,
-                   const QueryOptions &qo, const uint4 *d_rec, bool reference_walk, const uint32_t *d_compact,
-                   bool compact_stored, const uint8_t *d_chunk_flags, bool narrow_offsets, const unsigned long long *d_total)
+void launch_locate(const IndexView &ix, const LocateCall &c, hipStream_t stream, const QueryOptions &qo)
 {
+    const uint64_t m = c.m, total_hits = c.total_hits;
     if (total_hits == 0 || m == 0) return;
-    if (d_total != nullptr && d_rec == nullptr) fail(GDX_ERR_INVALID_ARGUMENT, "internal: a device-side total goes with search records");
-    if (narrow_offsets && d_rec == nullptr) fail(GDX_ERR_INVALID_ARGUMENT, "internal: narrow offsets go with search records");
-    const HitOffsets offs{d_hit_offsets, narrow_offsets ? 1u : 0u};
+    if (c.d_total != nullptr && c.d_rec == nullptr) fail(GDX_ERR_INVALID_ARGUMENT, "internal: a device-side total goes with search records");
+    if (c.narrow_offsets && c.d_rec == nullptr) fail(GDX_ERR_INVALID_ARGUMENT, "internal: narrow offsets go with search records");
+    const HitOffsets offs{c.d_hit_offsets, c.narrow_offsets ? 1u : 0u};
     // (rounds 1-4 kept two lock-step variants beside the chunk kernels -- one lane per hit, eight lanes per hit on pair lines --
     // behind gdx_query_options_t.locate_kernel: 3 and 5 times slower (profiles/r01/search_variants.md), reached by no
     // configuration, and their slot -> query map cost 4 bytes of workspace per hit; removed in round 5, the option is ignored)
@@ -1801,73 +1838,73 @@ void launch_locate(const IndexView &ix, const uint32_t *d_start, const uint32_t 
     // SA[row] is one fetch and every slot is open (no chunk flags): by query, no chunk table at all
     // (GDX_LOCATE_BY_QUERY=0, experiments: the stream kernel for those too)
     static const bool by_query = [] { const char *e = getenv("GDX_LOCATE_BY_QUERY"); return e == nullptr || atoi(e) != 0; }();
-    const bool sa_at_hand = ix.layout == 0 && !reference_walk && qo.locate_jump_walk != 0 &&
+    const bool sa_at_hand = ix.layout == 0 && !c.reference_walk && qo.locate_jump_walk != 0 &&
                             (ix.sa_full != nullptr || (ix.jump != nullptr && ix.jump_bytes == 32));
-    if (by_query && sa_at_hand && d_chunk_flags == nullptr) {
+    if (by_query && sa_at_hand && c.d_chunk_flags == nullptr) {
         uint32_t shift = 0;
         while ((static_cast<uint64_t>(ix.n) >> shift) >= kTextTab) shift++;
         const StreamView sv{ix.sa_full, ix.sa_full == nullptr ? static_cast<const uint32_t *>(ix.jump) : nullptr, ix.sentinels,
-                            ix.n_texts, shift, compact_stored ? 2u : 0u};
+                            ix.n_texts, shift, c.compact_stored ? 2u : 0u};
         static const unsigned cap_q = resident_blocks(locate_by_query_kernel<false>), cap_qw = resident_blocks(locate_by_query_kernel<true>);
         const uint64_t groups = (m + 63) / 64, blocks = (groups + kBlock / 64 - 1) / (kBlock / 64);
         const unsigned bgrid = grid_override > 0 ? static_cast<unsigned>(grid_override)
-                                                 : static_cast<unsigned>(std::min<uint64_t>(blocks, 4ull * (wide ? cap_qw : cap_q)));
-        if (wide)
-            hipLaunchKernelGGL(locate_by_query_kernel<true>, dim3(bgrid), dim3(kBlock), 0, stream, sv, d_start, offs, m, d_hint, d_rec,
-                               total_hits, d_hits, d_compact, d_total);
+                                                 : static_cast<unsigned>(std::min<uint64_t>(blocks, 4ull * (c.wide ? cap_qw : cap_q)));
+        if (c.wide)
+            hipLaunchKernelGGL(locate_by_query_kernel<true>, dim3(bgrid), dim3(kBlock), 0, stream, sv, c.d_start, offs, m, c.d_hint, c.d_rec,
+                               total_hits, c.d_hits, c.d_compact, c.d_total);
         else
-            hipLaunchKernelGGL(locate_by_query_kernel<false>, dim3(bgrid), dim3(kBlock), 0, stream, sv, d_start, offs, m, d_hint, d_rec,
-                               total_hits, d_hits, d_compact, d_total);
+            hipLaunchKernelGGL(locate_by_query_kernel<false>, dim3(bgrid), dim3(kBlock), 0, stream, sv, c.d_start, offs, m, c.d_hint, c.d_rec,
+                               total_hits, c.d_hits, c.d_compact, c.d_total);
         return;
     }
     {
         const uint64_t n_chunks = (total_hits + kLocateChunk - 1) / kLocateChunk;
-        uint32_t *first = static_cast<uint32_t *>(d_workspace);  // n_chunks + 1 entries of the workspace
+        uint32_t *first = static_cast<uint32_t *>(c.d_workspace);  // n_chunks + 1 entries of the workspace
         uint32_t *ticket = first + n_chunks + 1;                 // (the table's spare entry: zeroed by chunk_first_query_kernel)
         hipLaunchKernelGGL(chunk_first_query_kernel, dim3(static_cast<unsigned>((n_chunks + kBlock) / kBlock)),
-                           dim3(kBlock), 0, stream, offs, m, n_chunks, kLocateChunk, total_hits, first, d_total, d_chunk_flags, ticket);
+                           dim3(kBlock), 0, stream, offs, m, n_chunks, kLocateChunk, total_hits, first, c.d_total, c.d_chunk_flags, ticket);
         // (with chunk flags few chunks have anything to do: a grid the chip holds at once, every block looks at its share
         // of the flags first)
-        const uint64_t grid_cap = d_chunk_flags != nullptr ? 2048u : 65536u;
+        const uint64_t grid_cap = c.d_chunk_flags != nullptr ? 2048u : 65536u;
         const unsigned qgrid = grid_override > 0 ? static_cast<unsigned>(grid_override)
                                                  : static_cast<unsigned>(n_chunks < grid_cap ? n_chunks : grid_cap);
 #define GDX_LOCATE_Q(TABLE, WIDE, JW)                                                                                   \
-    hipLaunchKernelGGL((locate_queue_kernel<TABLE, WIDE, JW>), dim3(qgrid), dim3(kBlock), 0, stream, lv, d_start, offs, \
-                       m, first, d_hint, d_rec, total_hits, d_hits, d_step_stats, d_compact, d_chunk_flags, d_total)
+    hipLaunchKernelGGL((locate_queue_kernel<TABLE, WIDE, JW>), dim3(qgrid), dim3(kBlock), 0, stream, lv, c.d_start, offs, \
+                       m, first, c.d_hint, c.d_rec, total_hits, c.d_hits, c.d_step_stats, c.d_compact, c.d_chunk_flags, c.d_total)
         // the walk goes through the jump table when there is one with at least two levels, unless the caller
         // counts the reference's own walk steps (reference_walk) or switched it off (QueryOptions::locate_jump_walk)
         const LocateView lv{ix.lines, ix.sb_offsets, ix.g_planes, ix.g_block_off, ix.jump, ix.sa_full, ix.count, ix.sa_samples,
                             ix.border_keys, ix.border_vals, ix.sentinels, ix.sb_stride, ix.jump_bytes, ix.n_texts,
-                            ix.sa_inv, ix.sa_rot, ix.sa_limit, ix.sigma, ix.nbits, compact_stored ? 2u : 0u,
+                            ix.sa_inv, ix.sa_rot, ix.sa_limit, ix.sigma, ix.nbits, c.compact_stored ? 2u : 0u,
                             ix.g_kind, ix.g_wpb, ix.g_used, ix.g_sb};
-        const bool jump_walk = ix.layout == 0 && ix.jump != nullptr && ix.jump_bytes >= 16 && !reference_walk &&
+        const bool jump_walk = ix.layout == 0 && ix.jump != nullptr && ix.jump_bytes >= 16 && !c.reference_walk &&
                                qo.locate_jump_walk != 0;
         // SA[row] inside the entries, or as an array of its own: no walk at all
         const bool entry_sa = (jump_walk && ix.jump_bytes == 32) ||
-                              (ix.layout == 0 && ix.sa_full != nullptr && !reference_walk && qo.locate_jump_walk != 0);
+                              (ix.layout == 0 && ix.sa_full != nullptr && !c.reference_walk && qo.locate_jump_walk != 0);
         if (entry_sa) {  // (nothing walks: a caller's step statistics stay zero)
             uint32_t shift = 0;
             while ((static_cast<uint64_t>(ix.n) >> shift) >= kTextTab) shift++;
             const StreamView sv{ix.sa_full, ix.sa_full == nullptr ? static_cast<const uint32_t *>(ix.jump) : nullptr, ix.sentinels,
-                                ix.n_texts, shift, compact_stored ? 2u : 0u};
+                                ix.n_texts, shift, c.compact_stored ? 2u : 0u};
             // a grid the chip holds at once (the text-id table is built once per block); every block strides over the chunks
             static const unsigned cap_s = resident_blocks(locate_stream_kernel<false>), cap_sw = resident_blocks(locate_stream_kernel<true>);
-            const unsigned s_cap = wide ? cap_sw : cap_s;
+            const unsigned s_cap = c.wide ? cap_sw : cap_s;
             const unsigned sgrid = grid_override > 0 ? static_cast<unsigned>(grid_override)
                                                      : static_cast<unsigned>(n_chunks < s_cap ? n_chunks : s_cap);
-            if (wide)
-                hipLaunchKernelGGL(locate_stream_kernel<true>, dim3(sgrid), dim3(kBlock), 0, stream, sv, d_start, offs, m, first, d_hint,
-                                   d_rec, total_hits, d_hits, d_compact, d_chunk_flags, d_total, ticket);
+            if (c.wide)
+                hipLaunchKernelGGL(locate_stream_kernel<true>, dim3(sgrid), dim3(kBlock), 0, stream, sv, c.d_start, offs, m, first, c.d_hint,
+                                   c.d_rec, total_hits, c.d_hits, c.d_compact, c.d_chunk_flags, c.d_total, ticket);
             else
-                hipLaunchKernelGGL(locate_stream_kernel<false>, dim3(sgrid), dim3(kBlock), 0, stream, sv, d_start, offs, m, first, d_hint,
-                                   d_rec, total_hits, d_hits, d_compact, d_chunk_flags, d_total, ticket);
+                hipLaunchKernelGGL(locate_stream_kernel<false>, dim3(sgrid), dim3(kBlock), 0, stream, sv, c.d_start, offs, m, first, c.d_hint,
+                                   c.d_rec, total_hits, c.d_hits, c.d_compact, c.d_chunk_flags, c.d_total, ticket);
         } else if (ix.layout == 0) {
-            if (wide && jump_walk) GDX_LOCATE_Q(LineTable, true, true);
-            else if (wide) GDX_LOCATE_Q(LineTable, true, false);
+            if (c.wide && jump_walk) GDX_LOCATE_Q(LineTable, true, true);
+            else if (c.wide) GDX_LOCATE_Q(LineTable, true, false);
             else if (jump_walk) GDX_LOCATE_Q(LineTable, false, true);
             else GDX_LOCATE_Q(LineTable, false, false);
         } else {
-            if (wide) GDX_LOCATE_Q(GenericTable, true, false);
+            if (c.wide) GDX_LOCATE_Q(GenericTable, true, false);
             else GDX_LOCATE_Q(GenericTable, false, false);
         }
 #undef GDX_LOCATE_Q

@@ -241,8 +241,14 @@ uint64_t FmIndex::locate_shard_dev(const uint8_t *d_qbuf, const uint64_t *d_qoff
     if (total) {
         if (hits.count < total) hits.alloc(total);
         DeviceBuffer<uint8_t> ws(locate_workspace_bytes(total));
-        launch_locate(view_, nullptr, nullptr, nq, off.get(), total, hits.get(), false, ws.get(), stream, nullptr, nullptr, qo,
-                      rec.get());
+        LocateCall loc;
+        loc.d_rec = rec.get();
+        loc.m = nq;
+        loc.d_hit_offsets = off.get();
+        loc.total_hits = total;
+        loc.d_hits = hits.get();
+        loc.d_workspace = ws.get();
+        launch_locate(view_, loc, stream, qo);
         GDX_HIP(hipGetLastError());
         GDX_HIP(hipStreamSynchronize(stream));
     }

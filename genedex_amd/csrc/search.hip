@@ -4016,24 +4016,6 @@ static int search_variant()
     return v;
 }
 
-void launch_search(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq,
-                   uint32_t *d_out_start, uint32_t *d_out_end, uint32_t *d_out_count, uint8_t *d_out_status,
-                   hipStream_t stream, unsigned long long *d_step_stats, uint2 *d_hint, const QueryOptions &qo)
-{
-    SearchCall c;
-    c.d_qbuf = d_qbuf;
-    c.d_qbeg = d_qoff;
-    c.d_qend = d_qoff + 1;
-    c.nq = nq;
-    c.d_start = d_out_start;
-    c.d_end = d_out_end;
-    c.d_count = d_out_count;
-    c.d_status = d_out_status;
-    c.d_hint = d_hint;
-    c.d_step_stats = d_step_stats;
-    launch_search_call(ix, c, stream, qo);
-}
-
 // ZeroSet (kernels.hpp): up to eight small regions zeroed by one launch
 struct ZeroSegments {
     uint32_t *p[ZeroSet::kMax];

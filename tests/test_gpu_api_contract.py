@@ -143,6 +143,212 @@ def test_device_resident_entry_points(setup, hint):
     assert rc == _lib.GDX_ERR_INVALID_ARGUMENT
 
 
+def test_device_entries_refuse_bad_arguments_in_order(setup):
+    """What the _dev entries refuse, with which status and which gdx_last_error text, and which of two faults is reported
+    (the order in which an entry looks at its arguments is part of the contract), read off capi.hip.  No case depends on a
+    launch: every pointer that is not null lies inside one live zero-filled allocation, a misaligned one too, counts are zero
+    or tiny wherever the refusal does not hang on them, and where it does (a batch without offsets, 2^32 - 1 cursors) the call
+    could do nothing if it went on -- no candidates, an empty active list."""
+    torch = pytest.importorskip("torch")
+    from genedex_amd import FmIndexConfig
+
+    _lib, lib, g, c, texts, rng = setup
+    buf = torch.zeros(1 << 22, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    A = (buf.data_ptr() + 255) // 256 * 256
+    h = g._h
+    INV, UNS, OK = _lib.GDX_ERR_INVALID_ARGUMENT, _lib.GDX_ERR_UNSUPPORTED, _lib.GDX_OK
+
+    def layout(struct_size=None, packed=0, uniform_len=0):
+        class Longer(C.Structure):  # room for a struct_size beyond what the library knows
+            _fields_ = [("l", _lib.QueryLayout), ("more", C.c_uint64)]
+
+        lo = Longer()
+        lib.gdx_query_layout_init(C.byref(lo.l))
+        assert lo.l.struct_size == C.sizeof(_lib.QueryLayout) == 16
+        if struct_size is not None:
+            lo.l.struct_size = struct_size
+        lo.l.packed, lo.l.uniform_len = packed, uniform_len
+        return C.cast(C.pointer(lo), C.POINTER(_lib.QueryLayout))
+
+    need = (C.c_uint64 * 2)()  # align: the workspace one candidate needs
+    assert lib.gdx_align_many_dev(h, None, None, 0, None, None, None, None, 1, 1, None, None, None, None, None, None, 0, need, None) == OK
+    assert need[0] > 1
+    QBUF8 = "d_qbuf must be 8-byte aligned"
+    REC = "d_records must be a non-null 16-byte aligned device pointer"
+    NARROW = "32-bit hit offsets need fewer than 2^32 hits"
+    WIDTH = "offsets_width must be 32 or 64"
+    LSIZE = "gdx_query_layout_t.struct_size"
+    COUNTERS = "active lists need their counters"
+    STEP = "gdx_locate_many_step_compact_layout_dev"
+
+    def step(layout_=None, rec=A, scan=A, totals=A, off=A, width=64, hits=None, capacity=0, ws=None, qbuf=A, nq=0):
+        return (STEP, (h, qbuf, A, nq, layout_, 0, rec, None, scan, totals, off, width, hits, capacity, ws, None, None))
+
+    def ham(layout_, qbuf=A, qoff=A, nq=0):  # m = 0: the layout is looked at, then the entry returns
+        return ("gdx_hamming_many_dev", (h, qbuf, qoff, nq, layout_, None, None, None, 0, 1, None, None))
+
+    cases = [
+        # the plain query side: 8-byte d_qbuf, then the entry's own outputs
+        ("gdx_count_many_dev", (h, A + 1, A, 0, A, None, None), INV, QBUF8),
+        ("gdx_cursors_for_many_queries_dev", (h, A + 4, A, 0, A, A, None, None), INV, QBUF8),
+        ("gdx_cursors_for_many_queries_hint_dev", (h, A, A, 0, A, A, None, None, None), INV,
+         "d_hint must be a non-null 8-byte aligned device pointer"),
+        ("gdx_cursors_for_many_queries_hint_dev", (h, A, A, 0, A, A, None, A + 4, None), INV,
+         "d_hint must be a non-null 8-byte aligned device pointer"),
+        ("gdx_cursors_for_many_queries_hint_dev", (h, A + 1, A, 0, A, A, None, None, None), INV, QBUF8),  # two faults
+        ("gdx_locate_many_search_dev", (h, A, A, 0, None, None), INV, REC),
+        ("gdx_locate_many_search_dev", (h, A, A, 0, A + 8, None), INV, REC),
+        ("gdx_locate_many_search_dev", (h, A + 2, A, 0, None, None), INV, QBUF8),  # two faults
+        ("gdx_locate_many_search_compact_dev", (h, A, A, 1, A, None, None), INV, "d_compact is null"),
+        ("gdx_locate_many_search_compact_dev", (h, A, A, 1, A + 8, None, None), INV, REC),  # two faults
+        ("gdx_locate_many_search_compact_dev", (h, A, A, 0, A, None, None), OK, ""),  # (no queries: no compact array needed)
+        # packed: 2-byte d_packed
+        ("gdx_count_many_packed_dev", (h, A + 1, A, 0, A, None, None), INV, "d_packed must be 2-byte aligned"),
+        ("gdx_cursors_for_many_queries_packed_dev", (h, A + 1, A, 0, A, A, None, None), INV, "d_packed must be 2-byte aligned"),
+        ("gdx_locate_many_search_packed_dev", (h, A + 2, A, 0, None, None), INV, REC),
+        ("gdx_locate_many_search_packed_dev", (h, A + 1, A, 0, None, None), INV, "d_packed must be 2-byte aligned"),  # two faults
+        # the record side
+        ("gdx_locate_many_offsets_capped_dev", (h, None, 0, 0, A, None), INV, REC),
+        ("gdx_locate_many_hits_dev", (h, A + 8, 0, A, 0, A, A, None), INV, REC),
+        ("gdx_locate_many_hits_compact_dev", (h, None, A, 0, A, 0, A, A, None), INV, REC),
+        ("gdx_locate_many_unpack_dev", (h, None, 0, None, None, None), INV, REC),
+        ("gdx_locate_many_unpack_dev", (h, A, 0, None, None, None), OK, ""),
+        ("gdx_locate_many_unpack_compact_dev", (h, A + 4, A, 0, A, A, None), INV, REC),
+        ("gdx_locate_many_totals_compact_dev", (h, A, A, 0, 0, None, A, None), INV, "gdx_locate_many_totals_compact_dev: null argument"),
+        ("gdx_locate_many_totals_compact_dev", (h, A, A, 0, 0, A, None, None), INV, "gdx_locate_many_totals_compact_dev: null argument"),
+        ("gdx_locate_many_totals_compact_dev", (h, None, A, 0, 0, None, A, None), INV, REC),  # two faults
+        ("gdx_locate_many_offsets_hits_compact_dev", (h, A, None, 0, 0, None, A, 0, 0, A, A, None), INV,
+         "gdx_locate_many_offsets_hits_compact_dev: null argument"),
+        ("gdx_locate_many_offsets_hits_compact_dev", (h, A, None, 0, 0, A, A, 1, 0, None, A, None), INV,
+         "gdx_locate_many_offsets_hits_compact_dev: null argument"),
+        ("gdx_locate_many_offsets_hits_compact_dev", (h, A, None, 0, 0, A, A, 1, 1, A, None, None), INV,
+         "gdx_locate_many_offsets_hits_compact_dev: d_workspace is null"),
+        ("gdx_locate_many_offsets32_hits_compact_dev", (h, A, None, 0, 0, A, A, 1 << 32, 0, A, A, None), INV, NARROW),
+        ("gdx_locate_many_offsets32_hits_compact_dev", (h, A, None, 0, 0, A, A, 1 << 32, 1, A, None, None), INV, NARROW),  # two faults
+        ("gdx_locate_many_search_totals_compact_layout_dev", (h, A, A, 0, None, 0, A, A, None, A, None), INV,
+         "gdx_locate_many_search_totals_compact_layout_dev: null argument"),
+        ("gdx_locate_many_search_totals_compact_layout_dev", (h, A, A, 1, None, 0, A, None, None, A, None), INV, "d_compact is null"),  # two
+        # the one-call step: records, null pointers, offsets width, narrow offsets, totals, and only then the layout
+        step(rec=None) + (INV, REC),
+        step(scan=None) + (INV, STEP + ": null argument"),
+        step(totals=None) + (INV, STEP + ": null argument"),
+        step(off=None) + (INV, STEP + ": null argument"),
+        step(capacity=1, hits=A) + (INV, STEP + ": null argument"),
+        step(width=48) + (INV, WIDTH),
+        step(width=32, capacity=1 << 32, hits=A, ws=A) + (INV, NARROW),
+        step(totals=A + 4) + (INV, "d_totals must be 8-byte aligned"),
+        step(width=48, totals=A + 4) + (INV, WIDTH),  # two faults
+        step(width=48, scan=None) + (INV, STEP + ": null argument"),  # two faults
+        step(layout_=layout(struct_size=8), totals=A + 4) + (INV, "d_totals must be 8-byte aligned"),  # two faults
+        step(layout_=layout(struct_size=8)) + (INV, LSIZE),
+        step(qbuf=A + 1) + (INV, QBUF8),
+        # the layout, through every entry that takes one
+        ("gdx_count_many_layout_dev", (h, A, A, 0, layout(struct_size=8), A, None, None), INV, LSIZE),
+        ("gdx_count_many_layout_dev", (h, A, A, 0, layout(struct_size=24), A, None, None), INV, LSIZE),
+        ("gdx_count_many_layout_dev", (h, A, A, 0, layout(packed=2), A, None, None), INV, "gdx_query_layout_t.packed must be 0 or 1"),
+        ("gdx_count_many_layout_dev", (h, A, A, 0, layout(uniform_len=1 << 21), A, None, None), INV,
+         "gdx_query_layout_t.uniform_len must be below 2^21"),
+        ("gdx_count_many_layout_dev", (h, A, A, 0, layout(packed=2, uniform_len=1 << 21), A, None, None), INV,
+         "gdx_query_layout_t.packed must be 0 or 1"),  # two faults
+        ("gdx_count_many_layout_dev", (h, A + 1, A, 0, None, A, None, None), INV, QBUF8),
+        ("gdx_count_many_layout_dev", (h, A + 2, A, 0, layout(), A, None, None), INV, QBUF8),
+        ("gdx_count_many_layout_dev", (h, A + 1, A, 0, layout(packed=1), A, None, None), INV, "d_qbuf (packed) must be 2-byte aligned"),
+        ("gdx_count_many_layout_dev", (h, A + 2, A, 0, layout(packed=1, uniform_len=30), A, None, None), OK, ""),
+        ("gdx_cursors_for_many_queries_layout_dev", (h, A + 4, A, 0, None, A, A, None, None), INV, QBUF8),
+        ("gdx_locate_many_search_layout_dev", (h, A, A, 0, layout(struct_size=24), A, None), INV, LSIZE),
+        ("gdx_locate_many_search_layout_dev", (h, A, A, 0, layout(struct_size=24), None, None), INV, REC),  # two faults
+        ("gdx_locate_many_search_compact_layout_dev", (h, A, A, 0, layout(packed=2), A, A, None), INV,
+         "gdx_query_layout_t.packed must be 0 or 1"),
+        ("gdx_locate_many_search_compact_layout_dev", (h, A, A, 1, layout(packed=2), A, None, None), INV, "d_compact is null"),  # two
+        ham(layout(struct_size=8)) + (INV, LSIZE),
+        ham(layout(), qoff=None, nq=1) + (INV, "d_qoff is null and the layout is not uniform"),
+        ham(None, qoff=None, nq=1) + (INV, "d_qoff is null and the layout is not uniform"),
+        ham(layout(), qbuf=A + 1, qoff=None, nq=1) + (INV, QBUF8),  # two faults
+        ham(layout(uniform_len=30), qoff=None, nq=1) + (OK, ""),
+        # cursor extension
+        ("gdx_cursor_extend_front_strings_dev", (h, None, None, A + 1, None, None, 0, None, None, None, None, None, None), INV, QBUF8),
+        ("gdx_cursor_extend_front_strings_dev", (h, A, A, A, None, A, 1, None, None, None, None, None, None), INV, "null argument"),
+        ("gdx_cursor_extend_front_strings_dev", (h, None, None, A, None, None, 0, None, None, None, A, None, None), INV, COUNTERS),
+        ("gdx_cursor_extend_front_strings_dev", (h, None, None, A, None, None, 0, None, A, None, None, None, None), INV, COUNTERS),
+        ("gdx_cursor_extend_front_strings_dev", (h, A, A, A, A, A, (1 << 32) - 1, None, A, A, None, None, None), UNS,
+         "more than 2^32-2 cursors in one call"),
+        ("gdx_cursor_extend_front_strings_dev", (h, A, A, A, A, A, (1 << 32) - 1, None, A, None, None, None, None), INV, COUNTERS),  # two
+        ("gdx_cursor_extend_front_chunk_dev", (h, None, None, A + 4, None, 0, 1, 0, None, None, None, None, None, None), INV, QBUF8),
+        ("gdx_cursor_extend_front_chunk_dev", (h, A, None, A, A, 1, 1, 0, None, None, None, None, None, None), INV, "null argument"),
+        ("gdx_cursor_extend_front_chunk_dev", (h, None, None, A, None, 0, 0, 0, None, None, None, None, None, None), INV,
+         "chunk_symbols must be positive"),
+        ("gdx_cursor_extend_front_chunk_dev", (h, None, None, A, None, 0, 0, 0, None, None, None, None, A, None), INV,
+         "chunk_symbols must be positive"),  # two faults
+        ("gdx_cursor_extend_front_chunk_dev", (h, None, None, A, None, 0, 1, 0, None, None, None, None, A, None), INV, COUNTERS),
+        ("gdx_cursor_extend_front_chunk_dev", (h, A, A, A, A, (1 << 32) - 1, 1, 0, None, A, A, None, None, None), UNS,
+         "more than 2^32-2 cursors in one call"),
+        # the secondary stages: the scalars first, then nothing to do, then the pointers
+        ("gdx_suffix_segments_many_dev", (h, None, None, 0, 0, 0, None, None, None, None, None, None, None), INV,
+         "max_segments must be at least 1"),
+        ("gdx_suffix_segments_many_dev", (h, None, None, 0, 1, 2, None, None, None, None, None, None, None), INV, "unknown bit in flags"),
+        ("gdx_suffix_segments_many_dev", (h, None, None, 0, 0, 2, None, None, None, None, None, None, None), INV,
+         "max_segments must be at least 1"),  # two faults
+        ("gdx_suffix_segments_many_dev", (h, None, None, 0, 1, 1, None, None, None, None, None, None, None), OK, ""),
+        ("gdx_suffix_segments_many_dev", (h, A + 1, A, 1, 1, 0, None, None, None, None, None, None, None), INV, QBUF8),  # two faults
+        ("gdx_suffix_segments_many_dev", (h, A, A, 1, 1, 0, A, A, A, A, None, None, None), INV, "null argument"),
+        ("gdx_hamming_many_dev", (h, None, None, 0, None, None, None, None, 0, 1, None, None), OK, ""),
+        ("gdx_hamming_many_dev", (h, A, A, 0, None, None, A, A, 1, 1, A, None), INV, "null argument"),
+        ("gdx_edit_distance_many_dev", (h, None, None, 0, None, None, None, None, 0, 1, None, None, None), OK, ""),
+        ("gdx_edit_distance_many_dev", (h, None, None, 1, layout(uniform_len=8), A, A, A, 1, 1, A, None, None), INV, "d_qbuf is null"),
+        ("gdx_best_hits_many_dev", (h, 0, 1) + (None,) * 5 + (0,) + (None,) * 10, OK, ""),
+        ("gdx_best_hits_many_dev", (h, 1, 1, A, A, A, None, None, 0) + (A,) * 9 + (None,), INV, "null argument"),
+        ("gdx_pair_hits_many_dev", (h, 0, 1) + (None,) * 5 + (0, 0, 0) + (None,) * 12, OK, ""),
+        ("gdx_seed_candidates_many_dev", (h, 0, 1) + (None,) * 5 + (1, 0, 1) + (None,) * 9, OK, ""),
+        # align: the workspace, before the outputs and the candidates (which are null here)
+        ("gdx_align_many_dev", (h, A, A, 0, None, None, None, None, 1, 1, None, None, None, None, None, A, 1, None, None), INV,
+         "workspace of 1 bytes, at least %d are needed" % need[0]),
+        ("gdx_align_many_dev", (h, A, A, 0, None, None, None, None, 1, 1, None, None, None, None, None, A + 8, need[0], None, None), INV,
+         "d_workspace must be 16-byte aligned"),
+        ("gdx_align_many_dev", (h, A, A, 0, None, None, None, None, 1, 1, None, None, None, None, None, A, need[0], None, None), INV,
+         "null output"),
+        ("gdx_align_many_dev", (h, A, A, 0, layout(struct_size=8), None, None, None, 1, 1, None, None, None, None, None, A, 1, None, None),
+         INV, LSIZE),  # two faults
+        ("gdx_align_many_dev", (h, A, A, 0, None, None, None, None, 0, 1, A, A, A, A, A, A, need[0], None, None), OK, ""),
+        # both strands: mode, layout, outputs, the overlap
+        ("gdx_strands_expand_dev", (h, A, A, 0, None, 0, None, 3, A + 4096, None, None), INV,
+         "mode must be GDX_STRANDS_REVERSE or GDX_STRANDS_BOTH"),
+        ("gdx_strands_expand_dev", (h, A, A, 0, layout(struct_size=8), 0, None, 0, A + 4096, None, None), INV,
+         "mode must be GDX_STRANDS_REVERSE or GDX_STRANDS_BOTH"),  # two faults
+        ("gdx_strands_expand_dev", (h, A, A, 0, layout(struct_size=8), 0, None, 1, A + 4096, None, None), INV, LSIZE),
+        ("gdx_strands_expand_dev", (h, A, A, 0, None, 0, None, 1, None, None, None), INV, "null output"),
+        ("gdx_strands_expand_dev", (h, A, A, 0, None, 0, None, 2, A + 4096, None, None), INV, "null output"),
+        ("gdx_strands_expand_dev", (h, A, A, 0, None, 0, None, 1, A + 4100, None, None), INV, "d_out_qbuf must be 8-byte aligned"),
+        ("gdx_strands_expand_dev", (h, A, None, 2, layout(uniform_len=8), 17, None, 1, A + 4096, None, None), INV,
+         "a uniform batch of 2 queries of 8 symbols has 16 symbols, not 17"),
+        ("gdx_strands_expand_dev", (h, A + 4096, A, 1, None, 8, None, 1, A + 4096, None, None), INV, "d_out_qbuf overlaps d_qbuf"),
+        ("gdx_strands_expand_dev", (h, A + 4096, A, 1, None, 8, None, 2, A + 4088, A + 8192, None), INV, "d_out_qbuf overlaps d_qbuf"),
+    ]
+    for k, (name, args, status, text) in enumerate(cases):
+        rc = getattr(lib, name)(*args)
+        assert rc == status, (k, name, rc, _lib.last_error())
+        if status != OK:
+            assert _lib.last_error() == text, (k, name)
+    # an index with 64-bit storage: every _dev entry says that it is not for it, before it looks at anything else
+    lib.gdx_debug_force_wide(1)
+    try:
+        w = FmIndexConfig("i64").construct_index([b"ACGTTGCAACGT", b"GGA"], alph.ascii_dna_with_n())
+    finally:
+        lib.gdx_debug_force_wide(0)
+    assert w.info.index_width == 64
+    WIDE = ("this call is not available on an index with 64-bit storage (count, cursors_for_many_queries "
+            "and locate on host pointers are)")
+    for name, args in [("gdx_count_many_dev", (w._h, A + 1, A, 0, A, None, None)),
+                       ("gdx_locate_many_search_dev", (w._h, A, A, 0, None, None)),
+                       step()[:1] + ((w._h,) + step(width=48)[1][1:],),
+                       ("gdx_suffix_segments_many_dev", (w._h, None, None, 0, 0, 0, None, None, None, None, None, None, None))]:
+        assert getattr(lib, name)(*args) == UNS, name
+        assert _lib.last_error() == WIDE, name
+    assert lib.gdx_count_many_dev(None, A, A, 0, A, None, None) == INV and _lib.last_error() == "index handle is null"
+    torch.cuda.synchronize()
+    assert not bool(buf.any().item())  # nothing was written: no refused call got as far as a launch
+
+
 def test_save_and_load_round_trip(setup, tmp_path):
     """FmIndex::save_to_file / load_from_file (lib.rs:296-327), own format around the reference's logical arrays."""
     from genedex_amd import FmIndex, GdxError
