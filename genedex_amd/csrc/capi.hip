@@ -1589,8 +1589,7 @@ int gdx_strands_expand_dev(const gdx_index_t *ix, const void *d_qbuf, const void
             gdx::fail(GDX_ERR_INVALID_ARGUMENT, "mode must be GDX_STRANDS_REVERSE or GDX_STRANDS_BOTH");
         // (the layout's checks: struct size, alignment of d_qbuf, offsets of a batch that is not uniform)
         const gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, layout);
-        if (c.packed && (d.f.view().layout != 0 || d.f.view().n_searchable < 4))
-            gdx::fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
+        if (c.packed) d.f.check_packed_supported();
         uint8_t stock[256];
         if (!complement) {
             gdx::dna_complement_table(stock);

@@ -2412,8 +2412,7 @@ void FmIndex::check_hamming(bool packed, uint32_t max_mismatches) const
 {
     if (view_.text_units == nullptr)
         fail(GDX_ERR_UNSUPPORTED, "the index holds no text units (gdx_build_options_t.text_units): there is no text to compare with");
-    if (packed && (view_.layout != 0 || view_.n_searchable < 4))
-        fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
+    if (packed) check_packed_supported();
     if (max_mismatches > 0x80000000u) fail(GDX_ERR_INVALID_ARGUMENT, "max_mismatches must be at most 2^31");
 }
 

@@ -63,7 +63,7 @@ struct IndexConfig {
     BuildOptions build;
 };
 
-struct Narrow32Sink;  // (below)
+struct HostCall;  // (below)
 
 class FmIndex {
 public:
@@ -133,6 +133,8 @@ public:
     // reversed (device, n, number of texts, alphabet and count array agree), with GDX_ERR_UNSUPPORTED when the two have
     // different occurrence-table layouts
     void check_companion(const FmIndex &reversed) const;
+    // what every call refuses whose queries are packed (2-bit codes) when the index's kernels cannot read them
+    void check_packed_supported() const { gdx::check_packed_supported(view_); }
     // gdx_smems_many: the whole batch staged (copy in, one launch, copy out)
     int smems_many(const FmIndex &reversed, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint32_t max_smems,
                    uint32_t min_length, uint32_t *out_n_smems, uint32_t *out_remaining, uint32_t *out_begin, uint32_t *out_length,
@@ -199,10 +201,10 @@ public:
 private:
     FmIndex() = default;
     // chunked, three-deep pipeline behind the host-pointer query calls (host_api.hip)
-    int host_pipeline(int kind, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint64_t *out_a, uint64_t *out_b,
-                      uint8_t *out_status, gdx_hit_t *hits, uint64_t hits_capacity, uint64_t *out_total,
-                      const std::function<gdx_hit_t *(uint64_t, uint64_t *)> *grow_hits, bool packed = false,
-                      uint64_t uniform_len = 0, Narrow32Sink *narrow = nullptr) const;
+    int host_pipeline(const HostCall &call) const;
+    // a wide locate (HostCall::Kind::kLocate) through the pipeline, run once more on the plain path when a chunk's hits do not
+    // fit the fused step's 32-bit offsets; refresh: sets the call's hit array anew before that second run
+    int locate_wide(HostCall call, const std::function<void(HostCall &)> &refresh = {}) const;
     void finish_from_bwt(const uint8_t *d_bwt_padded, hipStream_t stream);  // table + lookup + view
     void build_aux(const uint8_t *d_bwt_padded, hipStream_t stream);        // pair lines, jump table, top table
     void build_seed_table(const uint32_t *d_sa, uint32_t k, uint32_t load_percent, hipStream_t stream, uint64_t room_bytes);
@@ -352,6 +354,34 @@ struct Narrow32Sink {
     uint64_t cap = 0;             // hits the array holds
     // a larger array holding the first `keep` hits of the old one (called with no copy into the old one on its way)
     std::function<gdx_hit32_t *(uint64_t need, uint64_t keep, uint64_t *new_cap)> grow;
+};
+// one host-pointer query call as the pipeline takes it (FmIndex::host_pipeline): the batch, what is asked for, where it goes
+struct HostCall {
+    enum class Kind { kIntervals, kCounts, kLocate, kLocate32 };  // kLocate: u64 offsets, 16-byte hits; kLocate32: the narrow sink
+    Kind kind = Kind::kCounts;
+    // the queries.  packed: qbuf holds 2-bit codes (symbol j in bits 2 (j & 3) of byte j >> 2) and qoff counts symbols.
+    // uniform_len != 0: query i = symbols [i * uniform_len, (i + 1) * uniform_len) of the buffer, qoff is not looked at: no
+    // offsets are staged, copied or read by the kernels (gdx_query_layout_t)
+    const uint8_t *qbuf = nullptr;
+    const uint64_t *qoff = nullptr;
+    uint64_t nq = 0;
+    bool packed = false;
+    uint64_t uniform_len = 0;
+    // the results; each may be null
+    uint64_t *out_start = nullptr, *out_end = nullptr;  // kIntervals: nq each
+    uint64_t *out_count = nullptr;                      // kCounts: nq
+    uint64_t *out_hit_offsets = nullptr;                // kLocate: nq + 1
+    uint8_t *out_status = nullptr;                      // nq
+    gdx_hit_t *hits = nullptr;                          // kLocate: hits / hits_capacity / out_total as in gdx_locate_many
+    uint64_t hits_capacity = 0;
+    uint64_t *out_total = nullptr;                      // kLocate, kLocate32
+    // kLocate, optional: asked for room (at least `need` hits; returns the array and its capacity) when the library manages the
+    // caller's buffer (gdx_locate_many_alloc)
+    const std::function<gdx_hit_t *(uint64_t need, uint64_t *new_cap)> *grow_hits = nullptr;
+    Narrow32Sink *narrow = nullptr;  // kLocate32: required
+    // kLocate: take the plain path (u64 offsets throughout) whatever the environment says -- the second run of a call whose
+    // chunk had more hits than the fused step's 32-bit offsets hold
+    bool plain_locate_only = false;
 };
 // parser threads of the mapped FASTA / FASTQ reader (fastx.hpp): the CPUs the process may use, at most 32 (host_api.hip)
 unsigned fastx_default_threads();

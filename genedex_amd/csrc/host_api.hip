@@ -1,8 +1,8 @@
-// host_api.hip -- the host-pointer query calls (gdx_count_many, gdx_cursors_for_many_queries, gdx_locate_many):
+// host_api.hip -- the host-pointer query calls (gdx_count_many, gdx_cursors_for_many_queries, gdx_locate_many[_alloc][_layout][32]):
 // FmIndex::count_many / cursors_for_many_queries / locate_many of the reference (lib.rs:155-185) for callers whose
 // queries and results live in host memory.
 //
-// A call is a pipeline over chunks of the batch, four chunks in flight, three host threads:
+// A call is a pipeline over chunks of the batch, four chunks in flight (Slot), three host threads (ThreeStageRunner):
 //
 //     feeder thread + workers: user memory -> pinned staging  |  H2D (copy-in stream)  |  kernels (compute stream)
 //     calling thread: waits for a chunk's search (locate: its number of hits), enqueues locate and the copies out
@@ -10,11 +10,13 @@
 //                                                                                         pinned -> the user's arrays
 //
 // so that the PCIe transfers of chunk k + 1 / k - 1 run beside the kernels of chunk k and a call costs about
-// max(H2D time, D2H time, kernel time) instead of their sum.  Counts and interval borders travel narrow (u32) and are
-// widened by the host threads while they copy; so do the hits of a locate since round 4 (8-byte gdx_hit32_t over PCIe,
-// 16-byte gdx_hit_t in the caller's array; round 3 shipped them wide, when 58 bytes per read came in and the D2H link had
-// room -- with reads as 2-bit codes, 12.5 bytes in, the results are the longer leg); the chunk's hit offsets stay u64.  The
-// host cores of a container often do not.  Results are order preserving: chunk boundaries are invisible to the caller.
+// max(H2D time, D2H time, kernel time) instead of their sum.  Results are order preserving: chunk boundaries are invisible
+// to the caller.
+//
+// How it reads: a call site names its batch and outputs in a HostCall (fm_index.hpp); make_host_plan resolves it, with the
+// index and the environment, into a HostPlan -- one of five result paths (enum Path: what crosses the link in which form is
+// said there), the chunk list and the wire layout (host_plan.hpp), the sizes; fill_slots gives every slot the buffers of
+// that path; the three stages (stage_in, stage_mid, stage_out) each dispatch over the path to one short function per path.
 #include <malloc.h>
 
 #include <algorithm>
@@ -30,6 +32,7 @@
 #include <sys/mman.h>
 
 #include "fm_index.hpp"
+#include "host_plan.hpp"
 #include "kernels.hpp"
 #include "pack_host.hpp"
 #include "wire_host.hpp"
@@ -281,8 +284,6 @@ void check_queries(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, Worke
     if (qoff[nq] > qoff[0] && !qbuf) fail(GDX_ERR_INVALID_ARGUMENT, "qbuf is null");
 }
 
-enum class Kind { kIntervals, kCounts, kLocate, kLocate32 };
-
 // every slot's u32 offsets (entries 1 .. n of a chunk) shifted by the hits of the chunks before it
 __global__ __launch_bounds__(256) void add_hit_base_kernel(uint32_t *__restrict__ off, uint64_t n, uint32_t base)
 {
@@ -302,14 +303,9 @@ bool is_pinned_host(const void *p)
     return attr.type == hipMemoryTypeHost;
 }
 
-struct Chunk {
-    uint64_t q0 = 0, nq = 0, bytes = 0, total = 0, hit_base = 0;
-};
-
-// A chunk of the wide locate calls whose hits do not fit the fused step's 32-bit offsets: the call is run again with the
-// device-written results of rounds 1-4 (u64 offsets throughout), which have no such limit (host_pipeline, locate_many*)
+// A chunk of the wide locate calls whose hits do not fit the fused step's 32-bit offsets: the call is run again on the plain
+// path (u64 offsets throughout), which has no such limit (FmIndex::locate_wide)
 struct RetryWithWideOffsets {};
-thread_local bool t_force_plain_locate = false;
 // (tests: GDX_TEST_CHUNK_HIT_LIMIT lowers the number of hits a chunk of the fused step may hold; read per call)
 uint64_t chunk_hit_limit()
 {
@@ -317,642 +313,807 @@ uint64_t chunk_hit_limit()
     const uint64_t v = e ? std::strtoull(e, nullptr, 10) : 0;
     return v != 0 ? v : 0xffffffffull;
 }
-
-}  // namespace
-
-// The pipeline behind all three calls.  Intervals: out_a = start, out_b = end.  Counts: out_a = counts.  Locate:
-// out_a = hit offsets (nq + 1), hits / hits_capacity / out_total as in gdx_locate_many; grow_hits (optional) is asked
-// for room when the caller's buffer is managed by the library (gdx_locate_many_alloc).
-int FmIndex::host_pipeline(int kind_i, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint64_t *out_a,
-                           uint64_t *out_b, uint8_t *out_status, gdx_hit_t *hits, uint64_t hits_capacity,
-                           uint64_t *out_total, const std::function<gdx_hit_t *(uint64_t, uint64_t *)> *grow_hits,
-                           bool packed, uint64_t uniform_len, Narrow32Sink *narrow) const
+// GDX_HOST_TIMING=1 (debug): where the three threads spend the call, in seconds
+bool host_timing()
 {
-    // packed: qbuf holds 2-bit codes (symbol j in bits 2 (j & 3) of byte j >> 2) and qoff counts symbols
-    // uniform_len != 0: query i = symbols [i * uniform_len, (i + 1) * uniform_len) of the buffer, qoff is not looked at: no
-    // offsets are staged, copied or read by the kernels (gdx_query_layout_t)
-    const Kind kind = static_cast<Kind>(kind_i);
-    // Locate calls: by default a chunk's results do not cross the link as offsets and hits but as the "found bitmap" wire the
-    // multi-GPU gather uses (launch_wire_pack: a bit per read, position + text id byte per found read, the exceptions with their
-    // hits -- 3.7-4.6 bytes per read instead of 12.2 narrow / 16.2 wide), and the drainer's workers expand them into the
-    // caller's arrays (wire_host.hpp): the link's two directions share its rate (65 GB/s together on the test box against 57
-    // alone), so bytes saved going out are time saved.  GDX_HOST_RESULTS=dma: the device-written forms (hosts with few cores
-    // to spare).  Collections of more than 256 texts take those too (text ids travel as bytes).
+    static const bool timing = getenv("GDX_HOST_TIMING") != nullptr;
+    return timing;
+}
+
+using Kind = HostCall::Kind;
+
+// ---- the plan of a call: its result path, chunks and sizes, resolved once ----------------------------------------------------
+// How a chunk's results cross the link and reach the caller's arrays:
+//   kIntervals, kCounts  search; u32 borders / counts by D2H copy, widened by the drainer; the status bytes stay on the device
+//                        unless one of the chunk's is set
+//   kPlainLocate         search | the chunk's total to the host | locate; u64 offsets and 8-byte hits (GDX_HOST_WIDE_HITS=1: 16-byte
+//                        hits, the drainer then only copies) by D2H copy, shifted and widened by the drainer.  The wide calls when
+//                        the wire is off, their sizing call (no hit buffer: the locate launch is skipped) and their second run
+//   kStepDma             every chunk is ONE fused step (launch_locate_step: search, totals, u32 offsets, 8-byte hits, no host round
+//                        trip); offsets and hits go by D2H copy straight into the pinned arrays of the sink (narrow call only)
+//   kStepWire            the fused step, then the "found bitmap" wire the multi-GPU gather uses (launch_wire_pack: a bit per read,
+//                        position + text id byte per found read, the exceptions with their hits -- 3.7-4.6 bytes per read instead of
+//                        12.2 narrow / 16.2 wide), expanded into the caller's arrays by the drainer's workers (wire_host.hpp): the
+//                        link's two directions share its rate (65 GB/s together on the test box against 57 alone), so bytes saved
+//                        going out are time saved.  The default of the narrow and the wide locate calls.  GDX_HOST_RESULTS=dma: the
+//                        device-written forms (hosts with few cores to spare).  Collections of more than 256 texts take those too
+//                        (text ids travel as bytes).
+enum class Path { kIntervals, kCounts, kPlainLocate, kStepDma, kStepWire };
+
+struct HostPlan {
+    Path path = Path::kCounts;
+    bool flagged = false;       // kIntervals, kCounts
+    bool stepped = false;       // kStepDma, kStepWire
+    bool sizing_only = false;   // gdx_locate_many without a hit buffer: search, totals and offsets only
+    bool host_pack = false;     // ASCII chunks are packed by the feeder's workers and cross the link as 2-bit codes
+    bool pinned_input = false;  // the caller's query buffer is pinned: no staging copy
+    bool wide_hits = false;     // kPlainLocate: 16-byte hits from the device (GDX_HOST_WIDE_HITS=1)
+    size_t hit_bytes = 0;       // kPlainLocate: of a hit on the link
+    PackPlan pack_plan;
+    uint64_t hit_limit = 0;     // hits a chunk of the fused step may hold (wide calls)
+    unsigned in_threads = 1;    // workers of the feeder
+    std::vector<HostChunk> chunks;
+    uint64_t max_nq = 0, qbuf_cap = 0;  // the largest chunk's queries, and the bytes a slot's query buffer holds
+    uint64_t n32_cap = 0;               // stepped: hit slots a chunk's device buffers hold
+    WireLayout wl;
+};
+
+// (call, index, environment) -> plan; the batch is checked on the way (check_queries).  nq == 0: no chunks.
+HostPlan make_host_plan(const HostCall &call, const FmIndex &ix, WorkerPool &pool)
+{
     static const int narrow_mode = [] {
         const char *e = getenv("GDX_HOST_RESULTS");
         if (e && std::strcmp(e, "dma") == 0) return 0;
         if (e && std::strcmp(e, "wire") == 0) return 1;
         return host_threads() >= 4 ? 1 : 0;
     }();
-    // A sizing call of gdx_locate_many (no hit buffer): search, totals and offsets only -- nothing is located, packed or copied out
-    // that the call would throw away (round-5 advisor); it takes the plain path, whose locate launch is then skipped
-    const bool sizing_only = kind == Kind::kLocate && grow_hits == nullptr && (hits == nullptr || hits_capacity == 0);
-    const bool wire = (kind == Kind::kLocate32 || kind == Kind::kLocate) && narrow_mode == 1 && n_texts_ <= 256 && !sizing_only &&
-                      !(kind == Kind::kLocate && t_force_plain_locate);
-    // stepped: every chunk is ONE fused step (launch_locate_step: search, totals, u32 offsets, 8-byte hits, no host round trip)
-    const bool stepped = kind == Kind::kLocate32 || (kind == Kind::kLocate && wire);
-    const bool plain_locate = kind == Kind::kLocate && !stepped;  // search | total to the host | locate, u64 offsets (rounds 1-4)
-    const bool pinned_input = is_pinned_host(qbuf);
-    // (more than host_threads() workers did not shorten the expansion -- 13 ms of a 100 M-read call with 7 workers, 11 with 13 --
-    // and starved the runtime's own threads on a 16-CPU container)
-    WorkerPool pool(host_threads());
-    check_queries(qbuf, qoff, nq, pool, uniform_len);
+    const IndexView &view = ix.view();
+    const Kind kind = call.kind;
+    const bool locate = kind == Kind::kLocate || kind == Kind::kLocate32;
+    HostPlan p;
+    // A sizing call of gdx_locate_many: nothing is located, packed or copied out that the call would throw away
+    p.sizing_only = kind == Kind::kLocate && call.grow_hits == nullptr && (call.hits == nullptr || call.hits_capacity == 0);
+    const bool wire = locate && narrow_mode == 1 && ix.num_texts() <= 256 && !p.sizing_only && !(kind == Kind::kLocate && call.plain_locate_only);
+    p.flagged = !locate;
+    p.stepped = kind == Kind::kLocate32 || wire;
+    p.path = kind == Kind::kIntervals ? Path::kIntervals
+             : kind == Kind::kCounts  ? Path::kCounts
+             : !p.stepped             ? Path::kPlainLocate
+                                      : (wire ? Path::kStepWire : Path::kStepDma);
+    p.pinned_input = is_pinned_host(call.qbuf);
+    check_queries(call.qbuf, call.qoff, call.nq, pool, call.uniform_len);
     // ASCII batches of the count / locate calls are packed ON THE HOST, chunk by chunk in the feeder's worker pool (pack_host.hpp:
     // 32 symbols per step when the alphabet's table has a nucleotide alphabet's shape), and cross the link as 2-bit codes -- 12.5
     // bytes per len-50 read (+ 8 of offsets) instead of 58: the link, not the kernels, bounds these calls.  A chunk that holds a
     // symbol 2 bits cannot name (N, an invalid byte) goes as it is, ASCII, and gives the reference's result for it.  Exact
     // intervals stay ASCII (their kernels read bytes).  GDX_HOST_PACK=0: never.
     const bool env_host_pack = [] { const char *e = getenv("GDX_HOST_PACK"); return !(e && atoi(e) == 0); }();  // (read per call: tests)
-    const PackPlan pack_plan = make_pack_plan(cfg_.io_to_dense);
-    const bool host_pack = !packed && env_host_pack && kind != Kind::kIntervals && view_.layout == 0 && view_.n_searchable >= 4 &&
-                           pack_plan.fast && pack_have_avx2();
-    const bool uniform = uniform_len != 0;
-    auto off_of = [&](uint64_t i) { return uniform ? i * uniform_len : qoff[i]; };
-    if (out_total) *out_total = 0;
-    if (kind == Kind::kLocate && out_a) out_a[0] = 0;
-    if (kind == Kind::kLocate32 && narrow != nullptr && narrow->offsets != nullptr) narrow->offsets[0] = 0;
-    if (nq == 0) return GDX_OK;
-    make_current();
-    const int dev = cfg_.device_id;
-    const QueryOptions qo = query_options();
-    Streams st;
-
-    // chunk boundaries: at most kChunkBytes of query bytes and kChunkQueries queries each
-    // (a chunk's limit counts the bytes that cross the link: four symbols per byte of a packed batch; the narrow locate runs a
-    // whole fused step per chunk, a dozen launches, and takes up to four times the queries)
-    const uint64_t kChunkBytes = g_chunk_bytes.load() * ((packed || host_pack) ? 4 : 1), kChunkQueries = g_chunk_queries.load() * (stepped ? 4 : 1);
-    std::vector<Chunk> chunks;
-    // (uniform: every chunk but the last holds a multiple of 8 queries, so that a chunk starts on a 16-bit unit of a packed
-    // buffer and on a byte of an ASCII one, and is a uniform batch of its own)
-    const uint64_t uniform_chunk = uniform ? std::max<uint64_t>(8, std::min(kChunkQueries, kChunkBytes / uniform_len) / 8 * 8) : 0;
-    for (uint64_t q0 = 0; q0 < nq;) {
-        uint64_t hi = std::min(nq, q0 + (uniform ? uniform_chunk : kChunkQueries));
-        if (!uniform && qoff[hi] - qoff[q0] > kChunkBytes) {
-            const uint64_t *p = std::upper_bound(qoff + q0 + 1, qoff + hi + 1, qoff[q0] + kChunkBytes);
-            hi = static_cast<uint64_t>(p - qoff) - 1;
-            if (hi <= q0) hi = q0 + 1;  // a single query longer than a chunk
-        }
-        Chunk c;
-        c.q0 = q0;
-        c.nq = hi - q0;
-        c.bytes = off_of(hi) - off_of(q0);
-        chunks.push_back(c);
-        q0 = hi;
-    }
-    const size_t n_chunks = chunks.size();
-    uint64_t max_nq = 0, max_bytes = 0;
-    for (const Chunk &c : chunks) {
-        max_nq = std::max(max_nq, c.nq);
-        max_bytes = std::max(max_bytes, c.bytes);
-    }
-    // (packed: max_bytes counts symbols, four per byte, and a chunk starts up to seven symbols before its first query)
-    const uint64_t qbuf_cap = div_ceil((packed ? div_ceil(max_bytes + 8, 4) : max_bytes) + 1, 8) * 8 + 24;
-
-    // per-slot buffers (ids: slot * 16 + n)
-    uint8_t *h_in[kSlots], *d_qbuf[kSlots], *h_status[kSlots], *d_status[kSlots];
-    uint64_t *h_qoff[kSlots], *d_qoff[kSlots], *d_off[kSlots];
-    uint32_t *h_a[kSlots], *h_b[kSlots], *d_a[kSlots], *d_b[kSlots];
-    uint4 *d_rec[kSlots];
-    uint64_t *h_total[kSlots];
-    void *d_scan[kSlots];
-    size_t scan_bytes = 0;
-    if (plain_locate) scan_bytes = hit_offsets_rec_temp_bytes(max_nq);
-    for (int s = 0; s < kSlots; s++) {
-        h_in[s] = pinned_buf<uint8_t>(dev, s * 16 + 0, qbuf_cap);
-        h_qoff[s] = pinned_buf<uint64_t>(dev, s * 16 + 1, max_nq + 1);
-        h_a[s] = pinned_buf<uint32_t>(dev, s * 16 + 2, max_nq);
-        h_b[s] = kind == Kind::kIntervals ? pinned_buf<uint32_t>(dev, s * 16 + 3, max_nq) : nullptr;
-        h_status[s] = pinned_buf<uint8_t>(dev, s * 16 + 4, max_nq);
-        h_total[s] = pinned_buf<uint64_t>(dev, s * 16 + 5, 1);
-        d_qbuf[s] = device_buf<uint8_t>(dev, s * 16 + 0, qbuf_cap);
-        d_qoff[s] = device_buf<uint64_t>(dev, s * 16 + 1, max_nq + 1);
-        d_a[s] = device_buf<uint32_t>(dev, s * 16 + 2, max_nq);
-        d_b[s] = kind == Kind::kIntervals ? device_buf<uint32_t>(dev, s * 16 + 3, max_nq) : nullptr;
-        d_status[s] = device_buf<uint8_t>(dev, s * 16 + 4, max_nq);
-        d_rec[s] = plain_locate ? device_buf<uint4>(dev, s * 16 + 5, max_nq) : nullptr;
-        d_off[s] = plain_locate ? device_buf<uint64_t>(dev, s * 16 + 6, max_nq + 1) : nullptr;
-        d_scan[s] = plain_locate ? device_buf<uint8_t>(dev, s * 16 + 7, scan_bytes ? scan_bytes : 1) : nullptr;
-    }
-    // stepped: device buffers sized for the chunk's queries and a margin.  Without the wire (narrow call only) the u32 offsets
-    // and 8-byte hits go by D2H copy straight into the caller-visible pinned arrays of the sink
-    uint32_t *d_cmp[kSlots] = {}, *d_off32[kSlots] = {};
-    unsigned long long *d_tot[kSlots] = {};
-    uint64_t n32_cap = 0;  // hit slots a chunk's device buffers hold
-    void *d_hits[kSlots] = {}, *h_hits[kSlots] = {};
-    void *d_ws[kSlots] = {};
-    uint8_t *d_wire[kSlots] = {}, *h_wire[kSlots] = {}, *d_exc[kSlots] = {}, *h_exc[kSlots] = {}, *d_wws[kSlots] = {};
-    uint64_t exc_hits_cap[kSlots] = {}, w_found[kSlots] = {}, w_exc[kSlots] = {}, w_exc_hits[kSlots] = {};
-    bool w_status[kSlots] = {};
-    // a slot's wire: {meta 16 B | bitmap, 256 B per tile | tile_found | tile_off | found_pos} and -- collections of more than one
-    // text -- the found reads' text ids behind it, the same offsets on both sides, so that ONE copy brings everything up to the
-    // last found read's position and one more the ids
-    const bool w_ids = n_texts_ > 1;
-    const uint64_t w_tiles = div_ceil(max_nq, kHostWireTile);
-    const uint64_t w_bitmap = 256, w_tile_found = w_bitmap + w_tiles * 256, w_tile_off = w_tile_found + div_ceil((w_tiles + 1) * 4, 256) * 256,
-                   w_found_pos = w_tile_off + div_ceil((w_tiles + 1) * 4, 256) * 256, w_found_ids = w_found_pos + div_ceil(max_nq * 4 + 4, 256) * 256,
-                   w_bytes = w_found_ids + (w_ids ? max_nq + 1 : 0);
-    const bool flagged = kind == Kind::kCounts || kind == Kind::kIntervals;  // status bytes stay on the device unless one is set
-    if (flagged)
-        for (int s = 0; s < kSlots; s++) {
-            d_tot[s] = device_buf<unsigned long long>(dev, s * 16 + 13, 4);
-            h_total[s] = pinned_buf<uint64_t>(dev, s * 16 + 5, 8);
-        }
-    if (stepped) {
-        if (kind == Kind::kLocate32 && narrow == nullptr) fail(GDX_ERR_INVALID_ARGUMENT, "internal: the narrow locate needs its sink");
-        n32_cap = max_nq + max_nq / 4 + 4096;
-        const size_t tws = scan_totals_workspace_bytes(max_nq);
-        for (int s = 0; s < kSlots; s++) {
-            d_rec[s] = device_buf<uint4>(dev, s * 16 + 5, max_nq);
-            d_cmp[s] = device_buf<uint32_t>(dev, s * 16 + 11, max_nq);
-            d_off32[s] = device_buf<uint32_t>(dev, s * 16 + 12, max_nq + 1);
-            d_tot[s] = device_buf<unsigned long long>(dev, s * 16 + 13, 4);
-            d_scan[s] = device_buf<uint8_t>(dev, s * 16 + 7, tws ? tws : 1);
-            h_total[s] = pinned_buf<uint64_t>(dev, s * 16 + 5, 8);
-            d_hits[s] = device_buf<uint8_t>(dev, s * 16 + 8, n32_cap * sizeof(gdx_hit32_t));
-            d_ws[s] = device_buf<uint8_t>(dev, s * 16 + 9, locate_workspace_bytes(n32_cap));
-            if (wire) {
-                d_wire[s] = device_buf<uint8_t>(dev, s * 16 + 14, w_bytes);
-                h_wire[s] = pinned_buf<uint8_t>(dev, s * 16 + 7, w_bytes);
-                exc_hits_cap[s] = n32_cap;
-                d_exc[s] = device_buf<uint8_t>(dev, s * 16 + 15, max_nq * 8 + exc_hits_cap[s] * sizeof(gdx_hit32_t));
-                d_wws[s] = device_buf<uint8_t>(dev, s * 16 + 10, wire_pack_workspace_bytes(max_nq));
-            }
-        }
-    }
-    // (the exceptions of a slot: {read numbers | counts | hits}, max_nq entries of the first two)
-    auto pack_wire = [&](int s, uint64_t chunk_nq) {
-        uint8_t *w = d_wire[s], *e = d_exc[s];
-        WireHostForm hf;
-        hf.d_exc_hits32 = reinterpret_cast<gdx_hit32_t *>(e + max_nq * 8);
-        hf.d_tile_off = reinterpret_cast<uint32_t *>(w + w_tile_off);
-        hf.d_found_ids = w_ids ? w + w_found_ids : nullptr;
-        hf.ix = &view_;
-        hf.hits_stored = exc_hits_cap[s];
-        launch_wire_pack(d_cmp[s], d_off32[s], true, static_cast<const gdx_hit32_t *>(d_hits[s]), chunk_nq, w + w_bitmap,
-                         reinterpret_cast<uint32_t *>(w + w_tile_found), reinterpret_cast<uint32_t *>(w + w_found_pos), max_nq,
-                         reinterpret_cast<uint32_t *>(e), reinterpret_cast<uint32_t *>(e + max_nq * 4), max_nq, nullptr, nullptr,
-                         exc_hits_cap[s], reinterpret_cast<uint32_t *>(w), d_wws[s], st.k, &hf);
-        GDX_HIP(hipGetLastError());
-        GDX_HIP(hipMemcpyAsync(h_total[s] + 4, w, 16, hipMemcpyDeviceToHost, st.k));
-    };
-    uint64_t *h_off[kSlots] = {};  // locate: the chunk's hit offsets (h_off[i] = hits of its queries before query i)
-    if (plain_locate)
-        for (int s = 0; s < kSlots; s++) h_off[s] = pinned_buf<uint64_t>(dev, s * 16 + 10, max_nq + 1);
+    p.pack_plan = make_pack_plan(ix.config().io_to_dense);
+    p.host_pack = !call.packed && env_host_pack && kind != Kind::kIntervals && view.layout == 0 && view.n_searchable >= 4 &&
+                  p.pack_plan.fast && pack_have_avx2();
+    if (call.nq == 0) return p;
+    if (kind == Kind::kLocate32 && call.narrow == nullptr) fail(GDX_ERR_INVALID_ARGUMENT, "internal: the narrow locate needs its sink");
     // hits leave the device NARROW (gdx_hit32_t, 8 bytes) and are widened into the ABI's 16-byte gdx_hit_t by the drainer's
     // workers: with reads handed over as 2-bit codes the D2H link is the longer leg of a locate call (23 bytes per read out
-    // against 12.5 in), and the drainer reads half as much from the staging buffer.  GDX_HOST_WIDE_HITS=1: 16-byte hits from
-    // the device as in round 3 (the drainer then only copies)
+    // against 12.5 in), and the drainer reads half as much from the staging buffer
     static const bool wide_hits = [] { const char *e = getenv("GDX_HOST_WIDE_HITS"); return e && atoi(e) != 0; }();
-    const size_t hit_bytes = wide_hits ? sizeof(gdx_hit_t) : sizeof(gdx_hit32_t);
-
-    std::atomic<bool> any_status{false};
-    uint64_t hit_base = 0;    // hits of the chunks drained so far
-    bool capacity_ok = true;  // locate: the caller's buffer holds everything so far
-
-    // user memory -> pinned staging -> device, search (+ scan, total) enqueued; runs on the feeder thread
-    auto stage_in_with = [&](size_t k, WorkerPool &pool) {
-        const int s = static_cast<int>(k % kSlots);
-        Chunk &c = chunks[k];
-        bool as_packed = packed, packed_here = false;  // packed_here: the chunk's codes were made by this thread's workers, in h_in
-        uint64_t chunk_uniform = uniform ? uniform_len : 0;  // != 0: every query of the chunk has this many symbols
-        if (host_pack && c.bytes != 0) {
-            // the chunk's symbols are packed from ITS first symbol on (symbol j of the chunk in bits 2 (j & 3) of byte j >> 2)
-            const uint64_t first = off_of(c.q0), n_sym = off_of(c.q0 + c.nq) - first, nb = div_ceil(n_sym, 4);
-            std::atomic<bool> other{false};  // a symbol that is not one of the dense codes 1..4
-            std::atomic<bool> ragged{false};
-            const uint64_t len0 = uniform ? uniform_len : qoff[c.q0 + 1] - qoff[c.q0];
-            uint8_t *out = h_in[s];
-            pool.run([&](unsigned w, unsigned nw) {
-                const uint64_t per = (nb / nw + 64) / 64 * 64;
-                const uint64_t lo = std::min(nb, per * w), hi = std::min(nb, lo + per);
-                pack_range(pack_plan, cfg_.io_to_dense, qbuf + first, 0, n_sym, lo, hi, out,
-                           [&](uint64_t) { other.store(true, std::memory_order_relaxed); });
-                // reads of one length (a sequencer's) need no offsets at all: neither rebased, nor copied, nor read by the kernels
-                if (!uniform && len0 != 0) {
-                    const uint64_t qper = div_ceil(c.nq, nw), q_lo = std::min(c.nq, qper * w), q_hi = std::min(c.nq, q_lo + qper);
-                    bool same = true;
-                    for (uint64_t i = q_lo; i < q_hi; i++) same &= qoff[c.q0 + i + 1] - qoff[c.q0 + i] == len0;
-                    if (!same) ragged.store(true, std::memory_order_relaxed);
-                }
-            });
-            as_packed = packed_here = !other.load();
-            if (packed_here && !uniform && len0 != 0 && len0 < (1ull << 21) && !ragged.load()) chunk_uniform = len0;
-        }
-        // packed (by the caller): the chunk starts at the 16-bit unit that holds its first symbol, offsets are rebased to that unit
-        const uint64_t base = (as_packed && !packed_here) ? (off_of(c.q0) & ~7ull) : off_of(c.q0);
-        const uint64_t src_byte = as_packed ? base / 4 : base;
-        const uint64_t n_bytes = as_packed ? div_ceil(off_of(c.q0 + c.nq) - base, 4) : c.bytes;
-        if (!pinned_input && !packed_here)
-            pool.parallel_range(n_bytes, 64, [&](uint64_t lo, uint64_t hi) { stream_copy(h_in[s] + lo, qbuf + src_byte + lo, hi - lo); });
-        if (chunk_uniform == 0)
-            pool.parallel_range(c.nq + 1, 8, [&](uint64_t lo, uint64_t hi) {
-                for (uint64_t i = lo; i < hi; i++) h_qoff[s][i] = qoff[c.q0 + i] - base;
-            });
-        const uint64_t padded = div_ceil(n_bytes + 2, 8) * 8;
-        if (pinned_input && !packed_here) {  // the caller's buffer is pinned: the device reads it as it is, no staging copy
-            if (n_bytes) GDX_HIP(hipMemcpyAsync(d_qbuf[s], qbuf + src_byte, n_bytes, hipMemcpyHostToDevice, st.in));
-            GDX_HIP(hipMemsetAsync(d_qbuf[s] + n_bytes, 0, padded - n_bytes, st.in));  // windows may read past the last query
-        } else {
-            std::memset(h_in[s] + n_bytes, 0, padded - n_bytes);
-            GDX_HIP(hipMemcpyAsync(d_qbuf[s], h_in[s], padded, hipMemcpyHostToDevice, st.in));
-        }
-        if (chunk_uniform == 0) GDX_HIP(hipMemcpyAsync(d_qoff[s], h_qoff[s], (c.nq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st.in));
-        GDX_HIP(hipEventRecord(st.ev_in[s], st.in));
-        GDX_HIP(hipStreamWaitEvent(st.k, st.ev_in[s], 0));
-        SearchCall call;
-        call.d_qbuf = d_qbuf[s];
-        if (chunk_uniform != 0) {  // (base == the chunk's first symbol: the chunk is a uniform batch of its own)
-            call.uniform_len = static_cast<uint32_t>(chunk_uniform);
-        } else {
-            call.d_qbeg = d_qoff[s];
-            call.d_qend = d_qoff[s] + 1;
-        }
-        call.nq = c.nq;
-        call.packed = as_packed;
-        if (stepped) {
-            LocateStep step;
-            step.call = call;
-            step.call.d_rec = d_rec[s];
-            step.call.d_compact = d_cmp[s];
-            step.max_hits = qo.max_hits_per_query;
-            step.take = true;  // locate(q).take(k)
-            step.d_scan_workspace = d_scan[s];
-            step.d_totals = d_tot[s];
-            step.d_hit_offsets = d_off32[s];
-            step.narrow = true;
-            step.d_hits = d_hits[s];  // (sized for n32_cap hit slots; a chunk with more takes the second half again, stage_mid)
-            step.hits_capacity = n32_cap;
-            step.d_workspace = d_ws[s];
-            GDX_HIP(hipMemsetAsync(d_tot[s] + 2, 0, sizeof(unsigned long long), st.k));
-            launch_locate_step(view_, step, st.k, qo);
-            GDX_HIP(hipGetLastError());
-            launch_unpack_records(d_rec[s], c.nq, nullptr, d_status[s], st.k, d_cmp[s], d_tot[s] + 2);
-            GDX_HIP(hipMemcpyAsync(h_total[s], d_tot[s], 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, st.k));
-            if (wire) pack_wire(s, c.nq);
-            GDX_HIP(hipEventRecord(st.ev_total[s], st.k));
-            return;
-        }
-        if (kind == Kind::kIntervals) {
-            call.d_start = d_a[s];
-            call.d_end = d_b[s];
-            call.d_status = d_status[s];
-            call.mode = 0;
-        } else if (kind == Kind::kCounts) {
-            call.d_count = d_a[s];
-            call.d_status = d_status[s];
-            call.mode = 1;
-        } else {
-            call.d_rec = d_rec[s];
-            call.mode = 1;
-        }
-        launch_search_call(view_, call, st.k, qo);
-        GDX_HIP(hipGetLastError());
-        if (plain_locate) {
-            const unsigned blocks = static_cast<unsigned>(std::min<uint64_t>((c.nq + 255) / 256, 4096));
-            hipLaunchKernelGGL(unpack_status_kernel, dim3(blocks), dim3(256), 0, st.k, d_rec[s], c.nq, d_status[s]);
-            // (max_hits_per_query: a query gets slots for its first k rows only -- locate(q).take(k))
-            launch_hit_offsets_rec(d_rec[s], c.nq, d_off[s], d_scan[s], scan_bytes, st.k, qo.max_hits_per_query, true);
-            GDX_HIP(hipMemcpyAsync(h_total[s], d_off[s] + c.nq, sizeof(uint64_t), hipMemcpyDeviceToHost, st.k));
-            GDX_HIP(hipEventRecord(st.ev_total[s], st.k));
-        } else {
-            GDX_HIP(hipEventRecord(st.ev_k[s], st.k));
-            GDX_HIP(hipMemsetAsync(d_tot[s], 0, sizeof(unsigned long long), st.k));
-            hipLaunchKernelGGL(any_status_kernel, dim3(static_cast<unsigned>(std::min<uint64_t>(c.nq / 4096 + 1, 1024))), dim3(256), 0, st.k,
-                               d_status[s], c.nq, d_tot[s]);
-            GDX_HIP(hipMemcpyAsync(h_total[s], d_tot[s], sizeof(uint64_t), hipMemcpyDeviceToHost, st.k));
-            GDX_HIP(hipEventRecord(st.ev_total[s], st.k));
-        }
-    };
-
-    uint64_t mid_hit_base = 0;  // narrow locate: hits of the chunks whose copies out are enqueued
-    auto stage_mid = [&](size_t k) {  // locate: the chunk's total is known -> locate, then all D2H; else just D2H
-        const int s = static_cast<int>(k % kSlots);
-        Chunk &c = chunks[k];
-        if (stepped) {
-            GDX_HIP(hipEventSynchronize(st.ev_total[s]));
-            c.total = h_total[s][0];
-            const uint64_t rest = h_total[s][1];
-            if (kind == Kind::kLocate32 && mid_hit_base + c.total >= (1ull << 32))
-                fail(GDX_ERR_CAPACITY, "more than 2^32 - 1 hits: 32-bit hit offsets do not hold them (gdx_locate_many_alloc_layout does)");
-            if (c.total >= chunk_hit_limit() && kind == Kind::kLocate) throw RetryWithWideOffsets{};  // (the wide call has no such limit)
-            if (c.total >= 0xffffffffull)  // (the step counts a chunk's hit slots in 32 bits)
-                fail(GDX_ERR_CAPACITY, "%llu queries of the batch have %llu hits, more than a chunk's 32-bit offsets hold: cap them "
-                     "(gdx_query_options_t.max_hits_per_query), or take the device-written results (environment GDX_HOST_RESULTS=dma)",
-                     static_cast<unsigned long long>(c.nq), static_cast<unsigned long long>(c.total));
-            if (c.total > n32_cap) {  // rare: more hits than the chunk's buffers were sized for -- the second half again, with room
-                d_hits[s] = device_buf<uint8_t>(dev, s * 16 + 8, c.total * sizeof(gdx_hit32_t));
-                d_ws[s] = device_buf<uint8_t>(dev, s * 16 + 9, locate_workspace_bytes(c.total));
-                launch_offsets_hits(view_, d_rec[s], d_cmp[s], c.nq, qo.max_hits_per_query, true, d_scan[s], d_off32[s], true, c.total, rest,
-                                    d_hits[s], d_ws[s], st.k, qo);
-                GDX_HIP(hipGetLastError());
-                if (wire) {  // and the wire again, from the complete hits
-                    exc_hits_cap[s] = c.total;
-                    d_exc[s] = device_buf<uint8_t>(dev, s * 16 + 15, max_nq * 8 + exc_hits_cap[s] * sizeof(gdx_hit32_t));
-                    pack_wire(s, c.nq);
-                    GDX_HIP(hipStreamSynchronize(st.k));
-                }
-            }
-            if (wire) {
-                const uint32_t *meta = reinterpret_cast<const uint32_t *>(h_total[s] + 4);
-                w_exc[s] = meta[0], w_exc_hits[s] = meta[1], w_found[s] = meta[2];
-                w_status[s] = h_total[s][2] != 0;
-                if (w_exc[s] > max_nq || w_exc_hits[s] > exc_hits_cap[s] || w_found[s] + w_exc_hits[s] != c.total)
-                    fail(GDX_ERR_DEVICE, "internal: the wire of a chunk does not add up (%llu found + %llu exception hits, %llu hits)",
-                         static_cast<unsigned long long>(w_found[s]), static_cast<unsigned long long>(w_exc_hits[s]),
-                         static_cast<unsigned long long>(c.total));
-                GDX_HIP(hipEventRecord(st.ev_k[s], st.k));
-                GDX_HIP(hipStreamWaitEvent(st.out, st.ev_k[s], 0));
-                GDX_HIP(hipMemcpyAsync(h_wire[s], d_wire[s], w_found_pos + w_found[s] * 4, hipMemcpyDeviceToHost, st.out));
-                if (w_ids && w_found[s] != 0)
-                    GDX_HIP(hipMemcpyAsync(h_wire[s] + w_found_ids, d_wire[s] + w_found_ids, w_found[s], hipMemcpyDeviceToHost, st.out));
-                if (w_exc[s] != 0) {
-                    h_exc[s] = pinned_buf<uint8_t>(dev, s * 16 + 8, w_exc[s] * 8 + w_exc_hits[s] * sizeof(gdx_hit32_t));
-                    GDX_HIP(hipMemcpyAsync(h_exc[s], d_exc[s], w_exc[s] * 4, hipMemcpyDeviceToHost, st.out));
-                    GDX_HIP(hipMemcpyAsync(h_exc[s] + w_exc[s] * 4, d_exc[s] + max_nq * 4, w_exc[s] * 4, hipMemcpyDeviceToHost, st.out));
-                    if (w_exc_hits[s] != 0)
-                        GDX_HIP(hipMemcpyAsync(h_exc[s] + w_exc[s] * 8, d_exc[s] + max_nq * 8, w_exc_hits[s] * sizeof(gdx_hit32_t),
-                                               hipMemcpyDeviceToHost, st.out));
-                }
-                if (w_status[s]) GDX_HIP(hipMemcpyAsync(h_status[s], d_status[s], c.nq, hipMemcpyDeviceToHost, st.out));
-                GDX_HIP(hipEventRecord(st.ev_out[s], st.out));
-                c.hit_base = mid_hit_base;
-                mid_hit_base += c.total;
-                return;
-            }
-            if (mid_hit_base + c.total > narrow->cap) {  // the pinned hit array moves: nothing may be on its way into the old one
-                GDX_HIP(hipStreamSynchronize(st.out));
-                narrow->hits = narrow->grow(mid_hit_base + c.total, mid_hit_base, &narrow->cap);
-            }
-            if (mid_hit_base != 0)
-                hipLaunchKernelGGL(add_hit_base_kernel, dim3(static_cast<unsigned>(std::min<uint64_t>((c.nq + 255) / 256, 2048))), dim3(256),
-                                   0, st.k, d_off32[s] + 1, c.nq, static_cast<uint32_t>(mid_hit_base));
-            GDX_HIP(hipEventRecord(st.ev_k[s], st.k));
-            GDX_HIP(hipStreamWaitEvent(st.out, st.ev_k[s], 0));
-            GDX_HIP(hipMemcpyAsync(narrow->offsets + c.q0 + 1, d_off32[s] + 1, c.nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st.out));
-            GDX_HIP(hipMemcpyAsync(h_status[s], d_status[s], c.nq, hipMemcpyDeviceToHost, st.out));
-            if (c.total)
-                GDX_HIP(hipMemcpyAsync(narrow->hits + mid_hit_base, d_hits[s], c.total * sizeof(gdx_hit32_t), hipMemcpyDeviceToHost, st.out));
-            GDX_HIP(hipEventRecord(st.ev_out[s], st.out));
-            c.hit_base = mid_hit_base;
-            mid_hit_base += c.total;
-            return;
-        }
-        if (plain_locate) {
-            GDX_HIP(hipEventSynchronize(st.ev_total[s]));
-            c.total = *h_total[s];
-            if (c.total && !sizing_only) {
-                d_hits[s] = device_buf<uint8_t>(dev, s * 16 + 8, c.total * hit_bytes);
-                h_hits[s] = pinned_buf<uint8_t>(dev, s * 16 + 6, c.total * hit_bytes);
-                d_ws[s] = device_buf<uint8_t>(dev, s * 16 + 9, locate_workspace_bytes(c.total));
-                LocateCall loc;
-                loc.d_rec = d_rec[s];
-                loc.m = c.nq;
-                loc.d_hit_offsets = d_off[s];
-                loc.total_hits = c.total;
-                loc.d_hits = d_hits[s];
-                loc.wide = wide_hits;
-                loc.d_workspace = d_ws[s];
-                launch_locate(view_, loc, st.k, qo);
-                GDX_HIP(hipGetLastError());
-            }
-            GDX_HIP(hipEventRecord(st.ev_k[s], st.k));
-        }
-        if (flagged) {
-            GDX_HIP(hipEventSynchronize(st.ev_total[s]));
-            w_status[s] = h_total[s][0] != 0;
-        }
-        GDX_HIP(hipStreamWaitEvent(st.out, st.ev_k[s], 0));
-        if (plain_locate)
-            GDX_HIP(hipMemcpyAsync(h_off[s], d_off[s], (c.nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st.out));
-        else
-            GDX_HIP(hipMemcpyAsync(h_a[s], d_a[s], c.nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st.out));
-        if (kind == Kind::kIntervals)
-            GDX_HIP(hipMemcpyAsync(h_b[s], d_b[s], c.nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st.out));
-        if (!flagged || w_status[s]) GDX_HIP(hipMemcpyAsync(h_status[s], d_status[s], c.nq, hipMemcpyDeviceToHost, st.out));
-        if (plain_locate && c.total && !sizing_only)
-            GDX_HIP(hipMemcpyAsync(h_hits[s], d_hits[s], c.total * hit_bytes, hipMemcpyDeviceToHost, st.out));
-        GDX_HIP(hipEventRecord(st.ev_out[s], st.out));
-    };
-
-    // GDX_HOST_TIMING=1 (debug): where the three threads spend the call, in seconds
-    static const bool timing = getenv("GDX_HOST_TIMING") != nullptr;
-    double t_in_wait = 0, t_in_work = 0, t_mid_wait = 0, t_mid_work = 0, t_out_wait = 0, t_out_work = 0, t_out_sync = 0;
-    auto stage_out = [&](size_t k) {  // pinned staging -> the caller's arrays, widened
-        const int s = static_cast<int>(k % kSlots);
-        Chunk &c = chunks[k];
-        const double t_sync0 = timing ? now_seconds() : 0.0;
-        GDX_HIP(hipEventSynchronize(st.ev_out[s]));
-        if (timing) t_out_sync += now_seconds() - t_sync0;
-        const uint32_t *a = h_a[s], *b = h_b[s];
-        const uint8_t *stt = h_status[s];
-        if (wire) {  // the chunk's wire -> offsets and hits in the caller's arrays, tiles shared out among the workers
-            const uint64_t need = c.hit_base + c.total;
-            const HostWire w{h_wire[s] + w_bitmap,
-                             reinterpret_cast<const uint32_t *>(h_wire[s] + w_tile_found),
-                             reinterpret_cast<const uint32_t *>(h_wire[s] + w_tile_off),
-                             reinterpret_cast<const uint32_t *>(h_wire[s] + w_found_pos),
-                             w_ids ? h_wire[s] + w_found_ids : nullptr,
-                             reinterpret_cast<const uint32_t *>(h_exc[s]),
-                             reinterpret_cast<const uint32_t *>(h_exc[s] + w_exc[s] * 4),
-                             reinterpret_cast<const gdx_hit32_t *>(h_exc[s] + w_exc[s] * 8),
-                             w_exc[s]};
-            const uint64_t tiles = div_ceil(c.nq, kHostWireTile);
-            auto share = [&](unsigned wk, unsigned nw, uint64_t &lo, uint64_t &hi) {
-                const uint64_t per = div_ceil(tiles, nw);
-                lo = std::min<uint64_t>(tiles, per * wk), hi = std::min<uint64_t>(tiles, lo + per);
-            };
-            if (kind == Kind::kLocate32) {
-                if (need > narrow->cap) narrow->hits = narrow->grow(need, c.hit_base, &narrow->cap);  // (only this thread's workers write there)
-                uint32_t *offs = narrow->offsets + c.q0;
-                gdx_hit32_t *hh = narrow->hits;
-                const uint32_t hb = static_cast<uint32_t>(c.hit_base);
-                pool.run([&](unsigned wk, unsigned nw) {
-                    uint64_t lo, hi;
-                    share(wk, nw, lo, hi);
-                    wire_expand_tiles<uint32_t, gdx_hit32_t>(w, c.nq, lo, hi, hb, offs, hh);
-                });
-            } else {  // u64 offsets and 16-byte hits; the hits only while the caller's buffer holds them (gdx_locate_many's sizing pass)
-                if (grow_hits && need > hits_capacity) hits = (*grow_hits)(need, &hits_capacity);  // at least `need`
-                if (!(hits && need <= hits_capacity && capacity_ok)) capacity_ok = false;
-                uint64_t *offs = out_a ? out_a + c.q0 : nullptr;
-                gdx_hit_t *hh = capacity_ok ? hits : nullptr;
-                if (offs != nullptr || hh != nullptr)
-                    pool.run([&](unsigned wk, unsigned nw) {
-                        uint64_t lo, hi;
-                        share(wk, nw, lo, hi);
-                        wire_expand_tiles<uint64_t, gdx_hit_t>(w, c.nq, lo, hi, c.hit_base, offs, hh);
-                    });
-                hit_base = need;
-            }
-        } else if (kind == Kind::kLocate32) {
-            // (offsets and hits are where they belong already)
-        } else if (plain_locate) {
-            c.hit_base = hit_base;
-            if (out_a) {  // the chunk's offsets (scanned on the device) shifted by the hits of the chunks before it
-                const uint64_t *off = h_off[s];
-                const uint64_t shift_by = hit_base;
-                pool.parallel_range(c.nq, 8, [&](uint64_t lo, uint64_t hi) {
-                    for (uint64_t i = lo; i < hi; i++) out_a[c.q0 + i + 1] = off[i + 1] + shift_by;
-                });
-            }
-            const uint64_t need = hit_base + c.total;
-            if (grow_hits && need > hits_capacity) hits = (*grow_hits)(need, &hits_capacity);  // at least `need`
-            if (hits && need <= hits_capacity && capacity_ok && !sizing_only) {
-                gdx_hit_t *dst = hits + hit_base;
-                if (wide_hits) {
-                    const gdx_hit_t *src = static_cast<const gdx_hit_t *>(h_hits[s]);
-                    pool.parallel_range(c.total, 8, [&](uint64_t lo, uint64_t hi) { std::memcpy(dst + lo, src + lo, (hi - lo) * sizeof(gdx_hit_t)); });
-                } else {
-                    const gdx_hit32_t *src = static_cast<const gdx_hit32_t *>(h_hits[s]);
-                    pool.parallel_range(c.total, 8, [&](uint64_t lo, uint64_t hi) {
-                        for (uint64_t i = lo; i < hi; i++) {
-                            dst[i].text_id = src[i].text_id;
-                            dst[i].position = src[i].position;
-                        }
-                    });
-                }
-            } else {
-                capacity_ok = false;
-            }
-            hit_base = need;
-        } else {
-            pool.parallel_range(c.nq, 8, [&](uint64_t lo, uint64_t hi) {
-                if (out_a) widen_u32(a + lo, hi - lo, out_a + c.q0 + lo);
-                if (out_b) widen_u32(b + lo, hi - lo, out_b + c.q0 + lo);
-            });
-        }
-        if ((wire || flagged) && !w_status[s]) {  // (no read of the chunk has a status: the bytes stayed on the device)
-            if (out_status) pool.parallel_range(c.nq, 64, [&](uint64_t lo, uint64_t hi) { std::memset(out_status + c.q0 + lo, 0, hi - lo); });
-            return;
-        }
-        pool.parallel_range(c.nq, 64, [&](uint64_t lo, uint64_t hi) {
-            bool any = false;
-            for (uint64_t i = lo; i < hi; i++) any |= stt[i] != 0;
-            if (out_status) std::memcpy(out_status + c.q0 + lo, stt + lo, hi - lo);
-            if (any) any_status.store(true);
-        });
-    };
-
-    // Software pipeline with three host threads: the feeder stages chunks in (its own worker pool) as soon as a slot is
-    // free; this thread waits for the search of chunk k (locate: for its number of hits), enqueues locate and the
-    // copies out; the drainer widens chunk k - 1 into the caller's arrays (its own pool).  Copy-in, kernels, copy-out
-    // and both host-side copies of different chunks overlap; with the middle and the drain stage on one thread the
-    // locate call took 1.6-1.8 x the PCIe time of its input, the thread being busy widening hits while a finished
-    // search waited for its locate launch.
-    std::mutex mu;
-    std::condition_variable cv;
-    size_t staged = 0, launched = 0, drained = 0;  // chunks staged in / with their copy-out enqueued / fully drained
-    bool abort = false;
-    std::exception_ptr worker_error;
+    p.wide_hits = wide_hits;
+    p.hit_bytes = wide_hits ? sizeof(gdx_hit_t) : sizeof(gdx_hit32_t);
+    p.hit_limit = chunk_hit_limit();
     // (a feeder that packs is the call's bound: it gets half as many workers again as the drainer -- 10 of a 16-CPU container's:
     // count 1.0 -> 2.1, wide locate 0.9 -> 1.8 G reads/s on one box; both pools at 10 or 14 were slower than both at 7.
     // GDX_HOST_IN_THREADS: experiments)
-    const unsigned in_threads = [&] {
+    p.in_threads = [&] {
         if (const char *e = getenv("GDX_HOST_IN_THREADS")) return static_cast<unsigned>(std::max(1, atoi(e)));
-        if (!host_pack || getenv("GDX_HOST_THREADS")) return host_threads();
+        if (!p.host_pack || getenv("GDX_HOST_THREADS")) return host_threads();
         const unsigned cpus = usable_cpus();
         return std::max(host_threads(), std::min(host_threads() * 3u / 2u, cpus > 4u ? cpus - 4u : 1u));
     }();
-    WorkerPool in_pool(in_threads);
-    auto fail_all = [&](std::exception_ptr e) {
-        std::lock_guard<std::mutex> g(mu);
-        if (!worker_error) worker_error = e;
-        abort = true;
-        cv.notify_all();
+    // (a chunk's limit counts the bytes that cross the link: four symbols per byte of a packed batch; the fused step is a dozen
+    // launches per chunk and takes up to four times the queries)
+    p.chunks = plan_host_chunks(call.qoff, call.nq, call.uniform_len, g_chunk_bytes.load() * ((call.packed || p.host_pack) ? 4 : 1),
+                                g_chunk_queries.load() * (p.stepped ? 4 : 1));
+    uint64_t max_bytes = 0;
+    for (const HostChunk &c : p.chunks) {
+        p.max_nq = std::max(p.max_nq, c.nq);
+        max_bytes = std::max(max_bytes, c.bytes);
+    }
+    // (packed: max_bytes counts symbols, four per byte, and a chunk starts up to seven symbols before its first query)
+    p.qbuf_cap = div_ceil((call.packed ? div_ceil(max_bytes + 8, 4) : max_bytes) + 1, 8) * 8 + 24;
+    if (p.stepped) p.n32_cap = p.max_nq + p.max_nq / 4 + 4096;
+    p.wl = make_wire_layout(p.max_nq, ix.num_texts());
+    return p;
+}
+
+// ---- a slot: the buffers of one chunk in flight ------------------------------------------------------------------------------
+// Buffer ids of the grow-only cache (slot * 16 + id).  The numbers are kept from when they were literals: calls of different
+// kinds on one thread then share the blocks they always shared (pinned 7 and 8 and device 5, 7, 8, 9 serve two paths each).
+enum PinnedId { kPinIn = 0, kPinQoff = 1, kPinA = 2, kPinB = 3, kPinStatus = 4, kPinTotal = 5, kPinHits = 6, kPinWire = 7, kPinExc = 8, kPinOff = 10 };
+enum DeviceId {
+    kDevQbuf = 0, kDevQoff = 1, kDevA = 2, kDevB = 3, kDevStatus = 4, kDevRec = 5, kDevOff = 6, kDevScan = 7, kDevHits = 8, kDevWs = 9,
+    kDevWireWs = 10, kDevCmp = 11, kDevOff32 = 12, kDevTotals = 13, kDevWire = 14, kDevExc = 15
+};
+
+struct Slot {
+    int dev = 0, s = 0;
+    // every path: the chunk's queries, pinned and on the device; narrow results a / b (counts, or interval borders), status bytes
+    uint8_t *h_in = nullptr, *d_qbuf = nullptr, *h_status = nullptr, *d_status = nullptr;
+    uint64_t *h_qoff = nullptr, *d_qoff = nullptr;
+    uint32_t *h_a = nullptr, *h_b = nullptr, *d_a = nullptr, *d_b = nullptr;
+    uint64_t *h_total = nullptr;          // [0..2] totals / the any-status flag, [4..5] the wire's meta
+    unsigned long long *d_tot = nullptr;  // flagged: the any-status flag; stepped: the step's totals
+    // the locate paths
+    uint4 *d_rec = nullptr;
+    void *d_scan = nullptr, *d_hits = nullptr, *h_hits = nullptr, *d_ws = nullptr;
+    uint64_t *d_off = nullptr, *h_off = nullptr;  // plain: the chunk's hit offsets (h_off[i] = hits of its queries before query i)
+    uint32_t *d_cmp = nullptr, *d_off32 = nullptr;  // stepped
+    // the wire: sections at HostPlan::wl's offsets on both sides; the exceptions {reads | counts | hits} (pinned: packed tight)
+    uint8_t *d_wire = nullptr, *h_wire = nullptr, *d_exc = nullptr, *h_exc = nullptr, *d_wws = nullptr;
+    uint64_t exc_hits_cap = 0;
+    uint64_t w_found = 0, w_exc = 0, w_exc_hits = 0;  // of the chunk in the slot: found reads, exceptions, their hits
+    bool w_status = false;                            // and: its status bytes crossed the link (one of them is set)
+
+    // INVARIANT: every call of these two runs on the calling thread of the pipeline (fill_slots, the middle stage).  The cache
+    // behind them is thread_local and grow-only; the feeder and the drainer live for one call, so a block they asked for would
+    // be allocated anew in every call and freed when the thread ends, under the copies still on their way.
+    template <class T>
+    T *pinned(PinnedId id, size_t count) const { return pinned_buf<T>(dev, s * 16 + id, count); }
+    template <class T>
+    T *device(DeviceId id, size_t count) const { return device_buf<T>(dev, s * 16 + id, count); }
+};
+
+// one call's state, shared by the stages
+struct HostRun {
+    const HostCall &call;
+    const HostPlan plan;
+    std::vector<HostChunk> chunks;  // the plan's, with the totals filled in as the call runs
+    const IndexView &view;
+    const uint8_t *io_to_dense;
+    const QueryOptions qo;
+    WorkerPool &pool;  // the drainer's workers
+    Streams st;
+    Slot slots[kSlots];
+    size_t scan_bytes = 0;  // kPlainLocate: of the offsets scan's workspace
+    gdx_hit_t *hits = nullptr;  // wide locate: the caller's (or grow_hits') array as it stands
+    uint64_t hits_capacity = 0;
+    std::atomic<bool> any_status{false};
+    uint64_t hit_base = 0;      // hits of the chunks drained so far
+    uint64_t mid_hit_base = 0;  // stepped: hits of the chunks whose copies out are enqueued
+    bool capacity_ok = true;    // wide locate: the caller's buffer holds everything so far
+    double t_out_sync = 0;      // (timing) the drainer's wait for the copies out
+
+    HostRun(const HostCall &c, HostPlan &&p, const FmIndex &ix, WorkerPool &drain_pool)
+        : call(c), plan(std::move(p)), chunks(plan.chunks), view(ix.view()), io_to_dense(ix.config().io_to_dense), qo(ix.query_options()),
+          pool(drain_pool), hits(c.hits), hits_capacity(c.hits_capacity)
+    {
+    }
+};
+
+// Which path needs which buffer.  Sizes: for the largest chunk; hits of the plain path and a chunk of the fused step with
+// more hits than n32_cap grow theirs in the middle stage.
+void fill_slots(HostRun &r, int dev)
+{
+    const HostPlan &p = r.plan;
+    const uint64_t max_nq = p.max_nq;
+    if (p.path == Path::kPlainLocate) r.scan_bytes = hit_offsets_rec_temp_bytes(max_nq);
+    const size_t tws = p.stepped ? scan_totals_workspace_bytes(max_nq) : 0;
+    for (int s = 0; s < kSlots; s++) {
+        Slot &sl = r.slots[s];
+        sl.dev = dev, sl.s = s;
+        // (all of these for every path, a / d_a of a locate call too: the cache holds the same blocks whichever call came first)
+        sl.h_in = sl.pinned<uint8_t>(kPinIn, p.qbuf_cap);
+        sl.h_qoff = sl.pinned<uint64_t>(kPinQoff, max_nq + 1);
+        sl.h_a = sl.pinned<uint32_t>(kPinA, max_nq);
+        sl.h_status = sl.pinned<uint8_t>(kPinStatus, max_nq);
+        sl.h_total = sl.pinned<uint64_t>(kPinTotal, p.path == Path::kPlainLocate ? 1 : 8);
+        sl.d_qbuf = sl.device<uint8_t>(kDevQbuf, p.qbuf_cap);
+        sl.d_qoff = sl.device<uint64_t>(kDevQoff, max_nq + 1);
+        sl.d_a = sl.device<uint32_t>(kDevA, max_nq);
+        sl.d_status = sl.device<uint8_t>(kDevStatus, max_nq);
+        switch (p.path) {
+        case Path::kIntervals:
+            sl.h_b = sl.pinned<uint32_t>(kPinB, max_nq);
+            sl.d_b = sl.device<uint32_t>(kDevB, max_nq);
+            [[fallthrough]];
+        case Path::kCounts:
+            sl.d_tot = sl.device<unsigned long long>(kDevTotals, 4);
+            break;
+        case Path::kPlainLocate:
+            sl.d_rec = sl.device<uint4>(kDevRec, max_nq);
+            sl.d_off = sl.device<uint64_t>(kDevOff, max_nq + 1);
+            sl.d_scan = sl.device<uint8_t>(kDevScan, r.scan_bytes ? r.scan_bytes : 1);
+            sl.h_off = sl.pinned<uint64_t>(kPinOff, max_nq + 1);
+            break;  // (d_hits, h_hits, d_ws: sized for the chunk's total in the middle stage)
+        case Path::kStepWire:
+            sl.d_wire = sl.device<uint8_t>(kDevWire, p.wl.bytes);
+            sl.h_wire = sl.pinned<uint8_t>(kPinWire, p.wl.bytes);
+            sl.exc_hits_cap = p.n32_cap;
+            sl.d_exc = sl.device<uint8_t>(kDevExc, p.wl.exc_hits + sl.exc_hits_cap * sizeof(gdx_hit32_t));
+            sl.d_wws = sl.device<uint8_t>(kDevWireWs, wire_pack_workspace_bytes(max_nq));
+            [[fallthrough]];  // (h_exc: sized for the chunk's exceptions in the middle stage)
+        case Path::kStepDma:
+            sl.d_rec = sl.device<uint4>(kDevRec, max_nq);
+            sl.d_cmp = sl.device<uint32_t>(kDevCmp, max_nq);
+            sl.d_off32 = sl.device<uint32_t>(kDevOff32, max_nq + 1);
+            sl.d_tot = sl.device<unsigned long long>(kDevTotals, 4);
+            sl.d_scan = sl.device<uint8_t>(kDevScan, tws ? tws : 1);
+            sl.d_hits = sl.device<uint8_t>(kDevHits, p.n32_cap * sizeof(gdx_hit32_t));
+            sl.d_ws = sl.device<uint8_t>(kDevWs, locate_workspace_bytes(p.n32_cap));
+            break;
+        }
+    }
+}
+
+// ---- the three-thread loop ---------------------------------------------------------------------------------------------------
+// Software pipeline with three host threads: the feeder stages chunks in (its own worker pool) as soon as a slot is free;
+// the calling thread waits for the search of chunk k (locate: for its number of hits), enqueues locate and the copies out;
+// the drainer widens chunk k - 1 into the caller's arrays (its own pool).  Copy-in, kernels, copy-out and both host-side
+// copies of different chunks overlap; with the middle and the drain stage on one thread the locate call took 1.6-1.8 x the
+// PCIe time of its input, the thread being busy widening hits while a finished search waited for its locate launch.
+// A stage that throws stops all three; the first exception is thrown again when both side threads are joined and the device
+// is idle.
+class ThreeStageRunner {
+public:
+    using Stage = std::function<void(size_t)>;
+    // out_sync: seconds of stage_out's work that were a wait for the copies out (the timing line names them)
+    void run(size_t n_chunks, int dev, const Stage &stage_in, const Stage &stage_mid, const Stage &stage_out, const double &out_sync)
+    {
+        Times t_in, t_mid, t_out;
+        std::thread feeder([&] { loop(n_chunks, dev, stage_in, staged_, [&](size_t k) { return k < drained_ + kSlots; }, t_in); });
+        std::thread drainer([&] { loop(n_chunks, dev, stage_out, drained_, [&](size_t k) { return launched_ > k; }, t_out); });
+        loop(n_chunks, -1, stage_mid, launched_, [&](size_t k) { return staged_ > k; }, t_mid);
+        feeder.join();
+        drainer.join();
+        if (host_timing())
+            fprintf(stderr, "gdx host pipeline: %zu chunks; feeder wait %.3f work %.3f; launcher wait %.3f work %.3f; drainer wait %.3f work %.3f (of it %.3f waiting for the copies out)\n",
+                    n_chunks, t_in.wait, t_in.work, t_mid.wait, t_mid.work, t_out.wait, t_out.work, out_sync);
+        if (error_) {
+            (void)hipDeviceSynchronize();
+            std::rethrow_exception(error_);
+        }
+    }
+
+private:
+    struct Times {
+        double wait = 0, work = 0;
     };
-    std::thread feeder([&] {
+    // chunk after chunk: wait until ready(k), run the stage, publish `done` = k + 1.  dev >= 0: a side thread, which makes the
+    // device current first
+    template <class Ready>
+    void loop(size_t n_chunks, int dev, const Stage &stage, size_t &done, Ready ready, Times &t)
+    {
+        const bool timing = host_timing();
         try {
-            GDX_HIP(hipSetDevice(dev));
+            if (dev >= 0) GDX_HIP(hipSetDevice(dev));
             for (size_t k = 0; k < n_chunks; k++) {
                 const double t0 = timing ? now_seconds() : 0.0;
                 {
-                    std::unique_lock<std::mutex> g(mu);
-                    cv.wait(g, [&] { return abort || k < drained + kSlots; });
-                    if (abort) return;
+                    std::unique_lock<std::mutex> g(mu_);
+                    cv_.wait(g, [&] { return abort_ || ready(k); });
+                    if (abort_) return;
                 }
                 const double t1 = timing ? now_seconds() : 0.0;
-                stage_in_with(k, in_pool);
+                stage(k);
                 if (timing) {
-                    t_in_wait += t1 - t0;
-                    t_in_work += now_seconds() - t1;
+                    t.wait += t1 - t0;
+                    t.work += now_seconds() - t1;
                 }
                 {
-                    std::lock_guard<std::mutex> g(mu);
-                    staged = k + 1;
+                    std::lock_guard<std::mutex> g(mu_);
+                    done = k + 1;
                 }
-                cv.notify_all();
+                cv_.notify_all();
             }
         } catch (...) {
-            fail_all(std::current_exception());
+            std::lock_guard<std::mutex> g(mu_);
+            if (!error_) error_ = std::current_exception();
+            abort_ = true;
+            cv_.notify_all();
         }
-    });
-    std::thread drainer([&] {
-        try {
-            GDX_HIP(hipSetDevice(dev));
-            for (size_t k = 0; k < n_chunks; k++) {
-                const double t0 = timing ? now_seconds() : 0.0;
-                {
-                    std::unique_lock<std::mutex> g(mu);
-                    cv.wait(g, [&] { return abort || launched > k; });
-                    if (abort) return;
-                }
-                const double t1 = timing ? now_seconds() : 0.0;
-                stage_out(k);
-                if (timing) {
-                    t_out_wait += t1 - t0;
-                    t_out_work += now_seconds() - t1;
-                }
-                {
-                    std::lock_guard<std::mutex> g(mu);
-                    drained = k + 1;
-                }
-                cv.notify_all();
+    }
+    std::mutex mu_;
+    std::condition_variable cv_;
+    size_t staged_ = 0, launched_ = 0, drained_ = 0;  // chunks staged in / with their copy-out enqueued / fully drained
+    bool abort_ = false;
+    std::exception_ptr error_;
+};
+
+// ---- stage in (feeder thread): user memory -> pinned staging -> device, the chunk's kernels enqueued -------------------------
+struct StagedChunk {
+    bool as_packed = false;    // the chunk is on the device as 2-bit codes (the caller's, or made by the feeder's workers)
+    uint64_t uniform_len = 0;  // != 0: every query of the chunk has this many symbols, and no offsets went over
+};
+
+// The shared front of every path: host pack, staging copy or pinned pass-through, zero padding, offsets rebase, H2D copies;
+// the compute stream then waits for them
+StagedChunk stage_queries(HostRun &r, size_t k, WorkerPool &pool)
+{
+    const HostPlan &p = r.plan;
+    const Slot &sl = r.slots[k % kSlots];
+    const HostChunk &c = r.chunks[k];
+    const uint8_t *qbuf = r.call.qbuf;
+    const uint64_t *qoff = r.call.qoff;
+    const uint64_t uniform_len = r.call.uniform_len;
+    const bool uniform = uniform_len != 0;
+    auto off_of = [&](uint64_t i) { return uniform ? i * uniform_len : qoff[i]; };
+    bool as_packed = r.call.packed, packed_here = false;  // packed_here: the chunk's codes were made by this thread's workers, in h_in
+    uint64_t chunk_uniform = uniform ? uniform_len : 0;
+    if (p.host_pack && c.bytes != 0) {
+        // the chunk's symbols are packed from ITS first symbol on (symbol j of the chunk in bits 2 (j & 3) of byte j >> 2)
+        const uint64_t first = off_of(c.q0), n_sym = off_of(c.q0 + c.nq) - first, nb = div_ceil(n_sym, 4);
+        std::atomic<bool> other{false};  // a symbol that is not one of the dense codes 1..4
+        std::atomic<bool> ragged{false};
+        const uint64_t len0 = uniform ? uniform_len : qoff[c.q0 + 1] - qoff[c.q0];
+        uint8_t *out = sl.h_in;
+        pool.run([&](unsigned w, unsigned nw) {
+            const uint64_t per = (nb / nw + 64) / 64 * 64;
+            const uint64_t lo = std::min(nb, per * w), hi = std::min(nb, lo + per);
+            pack_range(p.pack_plan, r.io_to_dense, qbuf + first, 0, n_sym, lo, hi, out,
+                       [&](uint64_t) { other.store(true, std::memory_order_relaxed); });
+            // reads of one length (a sequencer's) need no offsets at all: neither rebased, nor copied, nor read by the kernels
+            if (!uniform && len0 != 0) {
+                const uint64_t qper = div_ceil(c.nq, nw), q_lo = std::min(c.nq, qper * w), q_hi = std::min(c.nq, q_lo + qper);
+                bool same = true;
+                for (uint64_t i = q_lo; i < q_hi; i++) same &= qoff[c.q0 + i + 1] - qoff[c.q0 + i] == len0;
+                if (!same) ragged.store(true, std::memory_order_relaxed);
             }
-        } catch (...) {
-            fail_all(std::current_exception());
-        }
+        });
+        as_packed = packed_here = !other.load();
+        if (packed_here && !uniform && len0 != 0 && len0 < (1ull << 21) && !ragged.load()) chunk_uniform = len0;
+    }
+    // packed (by the caller): the chunk starts at the 16-bit unit that holds its first symbol, offsets are rebased to that unit
+    const uint64_t base = (as_packed && !packed_here) ? (off_of(c.q0) & ~7ull) : off_of(c.q0);
+    const uint64_t src_byte = as_packed ? base / 4 : base;
+    const uint64_t n_bytes = as_packed ? div_ceil(off_of(c.q0 + c.nq) - base, 4) : c.bytes;
+    if (!p.pinned_input && !packed_here)
+        pool.parallel_range(n_bytes, 64, [&](uint64_t lo, uint64_t hi) { stream_copy(sl.h_in + lo, qbuf + src_byte + lo, hi - lo); });
+    if (chunk_uniform == 0)
+        pool.parallel_range(c.nq + 1, 8, [&](uint64_t lo, uint64_t hi) {
+            for (uint64_t i = lo; i < hi; i++) sl.h_qoff[i] = qoff[c.q0 + i] - base;
+        });
+    const uint64_t padded = div_ceil(n_bytes + 2, 8) * 8;
+    if (p.pinned_input && !packed_here) {  // the caller's buffer is pinned: the device reads it as it is, no staging copy
+        if (n_bytes) GDX_HIP(hipMemcpyAsync(sl.d_qbuf, qbuf + src_byte, n_bytes, hipMemcpyHostToDevice, r.st.in));
+        GDX_HIP(hipMemsetAsync(sl.d_qbuf + n_bytes, 0, padded - n_bytes, r.st.in));  // windows may read past the last query
+    } else {
+        std::memset(sl.h_in + n_bytes, 0, padded - n_bytes);
+        GDX_HIP(hipMemcpyAsync(sl.d_qbuf, sl.h_in, padded, hipMemcpyHostToDevice, r.st.in));
+    }
+    if (chunk_uniform == 0) GDX_HIP(hipMemcpyAsync(sl.d_qoff, sl.h_qoff, (c.nq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, r.st.in));
+    GDX_HIP(hipEventRecord(r.st.ev_in[sl.s], r.st.in));
+    GDX_HIP(hipStreamWaitEvent(r.st.k, r.st.ev_in[sl.s], 0));
+    return StagedChunk{as_packed, chunk_uniform};
+}
+
+// the query side of the chunk's search
+SearchCall chunk_search_call(const Slot &sl, const HostChunk &c, const StagedChunk &sc)
+{
+    SearchCall call;
+    call.d_qbuf = sl.d_qbuf;
+    if (sc.uniform_len != 0) {  // (the chunk starts at its first symbol: it is a uniform batch of its own)
+        call.uniform_len = static_cast<uint32_t>(sc.uniform_len);
+    } else {
+        call.d_qbeg = sl.d_qoff;
+        call.d_qend = sl.d_qoff + 1;
+    }
+    call.nq = c.nq;
+    call.packed = sc.as_packed;
+    return call;
+}
+
+// kIntervals, kCounts: search, then *d_tot |= 1 when a status byte of the chunk is set
+void enqueue_flagged(HostRun &r, const Slot &sl, const HostChunk &c, SearchCall call)
+{
+    if (r.plan.path == Path::kIntervals) {
+        call.d_start = sl.d_a;
+        call.d_end = sl.d_b;
+        call.mode = 0;
+    } else {
+        call.d_count = sl.d_a;
+        call.mode = 1;
+    }
+    call.d_status = sl.d_status;
+    launch_search_call(r.view, call, r.st.k, r.qo);
+    GDX_HIP(hipGetLastError());
+    GDX_HIP(hipEventRecord(r.st.ev_k[sl.s], r.st.k));
+    GDX_HIP(hipMemsetAsync(sl.d_tot, 0, sizeof(unsigned long long), r.st.k));
+    hipLaunchKernelGGL(any_status_kernel, dim3(static_cast<unsigned>(std::min<uint64_t>(c.nq / 4096 + 1, 1024))), dim3(256), 0, r.st.k,
+                       sl.d_status, c.nq, sl.d_tot);
+    GDX_HIP(hipMemcpyAsync(sl.h_total, sl.d_tot, sizeof(uint64_t), hipMemcpyDeviceToHost, r.st.k));
+    GDX_HIP(hipEventRecord(r.st.ev_total[sl.s], r.st.k));
+}
+
+// kPlainLocate: search into records, status unpack, offsets scan; the chunk's total goes to the host
+void enqueue_plain_locate(HostRun &r, const Slot &sl, const HostChunk &c, SearchCall call)
+{
+    call.d_rec = sl.d_rec;
+    call.mode = 1;
+    launch_search_call(r.view, call, r.st.k, r.qo);
+    GDX_HIP(hipGetLastError());
+    const unsigned blocks = static_cast<unsigned>(std::min<uint64_t>((c.nq + 255) / 256, 4096));
+    hipLaunchKernelGGL(unpack_status_kernel, dim3(blocks), dim3(256), 0, r.st.k, sl.d_rec, c.nq, sl.d_status);
+    // (max_hits_per_query: a query gets slots for its first k rows only -- locate(q).take(k))
+    launch_hit_offsets_rec(sl.d_rec, c.nq, sl.d_off, sl.d_scan, r.scan_bytes, r.st.k, r.qo.max_hits_per_query, true);
+    GDX_HIP(hipMemcpyAsync(sl.h_total, sl.d_off + c.nq, sizeof(uint64_t), hipMemcpyDeviceToHost, r.st.k));
+    GDX_HIP(hipEventRecord(r.st.ev_total[sl.s], r.st.k));
+}
+
+// kStepWire: the slot's offsets and hits -> its wire and exceptions; the wire's meta goes to the host behind the totals
+void pack_wire(HostRun &r, const Slot &sl, uint64_t chunk_nq)
+{
+    const WireLayout &wl = r.plan.wl;
+    const uint64_t max_nq = r.plan.max_nq;
+    uint8_t *w = sl.d_wire, *e = sl.d_exc;
+    WireHostForm hf;
+    hf.d_exc_hits32 = reinterpret_cast<gdx_hit32_t *>(e + wl.exc_hits);
+    hf.d_tile_off = reinterpret_cast<uint32_t *>(w + wl.tile_off);
+    hf.d_found_ids = wl.ids ? w + wl.found_ids : nullptr;
+    hf.ix = &r.view;
+    hf.hits_stored = sl.exc_hits_cap;
+    launch_wire_pack(sl.d_cmp, sl.d_off32, true, static_cast<const gdx_hit32_t *>(sl.d_hits), chunk_nq, w + wl.bitmap,
+                     reinterpret_cast<uint32_t *>(w + wl.tile_found), reinterpret_cast<uint32_t *>(w + wl.found_pos), max_nq,
+                     reinterpret_cast<uint32_t *>(e + wl.exc_reads), reinterpret_cast<uint32_t *>(e + wl.exc_counts), max_nq, nullptr,
+                     nullptr, sl.exc_hits_cap, reinterpret_cast<uint32_t *>(w), sl.d_wws, r.st.k, &hf);
+    GDX_HIP(hipGetLastError());
+    GDX_HIP(hipMemcpyAsync(sl.h_total + 4, w, 16, hipMemcpyDeviceToHost, r.st.k));
+}
+
+// kStepDma, kStepWire: the fused step (search, totals, u32 offsets, 8-byte hits), status unpack, (wire pack)
+void enqueue_step(HostRun &r, const Slot &sl, const HostChunk &c, const SearchCall &call)
+{
+    LocateStep step;
+    step.call = call;
+    step.call.d_rec = sl.d_rec;
+    step.call.d_compact = sl.d_cmp;
+    step.max_hits = r.qo.max_hits_per_query;
+    step.take = true;  // locate(q).take(k)
+    step.d_scan_workspace = sl.d_scan;
+    step.d_totals = sl.d_tot;
+    step.d_hit_offsets = sl.d_off32;
+    step.narrow = true;
+    step.d_hits = sl.d_hits;  // (sized for n32_cap hit slots; a chunk with more takes the second half again, second_half_again)
+    step.hits_capacity = r.plan.n32_cap;
+    step.d_workspace = sl.d_ws;
+    GDX_HIP(hipMemsetAsync(sl.d_tot + 2, 0, sizeof(unsigned long long), r.st.k));
+    launch_locate_step(r.view, step, r.st.k, r.qo);
+    GDX_HIP(hipGetLastError());
+    launch_unpack_records(sl.d_rec, c.nq, nullptr, sl.d_status, r.st.k, sl.d_cmp, sl.d_tot + 2);
+    GDX_HIP(hipMemcpyAsync(sl.h_total, sl.d_tot, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, r.st.k));
+    if (r.plan.path == Path::kStepWire) pack_wire(r, sl, c.nq);
+    GDX_HIP(hipEventRecord(r.st.ev_total[sl.s], r.st.k));
+}
+
+void stage_in(HostRun &r, size_t k, WorkerPool &in_pool)
+{
+    const Slot &sl = r.slots[k % kSlots];
+    const HostChunk &c = r.chunks[k];
+    const SearchCall call = chunk_search_call(sl, c, stage_queries(r, k, in_pool));
+    switch (r.plan.path) {
+    case Path::kIntervals:
+    case Path::kCounts: enqueue_flagged(r, sl, c, call); break;
+    case Path::kPlainLocate: enqueue_plain_locate(r, sl, c, call); break;
+    case Path::kStepDma:
+    case Path::kStepWire: enqueue_step(r, sl, c, call); break;
+    }
+}
+
+// ---- stage mid (calling thread): the chunk's search is done (locate: its total is known) -> locate, then all D2H -------------
+void mid_flagged(HostRun &r, Slot &sl, const HostChunk &c)
+{
+    GDX_HIP(hipEventSynchronize(r.st.ev_total[sl.s]));
+    sl.w_status = sl.h_total[0] != 0;
+    GDX_HIP(hipStreamWaitEvent(r.st.out, r.st.ev_k[sl.s], 0));
+    GDX_HIP(hipMemcpyAsync(sl.h_a, sl.d_a, c.nq * sizeof(uint32_t), hipMemcpyDeviceToHost, r.st.out));
+    if (r.plan.path == Path::kIntervals) GDX_HIP(hipMemcpyAsync(sl.h_b, sl.d_b, c.nq * sizeof(uint32_t), hipMemcpyDeviceToHost, r.st.out));
+    if (sl.w_status) GDX_HIP(hipMemcpyAsync(sl.h_status, sl.d_status, c.nq, hipMemcpyDeviceToHost, r.st.out));
+    GDX_HIP(hipEventRecord(r.st.ev_out[sl.s], r.st.out));
+}
+
+void mid_plain_locate(HostRun &r, Slot &sl, HostChunk &c)
+{
+    const size_t hit_bytes = r.plan.hit_bytes;
+    GDX_HIP(hipEventSynchronize(r.st.ev_total[sl.s]));
+    c.total = *sl.h_total;
+    const bool locate = c.total && !r.plan.sizing_only;
+    if (locate) {
+        sl.d_hits = sl.device<uint8_t>(kDevHits, c.total * hit_bytes);
+        sl.h_hits = sl.pinned<uint8_t>(kPinHits, c.total * hit_bytes);
+        sl.d_ws = sl.device<uint8_t>(kDevWs, locate_workspace_bytes(c.total));
+        LocateCall loc;
+        loc.d_rec = sl.d_rec;
+        loc.m = c.nq;
+        loc.d_hit_offsets = sl.d_off;
+        loc.total_hits = c.total;
+        loc.d_hits = sl.d_hits;
+        loc.wide = r.plan.wide_hits;
+        loc.d_workspace = sl.d_ws;
+        launch_locate(r.view, loc, r.st.k, r.qo);
+        GDX_HIP(hipGetLastError());
+    }
+    GDX_HIP(hipEventRecord(r.st.ev_k[sl.s], r.st.k));
+    GDX_HIP(hipStreamWaitEvent(r.st.out, r.st.ev_k[sl.s], 0));
+    GDX_HIP(hipMemcpyAsync(sl.h_off, sl.d_off, (c.nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, r.st.out));
+    GDX_HIP(hipMemcpyAsync(sl.h_status, sl.d_status, c.nq, hipMemcpyDeviceToHost, r.st.out));
+    if (locate) GDX_HIP(hipMemcpyAsync(sl.h_hits, sl.d_hits, c.total * hit_bytes, hipMemcpyDeviceToHost, r.st.out));
+    GDX_HIP(hipEventRecord(r.st.ev_out[sl.s], r.st.out));
+}
+
+// rare: more hits than the chunk's buffers were sized for -- the second half of the step again, with room (and the wire again,
+// from the complete hits)
+void second_half_again(HostRun &r, Slot &sl, const HostChunk &c, uint64_t rest)
+{
+    sl.d_hits = sl.device<uint8_t>(kDevHits, c.total * sizeof(gdx_hit32_t));
+    sl.d_ws = sl.device<uint8_t>(kDevWs, locate_workspace_bytes(c.total));
+    launch_offsets_hits(r.view, sl.d_rec, sl.d_cmp, c.nq, r.qo.max_hits_per_query, true, sl.d_scan, sl.d_off32, true, c.total, rest,
+                        sl.d_hits, sl.d_ws, r.st.k, r.qo);
+    GDX_HIP(hipGetLastError());
+    if (r.plan.path == Path::kStepWire) {
+        sl.exc_hits_cap = c.total;
+        sl.d_exc = sl.device<uint8_t>(kDevExc, r.plan.wl.exc_hits + sl.exc_hits_cap * sizeof(gdx_hit32_t));
+        pack_wire(r, sl, c.nq);
+        GDX_HIP(hipStreamSynchronize(r.st.k));
+    }
+}
+
+// both stepped paths: the chunk's totals, the capacity / hit-limit checks, the second half again where it is needed
+void step_totals(HostRun &r, Slot &sl, HostChunk &c)
+{
+    GDX_HIP(hipEventSynchronize(r.st.ev_total[sl.s]));
+    c.total = sl.h_total[0];
+    const uint64_t rest = sl.h_total[1];
+    const Kind kind = r.call.kind;
+    if (kind == Kind::kLocate32 && r.mid_hit_base + c.total >= (1ull << 32))
+        fail(GDX_ERR_CAPACITY, "more than 2^32 - 1 hits: 32-bit hit offsets do not hold them (gdx_locate_many_alloc_layout does)");
+    if (c.total >= r.plan.hit_limit && kind == Kind::kLocate) throw RetryWithWideOffsets{};  // (the wide call has no such limit)
+    if (c.total >= 0xffffffffull)  // (the step counts a chunk's hit slots in 32 bits)
+        fail(GDX_ERR_CAPACITY, "%llu queries of the batch have %llu hits, more than a chunk's 32-bit offsets hold: cap them "
+             "(gdx_query_options_t.max_hits_per_query), or take the device-written results (environment GDX_HOST_RESULTS=dma)",
+             static_cast<unsigned long long>(c.nq), static_cast<unsigned long long>(c.total));
+    if (c.total > r.plan.n32_cap) second_half_again(r, sl, c, rest);
+}
+
+// kStepDma: u32 offsets (shifted by the hits before the chunk) and hits straight into the sink's pinned arrays
+void mid_step_dma(HostRun &r, Slot &sl, HostChunk &c)
+{
+    Narrow32Sink *narrow = r.call.narrow;
+    step_totals(r, sl, c);
+    if (r.mid_hit_base + c.total > narrow->cap) {  // the pinned hit array moves: nothing may be on its way into the old one
+        GDX_HIP(hipStreamSynchronize(r.st.out));
+        narrow->hits = narrow->grow(r.mid_hit_base + c.total, r.mid_hit_base, &narrow->cap);
+    }
+    if (r.mid_hit_base != 0)
+        hipLaunchKernelGGL(add_hit_base_kernel, dim3(static_cast<unsigned>(std::min<uint64_t>((c.nq + 255) / 256, 2048))), dim3(256),
+                           0, r.st.k, sl.d_off32 + 1, c.nq, static_cast<uint32_t>(r.mid_hit_base));
+    GDX_HIP(hipEventRecord(r.st.ev_k[sl.s], r.st.k));
+    GDX_HIP(hipStreamWaitEvent(r.st.out, r.st.ev_k[sl.s], 0));
+    GDX_HIP(hipMemcpyAsync(narrow->offsets + c.q0 + 1, sl.d_off32 + 1, c.nq * sizeof(uint32_t), hipMemcpyDeviceToHost, r.st.out));
+    GDX_HIP(hipMemcpyAsync(sl.h_status, sl.d_status, c.nq, hipMemcpyDeviceToHost, r.st.out));
+    if (c.total)
+        GDX_HIP(hipMemcpyAsync(narrow->hits + r.mid_hit_base, sl.d_hits, c.total * sizeof(gdx_hit32_t), hipMemcpyDeviceToHost, r.st.out));
+    GDX_HIP(hipEventRecord(r.st.ev_out[sl.s], r.st.out));
+    c.hit_base = r.mid_hit_base;
+    r.mid_hit_base += c.total;
+}
+
+// kStepWire: the wire up to the last found read's position, the ids, the exceptions packed tight, the status bytes if one is set
+void mid_step_wire(HostRun &r, Slot &sl, HostChunk &c)
+{
+    const WireLayout &wl = r.plan.wl;
+    step_totals(r, sl, c);
+    const uint32_t *meta = reinterpret_cast<const uint32_t *>(sl.h_total + 4);
+    sl.w_exc = meta[0], sl.w_exc_hits = meta[1], sl.w_found = meta[2];
+    sl.w_status = sl.h_total[2] != 0;
+    if (sl.w_exc > r.plan.max_nq || sl.w_exc_hits > sl.exc_hits_cap || sl.w_found + sl.w_exc_hits != c.total)
+        fail(GDX_ERR_DEVICE, "internal: the wire of a chunk does not add up (%llu found + %llu exception hits, %llu hits)",
+             static_cast<unsigned long long>(sl.w_found), static_cast<unsigned long long>(sl.w_exc_hits),
+             static_cast<unsigned long long>(c.total));
+    GDX_HIP(hipEventRecord(r.st.ev_k[sl.s], r.st.k));
+    GDX_HIP(hipStreamWaitEvent(r.st.out, r.st.ev_k[sl.s], 0));
+    GDX_HIP(hipMemcpyAsync(sl.h_wire, sl.d_wire, wl.found_pos + sl.w_found * 4, hipMemcpyDeviceToHost, r.st.out));
+    if (wl.ids && sl.w_found != 0)
+        GDX_HIP(hipMemcpyAsync(sl.h_wire + wl.found_ids, sl.d_wire + wl.found_ids, sl.w_found, hipMemcpyDeviceToHost, r.st.out));
+    if (sl.w_exc != 0) {
+        const uint64_t n = sl.w_exc;
+        sl.h_exc = sl.pinned<uint8_t>(kPinExc, n * 8 + sl.w_exc_hits * sizeof(gdx_hit32_t));
+        GDX_HIP(hipMemcpyAsync(sl.h_exc, sl.d_exc + wl.exc_reads, n * 4, hipMemcpyDeviceToHost, r.st.out));
+        GDX_HIP(hipMemcpyAsync(sl.h_exc + n * 4, sl.d_exc + wl.exc_counts, n * 4, hipMemcpyDeviceToHost, r.st.out));
+        if (sl.w_exc_hits != 0)
+            GDX_HIP(hipMemcpyAsync(sl.h_exc + n * 8, sl.d_exc + wl.exc_hits, sl.w_exc_hits * sizeof(gdx_hit32_t), hipMemcpyDeviceToHost,
+                                   r.st.out));
+    }
+    if (sl.w_status) GDX_HIP(hipMemcpyAsync(sl.h_status, sl.d_status, c.nq, hipMemcpyDeviceToHost, r.st.out));
+    GDX_HIP(hipEventRecord(r.st.ev_out[sl.s], r.st.out));
+    c.hit_base = r.mid_hit_base;
+    r.mid_hit_base += c.total;
+}
+
+void stage_mid(HostRun &r, size_t k)
+{
+    Slot &sl = r.slots[k % kSlots];
+    HostChunk &c = r.chunks[k];
+    switch (r.plan.path) {
+    case Path::kIntervals:
+    case Path::kCounts: mid_flagged(r, sl, c); break;
+    case Path::kPlainLocate: mid_plain_locate(r, sl, c); break;
+    case Path::kStepDma: mid_step_dma(r, sl, c); break;
+    case Path::kStepWire: mid_step_wire(r, sl, c); break;
+    }
+}
+
+// ---- stage out (drainer thread): pinned staging -> the caller's arrays, widened -----------------------------------------------
+void out_flagged(HostRun &r, const Slot &sl, const HostChunk &c)
+{
+    const bool intervals = r.plan.path == Path::kIntervals;
+    uint64_t *out_a = intervals ? r.call.out_start : r.call.out_count, *out_b = intervals ? r.call.out_end : nullptr;
+    r.pool.parallel_range(c.nq, 8, [&](uint64_t lo, uint64_t hi) {
+        if (out_a) widen_u32(sl.h_a + lo, hi - lo, out_a + c.q0 + lo);
+        if (out_b) widen_u32(sl.h_b + lo, hi - lo, out_b + c.q0 + lo);
     });
+}
+
+// wide locate: room for `need` hits in the caller's array (grown where the library manages it); false from the first chunk on
+// that does not fit (gdx_locate_many then reports the size it takes)
+bool room_for_hits(HostRun &r, uint64_t need)
+{
+    if (r.call.grow_hits && need > r.hits_capacity) r.hits = (*r.call.grow_hits)(need, &r.hits_capacity);  // at least `need`
+    if (!(r.hits && need <= r.hits_capacity && r.capacity_ok)) r.capacity_ok = false;
+    return r.capacity_ok;
+}
+
+void out_plain_locate(HostRun &r, const Slot &sl, HostChunk &c)
+{
+    uint64_t *out_off = r.call.out_hit_offsets;
+    c.hit_base = r.hit_base;
+    if (out_off) {  // the chunk's offsets (scanned on the device) shifted by the hits of the chunks before it
+        const uint64_t *off = sl.h_off;
+        const uint64_t shift_by = r.hit_base;
+        r.pool.parallel_range(c.nq, 8, [&](uint64_t lo, uint64_t hi) {
+            for (uint64_t i = lo; i < hi; i++) out_off[c.q0 + i + 1] = off[i + 1] + shift_by;
+        });
+    }
+    const uint64_t need = r.hit_base + c.total;
+    if (room_for_hits(r, need) && !r.plan.sizing_only) {
+        gdx_hit_t *dst = r.hits + r.hit_base;
+        if (r.plan.wide_hits) {
+            const gdx_hit_t *src = static_cast<const gdx_hit_t *>(sl.h_hits);
+            r.pool.parallel_range(c.total, 8, [&](uint64_t lo, uint64_t hi) { std::memcpy(dst + lo, src + lo, (hi - lo) * sizeof(gdx_hit_t)); });
+        } else {
+            const gdx_hit32_t *src = static_cast<const gdx_hit32_t *>(sl.h_hits);
+            r.pool.parallel_range(c.total, 8, [&](uint64_t lo, uint64_t hi) {
+                for (uint64_t i = lo; i < hi; i++) {
+                    dst[i].text_id = src[i].text_id;
+                    dst[i].position = src[i].position;
+                }
+            });
+        }
+    } else {
+        r.capacity_ok = false;
+    }
+    r.hit_base = need;
+}
+
+// kStepWire: the chunk's wire -> offsets and hits in the caller's arrays, tiles shared out among the workers
+void out_wire(HostRun &r, const Slot &sl, const HostChunk &c)
+{
+    const WireLayout &wl = r.plan.wl;
+    const uint64_t need = c.hit_base + c.total;
+    const HostWire w{sl.h_wire + wl.bitmap,
+                     reinterpret_cast<const uint32_t *>(sl.h_wire + wl.tile_found),
+                     reinterpret_cast<const uint32_t *>(sl.h_wire + wl.tile_off),
+                     reinterpret_cast<const uint32_t *>(sl.h_wire + wl.found_pos),
+                     wl.ids ? sl.h_wire + wl.found_ids : nullptr,
+                     reinterpret_cast<const uint32_t *>(sl.h_exc),
+                     reinterpret_cast<const uint32_t *>(sl.h_exc + sl.w_exc * 4),
+                     reinterpret_cast<const gdx_hit32_t *>(sl.h_exc + sl.w_exc * 8),
+                     sl.w_exc};
+    const uint64_t tiles = div_ceil(c.nq, kHostWireTile);
+    auto share = [&](unsigned wk, unsigned nw, uint64_t &lo, uint64_t &hi) {
+        const uint64_t per = div_ceil(tiles, nw);
+        lo = std::min<uint64_t>(tiles, per * wk), hi = std::min<uint64_t>(tiles, lo + per);
+    };
+    if (r.call.kind == Kind::kLocate32) {  // narrow: u32 offsets and 8-byte hits in the sink's arrays
+        Narrow32Sink *narrow = r.call.narrow;
+        if (need > narrow->cap) narrow->hits = narrow->grow(need, c.hit_base, &narrow->cap);  // (only this thread's workers write there)
+        uint32_t *offs = narrow->offsets + c.q0;
+        gdx_hit32_t *hh = narrow->hits;
+        const uint32_t hb = static_cast<uint32_t>(c.hit_base);
+        r.pool.run([&](unsigned wk, unsigned nw) {
+            uint64_t lo, hi;
+            share(wk, nw, lo, hi);
+            wire_expand_tiles<uint32_t, gdx_hit32_t>(w, c.nq, lo, hi, hb, offs, hh);
+        });
+        return;
+    }
+    // wide: u64 offsets and 16-byte hits; the hits only while the caller's buffer holds them
+    uint64_t *offs = r.call.out_hit_offsets ? r.call.out_hit_offsets + c.q0 : nullptr;
+    gdx_hit_t *hh = room_for_hits(r, need) ? r.hits : nullptr;
+    if (offs != nullptr || hh != nullptr)
+        r.pool.run([&](unsigned wk, unsigned nw) {
+            uint64_t lo, hi;
+            share(wk, nw, lo, hi);
+            wire_expand_tiles<uint64_t, gdx_hit_t>(w, c.nq, lo, hi, c.hit_base, offs, hh);
+        });
+    r.hit_base = need;
+}
+
+// the status tail of every path.  bytes_came == false: no read of the chunk has a status, the bytes stayed on the device
+void out_status(HostRun &r, const Slot &sl, const HostChunk &c, bool bytes_came)
+{
+    uint8_t *out_status = r.call.out_status;
+    if (!bytes_came) {
+        if (out_status) r.pool.parallel_range(c.nq, 64, [&](uint64_t lo, uint64_t hi) { std::memset(out_status + c.q0 + lo, 0, hi - lo); });
+        return;
+    }
+    const uint8_t *stt = sl.h_status;
+    r.pool.parallel_range(c.nq, 64, [&](uint64_t lo, uint64_t hi) {
+        bool any = false;
+        for (uint64_t i = lo; i < hi; i++) any |= stt[i] != 0;
+        if (out_status) std::memcpy(out_status + c.q0 + lo, stt + lo, hi - lo);
+        if (any) r.any_status.store(true);
+    });
+}
+
+void stage_out(HostRun &r, size_t k)
+{
+    const Slot &sl = r.slots[k % kSlots];
+    HostChunk &c = r.chunks[k];
+    const double t_sync0 = host_timing() ? now_seconds() : 0.0;
+    GDX_HIP(hipEventSynchronize(r.st.ev_out[sl.s]));
+    if (host_timing()) r.t_out_sync += now_seconds() - t_sync0;
+    switch (r.plan.path) {
+    case Path::kIntervals:
+    case Path::kCounts: out_flagged(r, sl, c); break;
+    case Path::kPlainLocate: out_plain_locate(r, sl, c); break;
+    case Path::kStepDma: break;  // (offsets and hits are where they belong already)
+    case Path::kStepWire: out_wire(r, sl, c); break;
+    }
+    const bool conditional = r.plan.flagged || r.plan.path == Path::kStepWire;  // (the status bytes cross only if one is set)
+    out_status(r, sl, c, !conditional || sl.w_status);
+}
+
+}  // namespace
+
+// The pipeline behind every host-pointer call: plan, slots, then the three stages over the chunks
+int FmIndex::host_pipeline(const HostCall &call) const
+{
+    // (more than host_threads() workers did not shorten the expansion -- 13 ms of a 100 M-read call with 7 workers, 11 with 13 --
+    // and starved the runtime's own threads on a 16-CPU container)
+    WorkerPool pool(host_threads());
+    HostPlan plan = make_host_plan(call, *this, pool);
+    if (call.out_total) *call.out_total = 0;
+    if (call.kind == Kind::kLocate && call.out_hit_offsets) call.out_hit_offsets[0] = 0;
+    if (call.kind == Kind::kLocate32 && call.narrow != nullptr && call.narrow->offsets != nullptr) call.narrow->offsets[0] = 0;
+    if (call.nq == 0) return GDX_OK;
+    make_current();
+    HostRun r(call, std::move(plan), *this, pool);
+    fill_slots(r, cfg_.device_id);
+    WorkerPool in_pool(r.plan.in_threads);
+    ThreeStageRunner runner;
+    runner.run(r.chunks.size(), cfg_.device_id, [&](size_t k) { stage_in(r, k, in_pool); }, [&](size_t k) { stage_mid(r, k); },
+               [&](size_t k) { stage_out(r, k); }, r.t_out_sync);
+    GDX_HIP(hipStreamSynchronize(r.st.out));
+    if (call.kind == Kind::kLocate32) {
+        call.narrow->offsets[0] = 0;
+        if (call.out_total) *call.out_total = r.mid_hit_base;
+        return r.any_status.load() ? GDX_ERR_QUERY_STATUS : GDX_OK;
+    }
+    if (call.out_total) *call.out_total = r.hit_base;
+    if (call.kind == Kind::kLocate && r.hit_base > 0 && !r.capacity_ok) return GDX_ERR_CAPACITY;
+    return r.any_status.load() ? GDX_ERR_QUERY_STATUS : GDX_OK;
+}
+
+// A wide locate, and once more on the plain path when a chunk's hits did not fit the fused step's 32-bit offsets.
+// refresh (optional): brings the call's hit array up to date before the second run (the first may have grown it)
+int FmIndex::locate_wide(HostCall call, const std::function<void(HostCall &)> &refresh) const
+{
     try {
-        for (size_t k = 0; k < n_chunks; k++) {
-            const double t0 = timing ? now_seconds() : 0.0;
-            {
-                std::unique_lock<std::mutex> g(mu);
-                cv.wait(g, [&] { return abort || staged > k; });
-                if (abort) break;
-            }
-            const double t1 = timing ? now_seconds() : 0.0;
-            stage_mid(k);
-            if (timing) {
-                t_mid_wait += t1 - t0;
-                t_mid_work += now_seconds() - t1;
-            }
-            {
-                std::lock_guard<std::mutex> g(mu);
-                launched = k + 1;
-            }
-            cv.notify_all();
-        }
-    } catch (...) {
-        fail_all(std::current_exception());
-    }
-    feeder.join();
-    drainer.join();
-    if (timing)
-        fprintf(stderr, "gdx host pipeline: %zu chunks; feeder wait %.3f work %.3f; launcher wait %.3f work %.3f; drainer wait %.3f work %.3f (of it %.3f waiting for the copies out)\n",
-                n_chunks, t_in_wait, t_in_work, t_mid_wait, t_mid_work, t_out_wait, t_out_work, t_out_sync);
-    if (worker_error) {
+        return host_pipeline(call);
+    } catch (const RetryWithWideOffsets &) {
         (void)hipDeviceSynchronize();
-        std::rethrow_exception(worker_error);
+        if (refresh) refresh(call);
+        call.plain_locate_only = true;
+        return host_pipeline(call);
     }
-    GDX_HIP(hipStreamSynchronize(st.out));
-    if (kind == Kind::kLocate32) {
-        narrow->offsets[0] = 0;
-        if (out_total) *out_total = mid_hit_base;
-        return any_status.load() ? GDX_ERR_QUERY_STATUS : GDX_OK;
-    }
-    if (out_total) *out_total = hit_base;
-    if (kind == Kind::kLocate && hit_base > 0 && !capacity_ok) return GDX_ERR_CAPACITY;
-    return any_status.load() ? GDX_ERR_QUERY_STATUS : GDX_OK;
 }
 
 // ASCII -> 2-bit on the host, by all pool threads; exceptions = the queries that hold a symbol which is not one of
@@ -1007,34 +1168,36 @@ int FmIndex::cursors_for_many_queries(const uint8_t *qbuf, const uint64_t *qoff,
                                       uint64_t *out_end, uint64_t *out_count, uint8_t *out_status, bool packed,
                                       uint64_t uniform_len) const
 {
-    if (packed && (view_.layout != 0 || view_.n_searchable < 4))
-        fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
+    if (packed) check_packed_supported();
+    HostCall call;
+    call.qbuf = qbuf, call.qoff = qoff, call.nq = nq, call.packed = packed, call.uniform_len = uniform_len;
+    call.out_status = out_status;
     if (out_start || out_end) {
-        const int rc = host_pipeline(static_cast<int>(Kind::kIntervals), qbuf, qoff, nq, out_start, out_end, out_status,
-                                     nullptr, 0, nullptr, nullptr, packed, uniform_len);
+        call.kind = HostCall::Kind::kIntervals;
+        call.out_start = out_start;
+        call.out_end = out_end;
+        const int rc = host_pipeline(call);
         if (out_count && out_start && out_end)
             for (uint64_t i = 0; i < nq; i++) out_count[i] = out_end[i] - out_start[i];
         return rc;
     }
-    return host_pipeline(static_cast<int>(Kind::kCounts), qbuf, qoff, nq, out_count, nullptr, out_status, nullptr, 0,
-                         nullptr, nullptr, packed, uniform_len);
+    call.kind = HostCall::Kind::kCounts;
+    call.out_count = out_count;
+    return host_pipeline(call);
 }
 
 int FmIndex::locate_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint64_t *out_hit_offsets,
                          gdx_hit_t *hits, uint64_t hits_capacity, uint64_t *out_total, uint8_t *out_status) const
 {
-    try {
-        return host_pipeline(static_cast<int>(Kind::kLocate), qbuf, qoff, nq, out_hit_offsets, nullptr, out_status, hits,
-                             hits ? hits_capacity : 0, out_total, nullptr);
-    } catch (const RetryWithWideOffsets &) {  // a chunk with more hits than the fused step's 32-bit offsets hold
-        (void)hipDeviceSynchronize();
-        struct Restore {
-            ~Restore() { t_force_plain_locate = false; }
-        } restore;
-        t_force_plain_locate = true;
-        return host_pipeline(static_cast<int>(Kind::kLocate), qbuf, qoff, nq, out_hit_offsets, nullptr, out_status, hits,
-                             hits ? hits_capacity : 0, out_total, nullptr);
-    }
+    HostCall call;
+    call.kind = HostCall::Kind::kLocate;
+    call.qbuf = qbuf, call.qoff = qoff, call.nq = nq;
+    call.out_hit_offsets = out_hit_offsets;
+    call.out_status = out_status;
+    call.hits = hits;
+    call.hits_capacity = hits ? hits_capacity : 0;
+    call.out_total = out_total;
+    return locate_wide(call);
 }
 
 // One hit array released with gdx_free_hits is kept for the next gdx_locate_many_alloc: a caller that locates batch
@@ -1080,8 +1243,7 @@ int FmIndex::locate_many_alloc(const uint8_t *qbuf, const uint64_t *qoff, uint64
                                gdx_hit_t **out_hits, uint64_t *out_total, uint8_t *out_status, bool packed,
                                uint64_t uniform_len) const
 {
-    if (packed && (view_.layout != 0 || view_.n_searchable < 4))
-        fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
+    if (packed) check_packed_supported();
     if (!out_hits) fail(GDX_ERR_INVALID_ARGUMENT, "out_hits is null");
     *out_hits = nullptr;
     gdx_hit_t *buf = nullptr;
@@ -1113,18 +1275,16 @@ int FmIndex::locate_many_alloc(const uint8_t *qbuf, const uint64_t *qoff, uint64
     try {
         // a first guess from the batch size spares most reallocations (one hit per query is the common shape)
         grow(nq + nq / 8, nullptr);
-        try {
-            rc = host_pipeline(static_cast<int>(Kind::kLocate), qbuf, qoff, nq, out_hit_offsets, nullptr, out_status, buf, cap,
-                               out_total, &grow, packed, uniform_len);
-        } catch (const RetryWithWideOffsets &) {  // (as in locate_many)
-            (void)hipDeviceSynchronize();
-            struct Restore {
-                ~Restore() { t_force_plain_locate = false; }
-            } restore;
-            t_force_plain_locate = true;
-            rc = host_pipeline(static_cast<int>(Kind::kLocate), qbuf, qoff, nq, out_hit_offsets, nullptr, out_status, buf, cap,
-                               out_total, &grow, packed, uniform_len);
-        }
+        HostCall call;
+        call.kind = HostCall::Kind::kLocate;
+        call.qbuf = qbuf, call.qoff = qoff, call.nq = nq, call.packed = packed, call.uniform_len = uniform_len;
+        call.out_hit_offsets = out_hit_offsets;
+        call.out_status = out_status;
+        call.out_total = out_total;
+        call.grow_hits = &grow;
+        auto current_array = [&](HostCall &c) { c.hits = buf, c.hits_capacity = cap; };
+        current_array(call);
+        rc = locate_wide(call, current_array);
     } catch (...) {
         std::free(buf);
         throw;
@@ -1183,8 +1343,7 @@ void pinned_give(int which, void *ptr, size_t bytes)
 int FmIndex::locate_many_alloc32(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, gdx_hits32_t *out, uint8_t *out_status,
                                  bool packed, uint64_t uniform_len) const
 {
-    if (packed && (view_.layout != 0 || view_.n_searchable < 4))
-        fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
+    if (packed) check_packed_supported();
     if (!out) fail(GDX_ERR_INVALID_ARGUMENT, "out is null");
     std::memset(out, 0, sizeof(*out));
     make_current();
@@ -1211,8 +1370,13 @@ int FmIndex::locate_many_alloc32(const uint8_t *qbuf, const uint64_t *qoff, uint
     uint64_t total = 0;
     int rc;
     try {
-        rc = host_pipeline(static_cast<int>(Kind::kLocate32), qbuf, qoff, nq, nullptr, nullptr, out_status, nullptr, 0, &total, nullptr,
-                           packed, uniform_len, &sink);
+        HostCall call;
+        call.kind = HostCall::Kind::kLocate32;
+        call.qbuf = qbuf, call.qoff = qoff, call.nq = nq, call.packed = packed, call.uniform_len = uniform_len;
+        call.out_status = out_status;
+        call.out_total = &total;
+        call.narrow = &sink;
+        rc = host_pipeline(call);
     } catch (...) {
         (void)hipDeviceSynchronize();
         pinned_give(0, sink.offsets, off_bytes);

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/gdx.h"
+#include "errors.hpp"
 #include "layout.hpp"
 
 namespace gdx {
@@ -83,6 +84,13 @@ struct ZeroSet {
     void add(void *ptr, size_t bytes);
     void flush(hipStream_t stream);  // zeroes what was added (one kernel; nothing added: nothing launched) and empties the set
 };
+
+// what every call with packed queries (2-bit codes) refuses first: an index whose kernels cannot read them
+inline void check_packed_supported(const IndexView &ix)
+{
+    if (ix.layout != 0 || ix.n_searchable < 4)
+        fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
+}
 
 struct SearchCall {
     const uint8_t *d_qbuf = nullptr;

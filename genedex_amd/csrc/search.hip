@@ -4708,8 +4708,7 @@ void launch_search_call(const IndexView &ix, const SearchCall &call, hipStream_t
     SearchLauncher l{ix, call, stream, knobs, SearchSettings(ix, qo, knobs, call), call.nq,
                      !(env_pairs != nullptr && atoi(env_pairs) == 0), env_lane_blocks != nullptr ? atol(env_lane_blocks) : 0L};
     SearchCall &c = l.c;
-    if (c.packed && (ix.layout != 0 || ix.n_searchable < 4))
-        fail(GDX_ERR_UNSUPPORTED, "packed queries need the rank-line layout (sigma <= 8) with dense symbols 1..4 searchable");
+    if (c.packed) check_packed_supported(ix);
     if (c.packed && (c.mode == 2 || c.d_step_stats != nullptr)) fail(GDX_ERR_UNSUPPORTED, "packed queries: search and count / locate only");
     const bool pair_lines = ix.layout == 0 && l.s.variant == 2 && ix.pair_lines != nullptr;
     // (b, early) a uniform batch in front of the pair-line kernels, which read offsets; a count / locate call may leave all but

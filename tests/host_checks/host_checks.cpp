@@ -6,6 +6,8 @@
 //                                                            byte loop) in exactly sized buffers; prints "ok <cases> <exceptions>"
 //   host_checks wire <seed> <reads> <texts> [<found of ten> <exceptions: one in>]  expands a random chunk's "found bitmap" wire (wire_host.hpp) in pieces,
 //                                                            exactly sized buffers; prints "ok <hits> <exceptions>"
+//   host_checks chunks <seed>                              the chunk planner and the wire layout of the host-pointer pipeline (host_plan.hpp);
+//                                                            prints "ok <cases> <chunks>"
 // A malformed input must end in "error: <message>" (exit code 3), never in a sanitizer report.
 #include <cinttypes>
 #include <cstdio>
@@ -16,6 +18,7 @@
 #include <vector>
 
 #include "../../genedex_amd/csrc/fastx.hpp"
+#include "../../genedex_amd/csrc/host_plan.hpp"
 #include "../../genedex_amd/csrc/index_file.hpp"
 #include "../../genedex_amd/csrc/pack_host.hpp"
 #include "../../genedex_amd/csrc/wire_host.hpp"
@@ -251,6 +254,101 @@ int main(int argc, char **argv)
                         if (wide[i] != narrow[i]) return 13;
                 }
             std::printf("ok %zu %zu\n", want_hits.size(), exc_q.size());
+        } else if (mode == "chunks") {
+            // host_plan.hpp: the chunk planner of the host-pointer pipeline on random and hand-made offset arrays, in heap blocks
+            // of exactly nq + 1 entries, and the wire layout.  `expected` is the loop as it stood inside the pipeline before it
+            // became a function: boundaries must match list for list.
+            uint64_t x = std::strtoull(argv[2], nullptr, 10) * 2654435761ull + 88172645463325252ull;
+            auto rnd = [&]() {
+                x ^= x << 13, x ^= x >> 7, x ^= x << 17;
+                return x;
+            };
+            auto expected = [](const uint64_t *qoff, uint64_t nq, uint64_t uniform_len, uint64_t kChunkBytes, uint64_t kChunkQueries) {
+                const bool uniform = uniform_len != 0;
+                auto off_of = [&](uint64_t i) { return uniform ? i * uniform_len : qoff[i]; };
+                std::vector<gdx::HostChunk> chunks;
+                const uint64_t uniform_chunk = uniform ? std::max<uint64_t>(8, std::min(kChunkQueries, kChunkBytes / uniform_len) / 8 * 8) : 0;
+                for (uint64_t q0 = 0; q0 < nq;) {
+                    uint64_t hi = std::min(nq, q0 + (uniform ? uniform_chunk : kChunkQueries));
+                    if (!uniform && qoff[hi] - qoff[q0] > kChunkBytes) {
+                        const uint64_t *p = std::upper_bound(qoff + q0 + 1, qoff + hi + 1, qoff[q0] + kChunkBytes);
+                        hi = static_cast<uint64_t>(p - qoff) - 1;
+                        if (hi <= q0) hi = q0 + 1;  // a single query longer than a chunk
+                    }
+                    gdx::HostChunk c;
+                    c.q0 = q0;
+                    c.nq = hi - q0;
+                    c.bytes = off_of(hi) - off_of(q0);
+                    chunks.push_back(c);
+                    q0 = hi;
+                }
+                return chunks;
+            };
+            uint64_t cases = 0, n_chunks = 0;
+            // lens == null: a uniform batch (no offsets at all, as the calls allow)
+            auto check = [&](const std::vector<uint64_t> *lens, uint64_t nq, uint64_t uniform_len, uint64_t first, uint64_t bytes, uint64_t queries) {
+                std::unique_ptr<uint64_t[]> qoff;
+                if (lens) {
+                    qoff.reset(new uint64_t[nq + 1]);
+                    qoff[0] = first;
+                    for (uint64_t i = 0; i < nq; i++) qoff[i + 1] = qoff[i] + (*lens)[i];
+                }
+                auto off_of = [&](uint64_t i) { return lens ? qoff[i] : i * uniform_len; };
+                const std::vector<gdx::HostChunk> got = gdx::plan_host_chunks(qoff.get(), nq, uniform_len, bytes, queries);
+                const std::vector<gdx::HostChunk> want = expected(qoff.get(), nq, uniform_len, bytes, queries);
+                if (got.size() != want.size()) return 20;
+                uint64_t next = 0;
+                for (size_t k = 0; k < got.size(); k++) {
+                    const gdx::HostChunk &c = got[k];
+                    if (c.q0 != want[k].q0 || c.nq != want[k].nq || c.bytes != want[k].bytes) return 21;
+                    if (c.q0 != next || c.nq == 0) return 22;  // in order, without gaps
+                    if (c.bytes != off_of(c.q0 + c.nq) - off_of(c.q0)) return 23;
+                    // both limits, except for one over-long query -- and a uniform chunk, which never holds fewer than 8 queries
+                    if (c.nq > queries && !(uniform_len != 0 && c.nq <= 8)) return 24;
+                    if (c.bytes > bytes && !(c.nq == 1 || (uniform_len != 0 && c.nq <= 8))) return 25;
+                    if (uniform_len != 0 && k + 1 < got.size() && c.nq % 8 != 0) return 26;
+                    next = c.q0 + c.nq;
+                }
+                if (next != nq) return 27;
+                cases++, n_chunks += got.size();
+                return 0;
+            };
+            auto all_limits = [&](const std::vector<uint64_t> *lens, uint64_t nq, uint64_t uniform_len, uint64_t first) {
+                for (uint64_t bytes : {uint64_t(1), uint64_t(600), uint64_t(1500), uint64_t(6000), uint64_t(32) << 20, uint64_t(128) << 20})
+                    for (uint64_t queries : {uint64_t(1), uint64_t(8), uint64_t(97), uint64_t(388), uint64_t(1) << 20})
+                        if (const int rc = check(lens, nq, uniform_len, first, bytes, queries)) return rc;
+                return 0;
+            };
+            const uint64_t big = 7000;  // longer than every byte limit below 32 MB
+            std::vector<std::vector<uint64_t>> made = {std::vector<uint64_t>(1000, 0), {0}, {50}, {big}, {big, 40, 41, 42}, {40, 41, big, 42, 43},
+                                                       {40, 41, 42, big}, {big, big, big}, std::vector<uint64_t>(500, 1), {0, 0, big, 0, 0}};
+            for (const auto &lens : made)
+                for (uint64_t first : {uint64_t(0), uint64_t(13)})
+                    if (const int rc = all_limits(&lens, lens.size(), 0, first)) return rc;
+            for (int round = 0; round < 40; round++) {
+                std::vector<uint64_t> lens(1 + rnd() % 3000);
+                for (uint64_t &l : lens) l = rnd() % 100 == 0 ? rnd() % 9000 : 18 + rnd() % 53;
+                if (const int rc = all_limits(&lens, lens.size(), 0, rnd() % 100)) return rc;
+            }
+            for (uint64_t ul : {uint64_t(1), uint64_t(50), (uint64_t(1) << 21) - 1})
+                for (uint64_t nq : {uint64_t(1), uint64_t(7), uint64_t(8), uint64_t(9), uint64_t(1000), uint64_t(4001)})
+                    if (const int rc = all_limits(nullptr, nq, ul, 0)) return rc;
+            // the wire layout: 256-byte aligned sections, in order, each as long as its content at least, `bytes` behind the last
+            for (uint64_t max_nq : {uint64_t(1), uint64_t(2047), uint64_t(2048), uint64_t(2049), uint64_t(100000)})
+                for (uint64_t n_texts : {uint64_t(1), uint64_t(2)}) {
+                    const gdx::WireLayout w = gdx::make_wire_layout(max_nq, n_texts);
+                    const uint64_t tiles = (max_nq + gdx::kHostWireTile - 1) / gdx::kHostWireTile;
+                    for (uint64_t o : {w.bitmap, w.tile_found, w.tile_off, w.found_pos, w.found_ids})
+                        if (o % 256 != 0) return 30;
+                    if (w.bitmap < 16) return 31;  // (the meta in front)
+                    if (w.tile_found < w.bitmap + tiles * 256 || w.tile_off < w.tile_found + (tiles + 1) * 4 ||
+                        w.found_pos < w.tile_off + (tiles + 1) * 4 || w.found_ids < w.found_pos + (max_nq + 1) * 4)
+                        return 32;
+                    if (w.ids != (n_texts > 1) || w.bytes != w.found_ids + (w.ids ? max_nq + 1 : 0)) return 33;
+                    if (w.exc_reads != 0 || w.exc_counts != max_nq * 4 || w.exc_hits != max_nq * 8) return 34;
+                    cases++;
+                }
+            std::printf("ok %" PRIu64 " %" PRIu64 "\n", cases, n_chunks);
         } else {
             return 2;
         }

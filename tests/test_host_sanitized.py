@@ -169,3 +169,14 @@ def test_host_wire_expansion_equals_the_plain_construction(checker):
         assert rc == 0 and out.startswith("ok "), (nq, texts, found, rc, out)
         if nq >= 4096 and found < 10 and exc_one_in == 3:
             assert int(out.split()[2]) > 0
+
+
+def test_host_chunk_planner_and_wire_layout(checker):
+    """host_plan.hpp (how the host-pointer pipeline cuts a batch into chunks, and where the sections of a chunk's wire lie)
+    under ASan + UBSan on offset arrays of exactly nq + 1 entries: the chunks tile the batch in order, respect both limits but
+    for a single over-long query, hold a multiple of 8 queries in the uniform form, and are list for list those of the loop as
+    it stood inside the pipeline; the wire's sections are 256-byte aligned, in order and do not overlap."""
+    for seed in (1, 2, 3):
+        rc, out = checker("chunks", seed)
+        assert rc == 0 and out.startswith("ok "), (seed, rc, out)
+        assert int(out.split()[1]) > 2000 and int(out.split()[2]) > 100000
