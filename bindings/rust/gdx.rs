@@ -151,6 +151,9 @@ pub const GDX_BEST_MAX_GROUP_SLOTS: u32 = 64;
 pub const GDX_PAIR_NONE: u32 = 0xFFFF_FFFF;
 pub const GDX_PAIR_MAPQ_NONE: u32 = 255;
 pub const GDX_PAIR_MAX_MATE_SLOTS: u32 = 32;
+pub const GDX_RESCUE_NONE: u32 = 0xFFFF_FFFF;
+pub const GDX_RESCUE_NOT_TRIED: u32 = 0xFFFF_FFFD;
+pub const GDX_RESCUE_MAX_SPREAD: u32 = 4096;
 
 /// gdx_query_layout_t
 #[repr(C)]
@@ -362,6 +365,25 @@ extern "C" {
         out_pair_span: *mut u32, out_mate_slot: *mut u32, out_mate_dist: *mut u32, out_win_query: *mut u32,
         out_win_begin: *mut u32, out_win_hits: *mut Hit,
     ) -> c_int;
+    /// Mate rescue (include/gdx_experimental.h "mate rescue"): for every pair without a proper combination, each placed mate is
+    /// the anchor from which the other mate's opposite strand is searched in the insert window of the anchor's text (queries
+    /// 4p .. 4p + 3 are both strands of both mates of pair p); per mate the attempt's distance and end, per pair the better
+    /// successful attempt, and the merged winners for gdx_align_many in place of those of gdx_pair_hits_many
+    pub fn gdx_mate_rescue_many_dev(
+        ix: *const gdx_index_t, d_qbuf: *const c_void, d_qoff: *const c_void, nq: u64, layout: *const QueryLayout, n_pairs: u64,
+        mate_slots: u32, d_end: *const c_void, d_n_proper: *const c_void, d_mate_slot: *const c_void, d_mate_dist: *const c_void,
+        d_win_query: *const c_void, d_win_begin: *const c_void, d_win_hits: *const c_void, max_edits: u32, min_insert: u32,
+        max_insert: u32, d_resc_dist: *mut c_void, d_resc_end: *mut c_void, d_resc_mate: *mut c_void, d_resc_pair_dist: *mut c_void,
+        d_resc_span: *mut c_void, d_out_win_query: *mut c_void, d_out_win_begin: *mut c_void, d_out_win_hits: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
+    pub fn gdx_mate_rescue_many(
+        ix: *const gdx_index_t, qbuf: *const u8, qoff: *const u64, nq: u64, n_pairs: u64, mate_slots: u32, end: *const u32,
+        n_proper: *const u32, mate_slot: *const u32, mate_dist: *const u32, win_query: *const u32, win_begin: *const u32,
+        win_hits: *const Hit, max_edits: u32, min_insert: u32, max_insert: u32, out_resc_dist: *mut u32, out_resc_end: *mut u32,
+        out_resc_mate: *mut u32, out_resc_pair_dist: *mut u32, out_resc_span: *mut u32, out_win_query: *mut u32,
+        out_win_begin: *mut u32, out_win_hits: *mut Hit,
+    ) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
     ) -> c_int;
@@ -558,6 +580,19 @@ pub struct PairHit {
     pub mapq: u32,
     pub pair_span: u32,
     pub mates: [MateHit; 2],
+}
+
+/// One pair after `GpuFmIndex::mate_rescue_many`.  `attempts[o]` = (resc_dist, resc_end) of mate o: dist GDX_RESCUE_NOT_TRIED where
+/// no attempt exists, max_edits + 1 (and end GDX_EDIT_NO_END) where it found nothing.  `rescued` = Some(o) when mate o was placed
+/// from the other mate; then pair_dist is the anchor's distance plus the attempt's and span the fragment's length, otherwise
+/// 2 max_edits + 2 and 0.  `winners` = (cand_query, cand_begin, hit) per mate, candidates of `align_many`.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct RescuedPair {
+    pub attempts: [(u32, u32); 2],
+    pub rescued: Option<u32>,
+    pub pair_dist: u32,
+    pub span: u32,
+    pub winners: [(u32, u32, Hit); 2],
 }
 
 /// Hits of one call, owned by the library's allocation; handed out per query without copying.
@@ -970,6 +1005,48 @@ impl GpuFmIndex {
                 mapq: pairs[4][g],
                 pair_span: pairs[5][g],
                 mates: [mate(2 * g), mate(2 * g + 1)],
+            })
+            .collect()
+    }
+
+    /// Mate rescue behind `pair_hits_many`: `queries` are the four strands of every pair (mate 0, its reverse complement, mate 1,
+    /// its reverse complement), `end` the ends `edit_distance_many` gave for all 2 * pairs * mate_slots slots and `pairs` what
+    /// `pair_hits_many` returned for them.  For a pair without a proper combination every placed mate serves as the anchor from
+    /// which the other mate is searched, on the opposite strand, where min_insert <= span <= max_insert puts it, with at most
+    /// `max_edits` (at most 256) edits.  Panics when the slices do not fit `pairs`, on insert bounds that are not min_insert <=
+    /// max_insert <= 2^31 - 1 or lie more than GDX_RESCUE_MAX_SPREAD apart, and on an index without text units.
+    pub fn mate_rescue_many<Q: AsRef<[u8]>>(
+        &self, queries: impl IntoIterator<Item = Q>, mate_slots: u32, end: &[u32], pairs: &[PairHit], max_edits: u32, min_insert: u32,
+        max_insert: u32,
+    ) -> Vec<RescuedPair> {
+        let np = pairs.len();
+        let (buf, off) = pack(queries);
+        assert!(off.len() - 1 == 4 * np && end.len() == 2 * np * mate_slots as usize);
+        let mates = || pairs.iter().flat_map(|p| p.mates.iter());
+        let n_proper: Vec<u32> = pairs.iter().map(|p| p.n_proper).collect();
+        let mate_slot: Vec<u32> = mates().map(|m| m.slot.unwrap_or(GDX_PAIR_NONE)).collect();
+        let mate_dist: Vec<u32> = mates().map(|m| m.dist).collect();
+        let win_query: Vec<u32> = mates().map(|m| m.winner.0).collect();
+        let win_begin: Vec<u32> = mates().map(|m| m.winner.1).collect();
+        let win_hits: Vec<Hit> = mates().map(|m| m.winner.2).collect();
+        let mut per_mate: Vec<Vec<u32>> = (0..4).map(|_| vec![0u32; 2 * np]).collect();
+        let mut per_pair: Vec<Vec<u32>> = (0..3).map(|_| vec![0u32; np]).collect();
+        let mut win = vec![Hit { text_id: 0, position: 0 }; 2 * np];
+        let m: Vec<*mut u32> = per_mate.iter_mut().map(|v| v.as_mut_ptr()).collect();
+        let p: Vec<*mut u32> = per_pair.iter_mut().map(|v| v.as_mut_ptr()).collect();
+        check(unsafe {
+            gdx_mate_rescue_many(self.raw, buf.as_ptr(), off.as_ptr(), (off.len() - 1) as u64, np as u64, mate_slots, end.as_ptr(),
+                                 n_proper.as_ptr(), mate_slot.as_ptr(), mate_dist.as_ptr(), win_query.as_ptr(), win_begin.as_ptr(),
+                                 win_hits.as_ptr(), max_edits, min_insert, max_insert, m[0], m[1], p[0], p[1], p[2], m[2], m[3],
+                                 win.as_mut_ptr())
+        });
+        (0..np)
+            .map(|g| RescuedPair {
+                attempts: [(per_mate[0][2 * g], per_mate[1][2 * g]), (per_mate[0][2 * g + 1], per_mate[1][2 * g + 1])],
+                rescued: if per_pair[0][g] == GDX_RESCUE_NONE { None } else { Some(per_pair[0][g]) },
+                pair_dist: per_pair[1][g],
+                span: per_pair[2][g],
+                winners: [(per_mate[2][2 * g], per_mate[3][2 * g], win[2 * g]), (per_mate[2][2 * g + 1], per_mate[3][2 * g + 1], win[2 * g + 1])],
             })
             .collect()
     }

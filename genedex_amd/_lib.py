@@ -48,6 +48,9 @@ GDX_BEST_MAX_GROUP_SLOTS = 64     # group_slots at most
 GDX_PAIR_NONE = 0xFFFFFFFF        # gdx_pair_hits_many[_dev]: mate_slot of a mate without a live slot
 GDX_PAIR_MAPQ_NONE = 255          # mapq of a pair without a proper combination
 GDX_PAIR_MAX_MATE_SLOTS = 32      # mate_slots at most
+GDX_RESCUE_NONE = 0xFFFFFFFF      # gdx_mate_rescue_many[_dev]: resc_mate of a pair without a successful attempt
+GDX_RESCUE_NOT_TRIED = 0xFFFFFFFD  # resc_dist of a mate without an attempt
+GDX_RESCUE_MAX_SPREAD = 4096      # max_insert - min_insert at most
 GDX_Q_OK = 0
 GDX_Q_INVALID_SYMBOL = 1
 GDX_Q_UNSEARCHABLE_IN_LOOKUP = 2
@@ -171,6 +174,7 @@ SIGNATURES = {
     "gdx_multi_from_indexes": [C.POINTER(vp), C.c_int, C.POINTER(vp)],
     "gdx_multi_free": [vp],
     "gdx_debug_force_wide": [C.c_int],
+    "gdx_debug_set_rescue_tiling": [C.c_uint64, C.c_uint64],
     "gdx_parts_build": [vp, C.c_int, u64p, C.c_uint64, u8p, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_uint64,
                         C.POINTER(BuildOptions), C.POINTER(vp)],
     "gdx_parts_free": [vp],
@@ -267,6 +271,10 @@ SIGNATURES = {
                                vp, vp, vp, vp, vp, vp],
     "gdx_pair_hits_many": [vp, C.c_uint64, C.c_uint32, u32p, u32p, C.POINTER(HitStruct), u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
                            u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.POINTER(HitStruct)],
+    "gdx_mate_rescue_many_dev": [vp, vp, vp, C.c_uint64, C.POINTER(QueryLayout), C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32,
+                                 C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "gdx_mate_rescue_many": [vp, u8p, u64p, C.c_uint64, C.c_uint64, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p, C.POINTER(HitStruct),
+                             C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.POINTER(HitStruct)],
     # gdx_bench.h
     "gdx_index_build_stats": [vp, C.POINTER(BuildStats)],
     "gdx_synth_text_dev": [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp],

@@ -1848,6 +1848,45 @@ int gdx_pair_hits_many(const gdx_index_t *ix, uint64_t n_pairs, uint32_t mate_sl
     });
 }
 
+// ---- mate rescue (mate_rescue.hip) ------------------------------------------------------------------------------
+
+int gdx_mate_rescue_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq, const gdx_query_layout_t *layout,
+                             uint64_t n_pairs, uint32_t mate_slots, const void *d_end, const void *d_n_proper, const void *d_mate_slot,
+                             const void *d_mate_dist, const void *d_win_query, const void *d_win_begin, const void *d_win_hits,
+                             uint32_t max_edits, uint32_t min_insert, uint32_t max_insert, void *d_resc_dist, void *d_resc_end,
+                             void *d_resc_mate, void *d_resc_pair_dist, void *d_resc_span, void *d_out_win_query, void *d_out_win_begin,
+                             void *d_out_win_hits, void *stream)
+{
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        const gdx::SearchCall c = query_side(d_qbuf, d_qoff, nq, layout);
+        d.f.check_mate_rescue(c.packed, nq, n_pairs, mate_slots, max_edits, min_insert, max_insert);
+        if (n_pairs == 0) return;
+        if (gdx::any_null({d_qbuf, d_end, d_n_proper, d_mate_slot, d_mate_dist, d_win_query, d_win_begin, d_win_hits, d_resc_dist, d_resc_end,
+                           d_resc_mate, d_resc_pair_dist, d_resc_span, d_out_win_query, d_out_win_begin, d_out_win_hits}))
+            gdx::fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+        d.enter();
+        const gdx::RescueCall call = {n_pairs, mate_slots, max_edits, min_insert, max_insert, u32(d_end), u32(d_n_proper), u32(d_mate_slot),
+                                      u32(d_mate_dist), u32(d_win_query), u32(d_win_begin), static_cast<const gdx_hit32_t *>(d_win_hits),
+                                      u32(d_resc_dist), u32(d_resc_end), u32(d_resc_mate), u32(d_resc_pair_dist), u32(d_resc_span),
+                                      u32(d_out_win_query), u32(d_out_win_begin), static_cast<gdx_hit32_t *>(d_out_win_hits)};
+        gdx::launch_mate_rescue(d.f.view(), c.d_qbuf, c.d_qbeg, c.packed, c.uniform_len, call, d.st);
+    });
+}
+
+int gdx_mate_rescue_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint64_t n_pairs,
+                         uint32_t mate_slots, const uint32_t *end, const uint32_t *n_proper, const uint32_t *mate_slot,
+                         const uint32_t *mate_dist, const uint32_t *win_query, const uint32_t *win_begin, const gdx_hit_t *win_hits,
+                         uint32_t max_edits, uint32_t min_insert, uint32_t max_insert, uint32_t *out_resc_dist, uint32_t *out_resc_end,
+                         uint32_t *out_resc_mate, uint32_t *out_resc_pair_dist, uint32_t *out_resc_span, uint32_t *out_win_query,
+                         uint32_t *out_win_begin, gdx_hit_t *out_win_hits)
+{
+    return guarded([&] {
+        return deref(ix).mate_rescue_many(qbuf, qoff, nq, n_pairs, mate_slots, end, n_proper, mate_slot, mate_dist, win_query, win_begin,
+                                          win_hits, max_edits, min_insert, max_insert, out_resc_dist, out_resc_end, out_resc_mate,
+                                          out_resc_pair_dist, out_resc_span, out_win_query, out_win_begin, out_win_hits);
+    });
+}
+
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {
@@ -1948,6 +1987,12 @@ int gdx_bench_lf_walk_dev(const gdx_index_t *ix, const void *d_rows, uint64_t m,
 int gdx_debug_force_wide(int on)
 {
     g_force_wide.store(on != 0 ? 1 : 0);
+    return GDX_OK;
+}
+
+int gdx_debug_set_rescue_tiling(uint64_t tile_pairs, uint64_t grid)
+{
+    gdx::set_rescue_tiling(tile_pairs, grid);
     return GDX_OK;
 }
 

@@ -2648,6 +2648,59 @@ int FmIndex::pair_hits_many(uint64_t n_pairs, uint32_t mate_slots, const uint32_
     return GDX_OK;
 }
 
+void FmIndex::check_mate_rescue(bool packed, uint64_t nq, uint64_t n_pairs, uint32_t mate_slots, uint32_t max_edits, uint32_t min_insert,
+                                uint32_t max_insert) const
+{
+    check_edit_distance(packed, max_edits);
+    if (mate_slots == 0 || mate_slots > GDX_PAIR_MAX_MATE_SLOTS)
+        fail(GDX_ERR_INVALID_ARGUMENT, "mate_slots must be 1..%u", GDX_PAIR_MAX_MATE_SLOTS);
+    if (min_insert > max_insert || max_insert > 0x7fffffffu)
+        fail(GDX_ERR_INVALID_ARGUMENT, "insert bounds [%u, %u]: min_insert <= max_insert <= 2^31 - 1", min_insert, max_insert);
+    if (max_insert - min_insert > GDX_RESCUE_MAX_SPREAD)
+        fail(GDX_ERR_INVALID_ARGUMENT, "insert bounds [%u, %u] are more than GDX_RESCUE_MAX_SPREAD (%u) apart", min_insert, max_insert,
+             GDX_RESCUE_MAX_SPREAD);
+    if (nq >= 0xffffffffull) fail(GDX_ERR_INVALID_ARGUMENT, "more than 2^32 - 2 queries (win_query is 32 bits wide)");
+    if (nq % 4 != 0 || nq / 4 != n_pairs)  // (not 4 * n_pairs, which wraps)
+        fail(GDX_ERR_INVALID_ARGUMENT, "%llu queries for %llu pairs: a pair is four queries (both strands of both mates)",
+             (unsigned long long)nq, (unsigned long long)n_pairs);
+}
+
+int FmIndex::mate_rescue_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint64_t n_pairs, uint32_t mate_slots,
+                              const uint32_t *end, const uint32_t *n_proper, const uint32_t *mate_slot, const uint32_t *mate_dist,
+                              const uint32_t *win_query, const uint32_t *win_begin, const gdx_hit_t *win_hits, uint32_t max_edits,
+                              uint32_t min_insert, uint32_t max_insert, uint32_t *out_resc_dist, uint32_t *out_resc_end,
+                              uint32_t *out_resc_mate, uint32_t *out_resc_pair_dist, uint32_t *out_resc_span, uint32_t *out_win_query,
+                              uint32_t *out_win_begin, gdx_hit_t *out_win_hits) const
+{
+    check_mate_rescue(false, nq, n_pairs, mate_slots, max_edits, min_insert, max_insert);
+    check_queries(qbuf, qoff, nq);
+    if (n_pairs == 0) return GDX_OK;
+    if (any_null({end, n_proper, mate_slot, mate_dist, win_query, win_begin, win_hits, out_resc_dist, out_resc_end, out_resc_mate,
+                  out_resc_pair_dist, out_resc_span, out_win_query, out_win_begin, out_win_hits}))
+        fail(GDX_ERR_INVALID_ARGUMENT, "null argument");
+    const uint64_t n_mates = 2 * n_pairs, n_slots = n_mates * mate_slots;
+    hipStream_t stream = hipStreamPerThread;
+    // the winners travel as slots do: query, begin, mate_dist in the place of dist and mate_slot in that of end
+    DeviceSlots win(*this, win_query, win_begin, win_hits, mate_dist, mate_slot, n_mates, stream);
+    const SlotArgs w = win.args(0, nullptr, nullptr, nullptr);
+    DeviceQueries dq(qbuf, qoff, nq, stream);
+    DeviceBuffer<uint32_t> d_in(n_slots + n_pairs);  // end, n_proper
+    GDX_HIP(hipMemcpyAsync(d_in.get(), end, n_slots * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    GDX_HIP(hipMemcpyAsync(d_in.get() + n_slots, n_proper, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    DeviceBuffer<uint32_t> d_out(11 * n_pairs);  // four per mate, then three per pair
+    DeviceBuffer<gdx_hit32_t> d_win(n_mates);
+    uint32_t *o = d_out.get(), *per_pair = o + 4 * n_mates;
+    const RescueCall call = {n_pairs, mate_slots, max_edits, min_insert, max_insert, d_in.get(), d_in.get() + n_slots, w.end, w.dist,
+                             w.cand_query, w.cand_begin, w.cand_hits, o, o + n_mates, per_pair, per_pair + n_pairs,
+                             per_pair + 2 * n_pairs, o + 2 * n_mates, o + 3 * n_mates, d_win.get()};
+    launch_mate_rescue(view_, dq.qbuf.get(), dq.qoff.get(), false, 0, call, stream);
+    GDX_HIP(hipGetLastError());
+    download_columns({out_resc_dist, out_resc_end, out_win_query, out_win_begin}, o, n_mates, stream);
+    download_columns({out_resc_mate, out_resc_pair_dist, out_resc_span}, per_pair, n_pairs, stream);
+    widen_hits(out_win_hits, n_mates, d_win.get(), stream);
+    return GDX_OK;
+}
+
 int FmIndex::rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const
 {
     if (m == 0) return GDX_OK;

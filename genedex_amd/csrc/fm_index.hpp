@@ -184,6 +184,15 @@ public:
                        uint32_t *out_mate_dist, uint32_t *out_win_query, uint32_t *out_win_begin, gdx_hit_t *out_win_hits) const;
     // what both forms of gdx_pair_hits_many refuse before they look at the batch
     void check_pair_hits(uint64_t n_pairs, uint32_t mate_slots, uint32_t max_dist, uint32_t min_insert, uint32_t max_insert) const;
+    // gdx_mate_rescue_many: the queries staged like edit_distance_many, the winners like pair_hits_many; one launch
+    int mate_rescue_many(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint64_t n_pairs, uint32_t mate_slots, const uint32_t *end,
+                         const uint32_t *n_proper, const uint32_t *mate_slot, const uint32_t *mate_dist, const uint32_t *win_query,
+                         const uint32_t *win_begin, const gdx_hit_t *win_hits, uint32_t max_edits, uint32_t min_insert, uint32_t max_insert,
+                         uint32_t *out_resc_dist, uint32_t *out_resc_end, uint32_t *out_resc_mate, uint32_t *out_resc_pair_dist,
+                         uint32_t *out_resc_span, uint32_t *out_win_query, uint32_t *out_win_begin, gdx_hit_t *out_win_hits) const;
+    // what both forms of gdx_mate_rescue_many refuse before they look at the batch: check_edit_distance's, and the pairing knobs
+    void check_mate_rescue(bool packed, uint64_t nq, uint64_t n_pairs, uint32_t mate_slots, uint32_t max_edits, uint32_t min_insert,
+                           uint32_t max_insert) const;
     int rank_many(const uint8_t *symbols, const uint64_t *idx, uint64_t m, uint64_t *out) const;
     int symbol_at_many(const uint64_t *idx, uint64_t m, uint8_t *out) const;
 

@@ -231,6 +231,30 @@ void launch_best_hits(const BestArgs &a, hipStream_t stream);
 struct PairArgs;
 void launch_pair_hits(const PairArgs &a, hipStream_t stream);
 
+// ---- mate_rescue.hip ----------------------------------------------------------------------
+// gdx_mate_rescue_many_dev: the batch of 4 * n_pairs queries gdx_strands_expand_dev makes of interleaved mates, in any of the four
+// layouts (uniform_len != 0: d_qoff unused), the `end` slots of the edit-distance call and six outputs of launch_pair_hits -> per
+// mate of a pair without a proper combination the other mate's opposite strand searched in the insert window of the text, per pair
+// the better successful attempt, and the merged winners for launch_align.  The caller has checked 1 <= mate_slots <=
+// GDX_PAIR_MAX_MATE_SLOTS, max_edits <= 256, min_insert <= max_insert <= 2^31 - 1, max_insert - min_insert <=
+// GDX_RESCUE_MAX_SPREAD and 4 * n_pairs < 2^32 - 1.  ix must hold text units.  One launch.
+struct RescueCall {
+    uint64_t n_pairs;
+    uint32_t mate_slots, max_edits, min_insert, max_insert;
+    const uint32_t *end;  // u32[2 n_pairs mate_slots]
+    const uint32_t *n_proper, *mate_slot, *mate_dist, *win_query, *win_begin;
+    const gdx_hit32_t *win_hits;
+    uint32_t *resc_dist, *resc_end;                    // u32[2 n_pairs]
+    uint32_t *resc_mate, *resc_pair_dist, *resc_span;  // u32[n_pairs]
+    uint32_t *out_win_query, *out_win_begin;           // u32[2 n_pairs]
+    gdx_hit32_t *out_win_hits;
+};
+void launch_mate_rescue(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *d_qoff, bool packed, uint32_t uniform_len,
+                        const RescueCall &call, hipStream_t stream);
+// tests and experiments (gdx_debug_set_rescue_tiling): pairs per tile (rounded up to whole sweeps of 256) and workgroups of the
+// launches to come, 0 = the launcher's own choice; the results do not depend on either
+void set_rescue_tiling(uint64_t tile_pairs, uint64_t grid);
+
 // ---- locate.hip ---------------------------------------------------------------------------
 size_t hit_offsets_temp_bytes(uint64_t m);
 void launch_hit_offsets(const uint32_t *d_start, const uint32_t *d_end, uint64_t m, uint64_t *d_hit_offsets,

@@ -645,8 +645,41 @@ class DeviceEngine:
             _stream()))
         return out
 
+    # ---- mate rescue (gdx_mate_rescue_many_dev) -------------------------------------------------------------------
+    def alloc_mate_rescue(self, n_pairs: int):
+        n_mates = 2 * max(n_pairs, 1)
+        return self._alloc_u32((n_mates, ("resc_dist", "resc_end", "win_query", "win_begin")),
+                               (n_pairs, ("resc_mate", "resc_pair_dist", "resc_span")), hits=(n_mates, "win_hits"))
+
+    def mate_rescue(self, q: DeviceQueries, end: torch.Tensor, pairs: dict, n_pairs: int, mate_slots: int, max_edits: int,
+                    min_insert: int, max_insert: int, out: dict = None):
+        """One launch: for every pair without a proper combination each placed mate is the anchor from which the other mate's
+        opposite strand is searched in the window of the text that min_insert <= span <= max_insert implies, within max_edits
+        (at most 256) edits; max_insert - min_insert is at most 4096 (GDX_RESCUE_MAX_SPREAD).  q: the batch with_strands("both")
+        made of the interleaved mates, 4 * n_pairs queries in any form; end: what edit_distance() returned for all 2 * n_pairs *
+        mate_slots slots; pairs: the `out` dict of pair_hits() as it is.  Results in `out` (alloc_mate_rescue; made here when
+        None) -> out.  Per mate "resc_dist" (-3, GDX_RESCUE_NOT_TRIED, without an attempt; max_edits + 1 when nothing was found)
+        and "resc_end"; per pair "resc_mate" (the rescued mate, -1 = GDX_RESCUE_NONE), "resc_pair_dist" and "resc_span"; and the
+        merged winners "win_query", "win_begin", "win_hits", which go into align() in place of those of pair_hits()."""
+        n_pairs, mate_slots = int(n_pairs), int(mate_slots)
+        if end is None or end.numel() < 2 * n_pairs * mate_slots:
+            raise ValueError("end holds 2 * n_pairs * mate_slots slots")
+        if any(pairs[name].numel() < n for n, names in ((n_pairs, ("n_proper",)), (2 * n_pairs, ("mate_slot", "mate_dist", "win_query",
+               "win_begin")), (4 * n_pairs, ("win_hits",))) for name in names):
+            raise ValueError("pairs holds the outputs of pair_hits() for n_pairs pairs")
+        if out is None:
+            out = self.alloc_mate_rescue(n_pairs)
+        lay, qoff = q.layout()
+        _lib.check(self.lib.gdx_mate_rescue_many_dev(
+            self.h, _ptr(q.qbuf), qoff, q.nq, _layout_arg(lay), n_pairs, mate_slots, _ptr(end), _ptr(pairs["n_proper"]),
+            _ptr(pairs["mate_slot"]), _ptr(pairs["mate_dist"]), _ptr(pairs["win_query"]), _ptr(pairs["win_begin"]),
+            _ptr(pairs["win_hits"]), int(max_edits), int(min_insert), int(max_insert), _ptr(out["resc_dist"]), _ptr(out["resc_end"]),
+            _ptr(out["resc_mate"]), _ptr(out["resc_pair_dist"]), _ptr(out["resc_span"]), _ptr(out["win_query"]),
+            _ptr(out["win_begin"]), _ptr(out["win_hits"]), _stream()))
+        return out
+
     def map_pairs(self, q: DeviceQueries, reversed_index, *, max_smems: int, min_length: int, max_occ: int, band: int,
-                  max_candidates: int, max_edits: int, min_insert: int, max_insert: int) -> dict:
+                  max_candidates: int, max_edits: int, min_insert: int, max_insert: int, rescue: bool = False) -> dict:
         """map_reads for paired reads.  q: a plain batch with the mates interleaved, reads 2p and 2p + 1 being the mates of pair p
         (an odd q.nq raises ValueError).  with_strands("both") -> smems -> seed_candidates -> edit_distance -> pair_hits ->
         best_hits per mate (for the single-end figures) -> align over the 2 * n_pairs winners of pair_hits.
@@ -654,7 +687,10 @@ class DeviceEngine:
         "n_cigar", "cigar" (int32[mates, 2 max_edits + 1]) and the single-end "mapq", "n_best", "sub_dist" of map_reads;
         per-pair tensors: "n_proper", "pair_n_best", "pair_dist", "pair_sub_dist", "pair_mapq" (255 without a proper
         combination), "pair_span".  A mate of a pair without a proper combination is placed as map_reads places it; an unmapped
-        mate has n_cigar 0, begin and end -1 and dist max_edits + 1.  No result crosses to the host in between."""
+        mate has n_cigar 0, begin and end -1 and dist max_edits + 1.  No result crosses to the host in between.
+        rescue=True puts mate_rescue() between pair_hits and align, which then runs over the merged winners, and adds the per-mate
+        "rescued" (1 for a mate placed from its partner, else 0) and the per-pair "resc_mate", "resc_pair_dist", "resc_span"; for
+        a rescued mate "strand" and "text_id" are the rescue candidate's and "dist" is align's own distance."""
         if q.nq % 2:
             raise ValueError("map_pairs takes the mates interleaved: an even number of reads")
         n_mates, n_pairs, mc = q.nq, q.nq // 2, int(max_candidates)
@@ -665,12 +701,22 @@ class DeviceEngine:
         dist, end = self.edit_distance(sq, cands["cand_query"], cands["cand_begin"], cands["cand_hits"], max_edits)
         pairs = self.pair_hits(cands, dist, end, n_pairs, 2 * mc, max_edits, min_insert, max_insert)
         single = self.best_hits(cands, dist, end, n_mates, 2 * mc, max_edits)
-        aligned = self.align(sq, pairs["win_query"][:n_mates], pairs["win_begin"][:n_mates], pairs["win_hits"][:n_mates], max_edits)
-        per_mate = {"strand": pairs["win_query"] & 1, "text_id": pairs["win_hits"][:, 0], "begin": aligned["begin"],
-                    "end": aligned["end"], "dist": pairs["mate_dist"], "n_cigar": aligned["n_cigar"], "cigar": aligned["cigar"],
+        win, dist_of = pairs, pairs["mate_dist"]
+        if rescue:
+            win = self.mate_rescue(sq, end, pairs, n_pairs, 2 * mc, max_edits, min_insert, max_insert)
+        aligned = self.align(sq, win["win_query"][:n_mates], win["win_begin"][:n_mates], win["win_hits"][:n_mates], max_edits)
+        per_mate = {"strand": win["win_query"] & 1, "text_id": win["win_hits"][:, 0], "begin": aligned["begin"],
+                    "end": aligned["end"], "dist": dist_of, "n_cigar": aligned["n_cigar"], "cigar": aligned["cigar"],
                     "mapq": single["mapq"], "n_best": single["n_best"], "sub_dist": single["sub_dist"]}
         per_pair = {"n_proper": pairs["n_proper"], "pair_n_best": pairs["n_best"], "pair_dist": pairs["pair_dist"],
                     "pair_sub_dist": pairs["sub_dist"], "pair_mapq": pairs["mapq"], "pair_span": pairs["pair_span"]}
+        if rescue:
+            # mate 2p + o is rescued when resc_mate[p] == o (resc_mate is -1 without a rescue)
+            mate_of = torch.arange(2 * max(n_pairs, 1), dtype=torch.int32, device=self.dev)
+            rescued = (win["resc_mate"].repeat_interleave(2) == (mate_of & 1)).to(torch.int32)
+            per_mate["rescued"] = rescued
+            per_mate["dist"] = torch.where(rescued != 0, aligned["dist"], dist_of)
+            per_pair.update({name: win[name] for name in ("resc_mate", "resc_pair_dist", "resc_span")})
         # (the buffers hold at least one entry: an empty batch gets empty tensors, not that unwritten row)
         return {**{name: t[:n_mates] for name, t in per_mate.items()}, **{name: t[:n_pairs] for name, t in per_pair.items()}}
 

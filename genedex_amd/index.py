@@ -634,6 +634,41 @@ class FmIndex:
                                                 win.ctypes.data_as(C.POINTER(_lib.HitStruct))))
         return tuple(o[:n] for o in pairs) + tuple(o[:2 * n] for o in mates) + (win[:2 * n, 0], win[:2 * n, 1])
 
+    # ---- mate rescue (gdx_experimental.h "mate rescue") -------------------------------------------------------
+    def mate_rescue_raw(self, qbuf, qoff, end, n_proper, mate_slot, mate_dist, win_query, win_begin, win_text_ids, win_positions,
+                        n_pairs, mate_slots, max_edits, min_insert, max_insert):
+        """gdx_mate_rescue_many -> (resc_dist, resc_end: u32[2 n_pairs]; resc_mate, resc_pair_dist, resc_span: u32[n_pairs];
+        win_query, win_begin: u32[2 n_pairs]; win_text_ids, win_positions: u64[2 n_pairs]).  qbuf / qoff: the 4 * n_pairs queries
+        (both strands of both mates of every pair); end: the ends of the edit-distance call over all 2 * n_pairs * mate_slots
+        slots; the other inputs as pair_hits_raw returned them.  For a pair without a proper combination every placed mate is
+        the anchor from which the other mate's opposite strand is searched where min_insert <= span <= max_insert puts it."""
+        n, ms = int(n_pairs), int(mate_slots)
+        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
+        qoff = np.ascontiguousarray(qoff, dtype=np.uint64)
+        u32 = lambda x, size, what: self._sized(np.ascontiguousarray(np.asarray(x).astype(np.uint32)), size, what)  # noqa: E731
+        end = u32(end, 2 * n * ms, "end")
+        n_proper = u32(n_proper, n, "n_proper")
+        per_mate = [u32(x, 2 * n, "a per-mate input") for x in (mate_slot, mate_dist, win_query, win_begin)]
+        hits = np.ascontiguousarray(np.stack([np.asarray(win_text_ids).astype(np.uint64), np.asarray(win_positions).astype(np.uint64)],
+                                             axis=1))
+        self._sized(hits, 4 * n, "win_hits")
+        mates = [np.zeros(max(2 * n, 1), dtype=np.uint32) for _ in range(4)]       # resc_dist, resc_end, win_query, win_begin
+        pairs = [np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3)]
+        win = np.zeros((max(2 * n, 1), 2), dtype=np.uint64)
+        _lib.check(self._lib.gdx_mate_rescue_many(
+            self._h, _p(qbuf, u8p), _p(qoff, u64p), qoff.size - 1, n, ms, _p(end, u32p), _p(n_proper, u32p),
+            *(_p(x, u32p) for x in per_mate), hits.ctypes.data_as(C.POINTER(_lib.HitStruct)), int(max_edits), int(min_insert),
+            int(max_insert), _p(mates[0], u32p), _p(mates[1], u32p), *(_p(o, u32p) for o in pairs), _p(mates[2], u32p),
+            _p(mates[3], u32p), win.ctypes.data_as(C.POINTER(_lib.HitStruct))))
+        return (mates[0][:2 * n], mates[1][:2 * n]) + tuple(o[:n] for o in pairs) + (mates[2][:2 * n], mates[3][:2 * n],
+                                                                                    win[:2 * n, 0], win[:2 * n, 1])
+
+    @staticmethod
+    def _sized(x, size, what):
+        if x.size < size:
+            raise ValueError(f"{what} holds {x.size} entries, {size} are needed")
+        return x
+
     def rank_many(self, symbols, idx):
         """TextWithRankSupport::rank (text_with_rank_support/mod.rs:106-110), batched."""
         sym = np.ascontiguousarray(symbols, dtype=np.uint8)

@@ -50,6 +50,11 @@ int gdx_debug_force_wide(int on);
  * 2^20 queries / 32 MB): tests force many small chunks through it */
 int gdx_debug_set_host_chunking(uint64_t queries, uint64_t bytes);
 
+/* tile and grid of gdx_mate_rescue_many[_dev] (gdx_experimental.h): pairs per workgroup tile (rounded up to a multiple of 256) and
+ * workgroups per launch (at most 1024) of the calls to come, 0 = the launcher's defaults.  The results do not depend on either;
+ * tests run one batch through several shapes, experiments time them.  Process-wide, not meant to change under running calls. */
+int gdx_debug_set_rescue_tiling(uint64_t tile_pairs, uint64_t grid);
+
 /* streaming copy of `bytes` (multiple of 16): the "measured HBM bandwidth" denominator */
 int gdx_bench_stream_copy(void *d_dst, const void *d_src, uint64_t bytes, void *stream);
 /* streaming read of `bytes` (multiple of 16) */

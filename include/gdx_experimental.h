@@ -3,9 +3,9 @@
  * replaced, hint arrays, compact-result plumbing of the multi-GPU gather) and building blocks the tests and bench.py still
  * drive one by one.  Exported and tested like the core (tests/test_abi.py, tests/test_gpu_*.py), but not what a binding of the
  * reference's API needs (INTEGRATION.md binds gdx.h only), and free to change.  Every call returns the results of the core call
- * it is a part of: lib.rs:155-246 of the reference.  The last three sections, "seed-hit candidates", "best hit per read" and
- * "paired-end pairing", are calls of the seed-and-verify chain that the reference has no counterpart of; they are declared here
- * because the core header keeps to its budget of names (tests/test_abi.py). */
+ * it is a part of: lib.rs:155-246 of the reference.  The last four sections, "seed-hit candidates", "best hit per read",
+ * "paired-end pairing" and "mate rescue", are calls of the seed-and-verify chain that the reference has no counterpart of; they
+ * are declared here because the core header keeps to its budget of names (tests/test_abi.py). */
 #ifndef GDX_EXPERIMENTAL_H
 #define GDX_EXPERIMENTAL_H
 
@@ -337,8 +337,8 @@ int gdx_best_hits_many(const gdx_index_t *ix, uint64_t n_groups, uint32_t group_
  * max_insert or max_insert > 2^31 - 1; 2 * n_pairs * mate_slots does not fit 64 bits; a null required pointer (only d_end / end
  * may be null).  GDX_ERR_UNSUPPORTED: a handle of the 64-bit engine.  n_pairs == 0 is GDX_OK and writes nothing.  A refused call
  * writes nothing.  gdx_parts_t and gdx_multi_t have no such call.
- * Out of scope: mate rescue (aligning the missing mate in the window the found one implies), other library orientations, an
- * insert-size model beyond the two bounds, preferring among equal scores by span. */
+ * Out of scope: other library orientations, an insert-size model beyond the two bounds, preferring among equal scores by span.
+ * Mate rescue (aligning the missing mate in the window the found one implies) is gdx_mate_rescue_many below. */
 #define GDX_PAIR_NONE           0xFFFFFFFFu  /* mate_slot of a mate without a live slot        */
 #define GDX_PAIR_MAPQ_NONE      255u         /* mapq of a pair without a proper combination    */
 #define GDX_PAIR_MAX_MATE_SLOTS 32u          /* the most slots of one mate                     */
@@ -355,6 +355,77 @@ int gdx_pair_hits_many(const gdx_index_t *ix, uint64_t n_pairs, uint32_t mate_sl
                        uint32_t *out_pair_dist, uint32_t *out_sub_dist, uint32_t *out_mapq, uint32_t *out_pair_span,
                        uint32_t *out_mate_slot, uint32_t *out_mate_dist, uint32_t *out_win_query, uint32_t *out_win_begin,
                        gdx_hit_t *out_win_hits);
+
+/* ---- mate rescue (the step behind gdx_pair_hits_many for pairs without a proper combination) ------------------------------
+ * gdx_pair_hits_many can only combine slots the seed stage produced for both mates: a pair one of whose mates got no usable seed
+ * has no proper combination.  gdx_mate_rescue_many takes the placed mate of such a pair as an ANCHOR and searches the other mate,
+ * on the opposite strand, in the window of the anchor's text that the insert bounds imply, and merges what it finds into the
+ * winners that go to the traceback.
+ * Inputs: the query batch exactly as gdx_edit_distance_many_dev takes it (d_qbuf, d_qoff, nq, layout; all four layouts), being
+ * the one gdx_strands_expand_dev with GDX_STRANDS_BOTH makes of interleaved mates: queries 4p .. 4p + 3 are mate 0 forward, mate 0
+ * reverse complement, mate 1 forward, mate 1 reverse complement of pair p, so nq == 4 * n_pairs.  n_pairs and mate_slots as in
+ * gdx_pair_hits_many.  end: u32[2 * n_pairs * mate_slots], the out_end of the edit-distance call over the slots; required here,
+ * because the reverse anchor's right end comes from it.  Six outputs of gdx_pair_hits_many[_dev], unchanged: n_proper (u32[n_pairs]),
+ * mate_slot, mate_dist, win_query, win_begin (u32[2 n_pairs]) and win_hits (2 n_pairs hits).
+ * Knobs: max_edits = k <= 256; min_insert <= max_insert <= 2^31 - 1 with max_insert - min_insert <= GDX_RESCUE_MAX_SPREAD, which
+ * bounds every search at GDX_RESCUE_MAX_SPREAD + 256 + 256 columns of the text.
+ * Attempts.  For pair p and a mate o (0 or 1) to be rescued, a = 1 - o is the anchor.  Attempt (p, o) exists when n_proper[p] == 0
+ * and mate_slot[2p + a] != GDX_PAIR_NONE; whether mate o has a single-end hit of its own does not matter.  A pair has 0, 1 or 2
+ * attempts.  Of the anchor: strand_a = win_query[2p + a] & 1; T = win_hits[2p + a].text_id; diag_a = (int64) position - (int64)
+ * win_begin[2p + a]; right_a = end[(2p + a) * mate_slots + mate_slot[2p + a]].  The searched query is rq = 4p + 2o + (1 - strand_a),
+ * the opposite strand of the other mate, and L its length: the batch holds it, no reverse complement is made here.
+ * Admissible ends, in signed 64-bit arithmetic.  strand_a == 0: the rescued mate is the reverse one and y is its right end; ylo =
+ * diag_a + min_insert, yhi = diag_a + max_insert.  strand_a == 1: the rescued mate is the forward one and its diagonal is defined
+ * as y - L; ylo = right_a - max_insert + L, yhi = right_a - min_insert + L.  Either way the rescued pair is proper by the rule of
+ * gdx_pair_hits_many step 3 by construction, with span = y - diag_a, respectively right_a - (y - L).
+ * Window and distance.  x0 = clamp(ylo - L - k, 0, |T|), x1 = clamp(yhi, 0, |T|); nothing is lost on the left, since an alignment
+ * with at most k edits that ends at y >= ylo begins at or after ylo - L - k.  The table D over the read's rows and the columns
+ * x0 .. x1, the MATCH rule (equal dense codes in 1..4) and the clipping to the text's own bounds are those of gdx_align_many:
+ * D[0][y] = 0, D[i][x0] = i.  dist = the minimum of D[L][y] over max(ylo, x0) <= y <= min(yhi, x1), end = the smallest such y;
+ * dist = k + 1 when that range is empty.
+ * Outputs per mate, at index 2p + o of arrays of 2 * n_pairs entries.  For an attempt: resc_dist = min(dist, k + 1); resc_end = end
+ * when dist <= k, otherwise GDX_EDIT_NO_END; resc_dist = GDX_EDIT_TOO_LONG when L > 256 and GDX_EDIT_INVALID when the anchor's
+ * text_id is not one of the index's texts or its mate_slot is not below mate_slots (both with resc_end = GDX_EDIT_NO_END).  Where
+ * no attempt exists: resc_dist = GDX_RESCUE_NOT_TRIED, resc_end = GDX_EDIT_NO_END.
+ * Merge, per pair.  An attempt succeeds when resc_dist <= k; its score is mate_dist[2p + a] + resc_dist.  The pair takes the
+ * successful attempt with the least (score, o): resc_mate[p] = that o (GDX_RESCUE_NONE without one), resc_pair_dist[p] = its score
+ * (2k + 2 without one), resc_span[p] = its span (0 without one).
+ * Winners: out_win_query, out_win_begin, out_win_hits, 2 * n_pairs entries each.  For a rescued pair index 2p + a copies the
+ * anchor's input winner and index 2p + o is the rescue candidate: out_win_query = rq, out_win_begin = max(0, L - end), out_win_hits
+ * = {T, max(0, end - L)}, whose diagonal is end - L exactly.  Every other pair copies both input winners.  The three arrays go
+ * into gdx_align_many_dev with m = 2 * n_pairs in place of those of gdx_pair_hits_many.  For a rescue candidate the window of
+ * gdx_align_many, [end - L - k, end + k), contains the rescue's alignment, so the distance gdx_align_many reports is at most
+ * resc_dist.  Equality of the distance and of the end is NOT promised: that window is not the rescue window (it reaches k columns
+ * beyond end, and it is not cut at ylo and yhi).
+ * Device form: ONE launch, no synchronisation, no allocation, no copy from pageable memory; returns GDX_OK.  No output may overlap
+ * an input.  Host form: plain queries only (qbuf, qoff: the caller supplies all 4 * n_pairs); win_hits and out_win_hits are
+ * gdx_hit_t, narrowed and widened as in gdx_pair_hits_many (a text id or a position of 2^32 or more:
+ * GDX_ERR_INVALID_ARGUMENT); staged with one launch.
+ * GDX_ERR_INVALID_ARGUMENT: mate_slots == 0 or > GDX_PAIR_MAX_MATE_SLOTS; max_edits > 256; min_insert > max_insert or max_insert >
+ * 2^31 - 1; max_insert - min_insert > GDX_RESCUE_MAX_SPREAD; nq != 4 * n_pairs; nq >= 2^32 - 1 (a query number must differ from
+ * GDX_CAND_NONE); an unknown layout; a null pointer.  GDX_ERR_UNSUPPORTED: as for gdx_edit_distance_many -- an index without text
+ * units, a handle of the 64-bit engine, the packed form on an index that does not take packed queries.  n_pairs == 0 (with nq ==
+ * 0) is GDX_OK and writes nothing.  A refused call writes nothing.  gdx_parts_t and gdx_multi_t have no such call.
+ * Out of scope: a mapping quality for rescued pairs, counting runner-up ends in the window, other library orientations, reads
+ * longer than 256 symbols, rescue for pairs that already have a proper combination. */
+#define GDX_RESCUE_NONE       0xFFFFFFFFu  /* resc_mate of a pair without a successful attempt */
+#define GDX_RESCUE_NOT_TRIED  0xFFFFFFFDu  /* resc_dist of a mate without an attempt            */
+#define GDX_RESCUE_MAX_SPREAD 4096u        /* max_insert - min_insert at most                   */
+int gdx_mate_rescue_many_dev(const gdx_index_t *ix, const void *d_qbuf, const void *d_qoff, uint64_t nq,
+                             const gdx_query_layout_t *layout, uint64_t n_pairs, uint32_t mate_slots,
+                             const void *d_end /*u32[2 n_pairs mate_slots]*/, const void *d_n_proper /*u32[n_pairs]*/,
+                             const void *d_mate_slot, const void *d_mate_dist, const void *d_win_query,
+                             const void *d_win_begin /*u32[2 n_pairs] each*/, const void *d_win_hits /*gdx_hit32_t[2 n_pairs]*/,
+                             uint32_t max_edits, uint32_t min_insert, uint32_t max_insert, void *d_resc_dist,
+                             void *d_resc_end /*u32[2 n_pairs] each*/, void *d_resc_mate, void *d_resc_pair_dist,
+                             void *d_resc_span /*u32[n_pairs] each*/, void *d_out_win_query, void *d_out_win_begin /*u32[2 n_pairs]*/,
+                             void *d_out_win_hits /*gdx_hit32_t[2 n_pairs]*/, void *stream);
+int gdx_mate_rescue_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint64_t n_pairs,
+                         uint32_t mate_slots, const uint32_t *end, const uint32_t *n_proper, const uint32_t *mate_slot,
+                         const uint32_t *mate_dist, const uint32_t *win_query, const uint32_t *win_begin, const gdx_hit_t *win_hits,
+                         uint32_t max_edits, uint32_t min_insert, uint32_t max_insert, uint32_t *out_resc_dist,
+                         uint32_t *out_resc_end, uint32_t *out_resc_mate, uint32_t *out_resc_pair_dist, uint32_t *out_resc_span,
+                         uint32_t *out_win_query, uint32_t *out_win_begin, gdx_hit_t *out_win_hits);
 
 #ifdef __cplusplus
 }
