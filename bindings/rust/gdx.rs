@@ -154,6 +154,10 @@ pub const GDX_PAIR_MAX_MATE_SLOTS: u32 = 32;
 pub const GDX_RESCUE_NONE: u32 = 0xFFFF_FFFF;
 pub const GDX_RESCUE_NOT_TRIED: u32 = 0xFFFF_FFFD;
 pub const GDX_RESCUE_MAX_SPREAD: u32 = 4096;
+pub const GDX_SAM_SINGLE: u32 = 0;
+pub const GDX_SAM_PAIRED: u32 = 1;
+pub const GDX_SAM_BAD_RECORD: u8 = 1;
+pub const GDX_SAM_MAX_RUN_SUM: u32 = 1 << 24;
 
 /// gdx_query_layout_t
 #[repr(C)]
@@ -161,6 +165,41 @@ pub struct QueryLayout {
     pub struct_size: u32,
     pub packed: i32,      // 0: IO symbols, 1: 2-bit codes (A C G T of the DNA alphabets)
     pub uniform_len: u64, // 0: offsets array; L: every read has L symbols, no offsets
+}
+
+/// gdx_sam_inputs_t: the argument block of gdx_sam_records_many[_dev] (include/gdx_experimental.h "SAM records").  Unused
+/// pointers are null; `dense_to_io` is a host pointer in both forms, every other pointer a device pointer in the device form.
+#[repr(C)]
+pub struct SamInputs {
+    pub qbuf: *const c_void,
+    pub qoff: *const c_void,
+    pub nq: u64,
+    pub layout: *const QueryLayout,
+    pub n_reads: u64,
+    pub strands: u32,
+    pub mode: u32,
+    pub max_edits: u32,
+    pub reserved: u32,
+    pub win_query: *const c_void,
+    pub win_hits: *const c_void,
+    pub dist: *const c_void,
+    pub begin: *const c_void,
+    pub end: *const c_void,
+    pub n_cigar: *const c_void,
+    pub cigar: *const c_void,
+    pub mapq: *const c_void,
+    pub proper: *const c_void,
+    pub names: *const c_void,
+    pub name_off: *const c_void,
+    pub text_names: *const c_void,
+    pub text_name_off: *const c_void,
+    pub dense_to_io: *const u8,
+    pub workspace: *mut c_void,
+    pub workspace_bytes: u64,
+    pub rec_off: *mut c_void,
+    pub out: *mut c_void,
+    pub out_capacity: u64,
+    pub status: *mut c_void,
 }
 
 extern "C" {
@@ -384,6 +423,12 @@ extern "C" {
         out_resc_mate: *mut u32, out_resc_pair_dist: *mut u32, out_resc_span: *mut u32, out_win_query: *mut u32,
         out_win_begin: *mut u32, out_win_hits: *mut Hit,
     ) -> c_int;
+    /// SAM records (include/gdx_experimental.h "SAM records"): one record per read from the winners and the outputs of
+    /// gdx_align_many for them, written into `out` at the offsets `rec_off`; `out` null is the sizing call
+    pub fn gdx_sam_workspace_bytes(n_reads: u64) -> u64;
+    pub fn gdx_sam_record_bound(max_read_len: u64, max_name_len: u64, max_text_name_len: u64, max_edits: u32) -> u64;
+    pub fn gdx_sam_records_many_dev(ix: *const gdx_index_t, input: *const SamInputs, stream: *mut c_void) -> c_int;
+    pub fn gdx_sam_records_many(ix: *const gdx_index_t, input: *const SamInputs) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
     ) -> c_int;

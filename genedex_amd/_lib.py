@@ -51,6 +51,10 @@ GDX_PAIR_MAX_MATE_SLOTS = 32      # mate_slots at most
 GDX_RESCUE_NONE = 0xFFFFFFFF      # gdx_mate_rescue_many[_dev]: resc_mate of a pair without a successful attempt
 GDX_RESCUE_NOT_TRIED = 0xFFFFFFFD  # resc_dist of a mate without an attempt
 GDX_RESCUE_MAX_SPREAD = 4096      # max_insert - min_insert at most
+GDX_SAM_SINGLE = 0                # gdx_sam_records_many[_dev]: mode
+GDX_SAM_PAIRED = 1
+GDX_SAM_BAD_RECORD = 1            # status of a read whose winner cannot be a record (written as unmapped)
+GDX_SAM_MAX_RUN_SUM = 1 << 24     # the run lengths of one CIGAR sum to at most this
 GDX_Q_OK = 0
 GDX_Q_INVALID_SYMBOL = 1
 GDX_Q_UNSEARCHABLE_IN_LOOKUP = 2
@@ -96,6 +100,18 @@ class QueryOptions(C.Structure):
 class QueryLayout(C.Structure):
     """gdx_query_layout_t"""
     _fields_ = [("struct_size", C.c_uint32), ("packed", C.c_int32), ("uniform_len", C.c_uint64)]
+
+
+class SamInputs(C.Structure):
+    """gdx_sam_inputs_t: the argument block of gdx_sam_records_many[_dev]"""
+    _fields_ = [("qbuf", C.c_void_p), ("qoff", C.c_void_p), ("nq", C.c_uint64), ("layout", C.POINTER(QueryLayout)),
+                ("n_reads", C.c_uint64), ("strands", C.c_uint32), ("mode", C.c_uint32), ("max_edits", C.c_uint32),
+                ("reserved", C.c_uint32), ("win_query", C.c_void_p), ("win_hits", C.c_void_p), ("dist", C.c_void_p),
+                ("begin", C.c_void_p), ("end", C.c_void_p), ("n_cigar", C.c_void_p), ("cigar", C.c_void_p), ("mapq", C.c_void_p),
+                ("proper", C.c_void_p), ("names", C.c_void_p), ("name_off", C.c_void_p), ("text_names", C.c_void_p),
+                ("text_name_off", C.c_void_p), ("dense_to_io", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_uint64), ("rec_off", C.c_void_p), ("out", C.c_void_p), ("out_capacity", C.c_uint64),
+                ("status", C.c_void_p)]
 
 
 class DeviceShard(C.Structure):
@@ -175,6 +191,7 @@ SIGNATURES = {
     "gdx_multi_free": [vp],
     "gdx_debug_force_wide": [C.c_int],
     "gdx_debug_set_rescue_tiling": [C.c_uint64, C.c_uint64],
+    "gdx_debug_set_sam_tiling": [C.c_uint32, C.c_uint32],
     "gdx_parts_build": [vp, C.c_int, u64p, C.c_uint64, u8p, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_uint64,
                         C.POINTER(BuildOptions), C.POINTER(vp)],
     "gdx_parts_free": [vp],
@@ -275,6 +292,10 @@ SIGNATURES = {
                                  C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "gdx_mate_rescue_many": [vp, u8p, u64p, C.c_uint64, C.c_uint64, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p, C.POINTER(HitStruct),
                              C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.POINTER(HitStruct)],
+    "gdx_sam_workspace_bytes": [C.c_uint64],
+    "gdx_sam_record_bound": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32],
+    "gdx_sam_records_many_dev": [vp, C.POINTER(SamInputs), vp],
+    "gdx_sam_records_many": [vp, C.POINTER(SamInputs)],
     # gdx_bench.h
     "gdx_index_build_stats": [vp, C.POINTER(BuildStats)],
     "gdx_synth_text_dev": [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp],
@@ -299,7 +320,7 @@ _RESTYPES = {"gdx_locate_many_totals_workspace_bytes": C.c_uint64, "gdx_wire_bit
              "gdx_wire_pack_workspace_bytes": C.c_uint64, "gdx_last_error": C.c_char_p, "gdx_index_free": None, "gdx_fastx_close": None,
              "gdx_build_options_init": None, "gdx_query_layout_init": None, "gdx_query_options_init": None, "gdx_free_hits": None, "gdx_free_hits32": None, "gdx_release_cached_hits": None, "gdx_multi_free": None, "gdx_parts_free": None,
              "gdx_locate_workspace_bytes": C.c_uint64, "gdx_packed_bytes": C.c_uint64, "gdx_strands_out_bytes": C.c_uint64,
-             "gdx_dna_complement_table": None}
+             "gdx_dna_complement_table": None, "gdx_sam_workspace_bytes": C.c_uint64, "gdx_sam_record_bound": C.c_uint64}
 
 _lib = None
 

@@ -1887,6 +1887,33 @@ int gdx_mate_rescue_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint6
     });
 }
 
+// ---- SAM records (sam_records.hip) ------------------------------------------------------------------------------
+
+uint64_t gdx_sam_workspace_bytes(uint64_t n_reads) { return gdx::sam_workspace_bytes(n_reads); }
+
+uint64_t gdx_sam_record_bound(uint64_t max_read_len, uint64_t max_name_len, uint64_t max_text_name_len, uint32_t max_edits)
+{
+    return gdx::sam_record_bound(max_read_len, max_name_len, max_text_name_len, max_edits);
+}
+
+int gdx_sam_records_many_dev(const gdx_index_t *ix, const gdx_sam_inputs_t *in, void *stream)
+{
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        if (!in) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "the argument block is null");
+        const gdx::SearchCall c = query_side(in->qbuf, in->qoff, in->nq, in->layout);
+        gdx::sam_records_dev(d.f, in, c.packed, c.uniform_len, d.st, [&] { d.enter(); });
+    });
+}
+
+int gdx_sam_records_many(const gdx_index_t *ix, const gdx_sam_inputs_t *in)
+{
+    return guarded([&] {
+        const gdx::FmIndex &f = deref(ix);
+        if (!in) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "the argument block is null");
+        return gdx::sam_records_host(f, in);
+    });
+}
+
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {
@@ -1993,6 +2020,12 @@ int gdx_debug_force_wide(int on)
 int gdx_debug_set_rescue_tiling(uint64_t tile_pairs, uint64_t grid)
 {
     gdx::set_rescue_tiling(tile_pairs, grid);
+    return GDX_OK;
+}
+
+int gdx_debug_set_sam_tiling(uint32_t tile_bytes, uint32_t grid)
+{
+    gdx::set_sam_tiling(tile_bytes, grid);
     return GDX_OK;
 }
 

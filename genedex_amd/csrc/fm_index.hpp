@@ -18,6 +18,8 @@
 #include "kernels.hpp"
 #include "layout.hpp"
 
+struct gdx_sam_inputs_t;  // (include/gdx_experimental.h)
+
 namespace gdx {
 
 // Build-time choices of this implementation that the reference has no counterpart for (gdx_build_options_t).
@@ -250,6 +252,13 @@ private:
     DeviceBuffer<uint2> lookup_;
     IndexView view_{};
 };
+
+// ---- sam_records.hip: the two forms of gdx_sam_records_many (the checks of the header, then the launches) ---------------
+// device form: packed / uniform_len from the parsed layout; enter() makes the index's device current before the first launch
+void sam_records_dev(const FmIndex &f, const gdx_sam_inputs_t *in, bool packed, uint32_t uniform_len, hipStream_t stream,
+                     const std::function<void()> &enter);
+// host form: staged like align_many -- copy in, a sizing pass, the records that fit, copy out
+int sam_records_host(const FmIndex &f, const gdx_sam_inputs_t *in);
 
 // ---- multi.hip: replicas on several devices behind one handle (gdx_multi_*) ---------------------------------
 // One long-lived worker thread per replica: the host-pointer pipeline keeps its pinned staging and device buffers in

@@ -255,6 +255,36 @@ void launch_mate_rescue(const IndexView &ix, const uint8_t *d_qbuf, const uint64
 // launches to come, 0 = the launcher's own choice; the results do not depend on either
 void set_rescue_tiling(uint64_t tile_pairs, uint64_t grid);
 
+// ---- sam_records.hip ----------------------------------------------------------------------
+// gdx_sam_records_many_dev: one SAM record per read from the winners, launch_align's outputs for them and the text units.  The
+// caller has checked what the header lists; every pointer but dense_to_io (host, 16 bytes) is a device pointer, optional ones
+// may be null.  Lengths, scan, offsets and -- with out != null and out_capacity != 0 -- the fill: four launches at the most.
+struct SamCall {
+    const uint8_t *d_qbuf = nullptr;
+    const uint64_t *d_qoff = nullptr;  // unused when uniform_len != 0
+    uint32_t uniform_len = 0;
+    uint64_t n_reads = 0;
+    uint32_t strands = 1, max_edits = 0;
+    bool paired = false;
+    const uint32_t *win_query = nullptr;
+    const gdx_hit32_t *win_hits = nullptr;
+    const uint32_t *dist = nullptr, *begin = nullptr, *end = nullptr, *n_cigar = nullptr, *cigar = nullptr, *mapq = nullptr;
+    const uint32_t *proper = nullptr;
+    const uint8_t *names = nullptr, *text_names = nullptr;
+    const uint64_t *name_off = nullptr, *text_name_off = nullptr;
+    const uint8_t *dense_to_io = nullptr;
+    void *d_workspace = nullptr;  // sam_workspace_bytes(n_reads), 8-byte aligned
+    uint64_t *rec_off = nullptr;
+    uint8_t *out = nullptr;
+    uint64_t out_capacity = 0;
+    uint8_t *status = nullptr;
+};
+uint64_t sam_workspace_bytes(uint64_t n_reads);
+uint64_t sam_record_bound(uint64_t max_read_len, uint64_t max_name_len, uint64_t max_text_name_len, uint32_t max_edits);
+void launch_sam_records(const IndexView &ix, const SamCall &call, hipStream_t stream);
+// tests and experiments (gdx_debug_set_sam_tiling): tile bytes and workgroups of the fills to come, 0 = the launcher's choice
+void set_sam_tiling(uint32_t tile_bytes, uint32_t grid);
+
 // ---- locate.hip ---------------------------------------------------------------------------
 size_t hit_offsets_temp_bytes(uint64_t m);
 void launch_hit_offsets(const uint32_t *d_start, const uint32_t *d_end, uint64_t m, uint64_t *d_hit_offsets,

@@ -678,6 +678,107 @@ class DeviceEngine:
             _ptr(out["win_begin"]), _ptr(out["win_hits"]), _stream()))
         return out
 
+    # ---- SAM records (gdx_sam_records_many_dev) --------------------------------------------------------------------
+    def sam_workspace_bytes(self, n_reads: int) -> int:
+        return int(self.lib.gdx_sam_workspace_bytes(int(n_reads)))
+
+    def sam_record_bound(self, max_read_len: int, max_name_len: int, max_text_name_len: int, max_edits: int) -> int:
+        """an upper bound of one record's bytes (gdx_sam_record_bound): sizes `out` without a look at the device"""
+        return int(self.lib.gdx_sam_record_bound(int(max_read_len), int(max_name_len), int(max_text_name_len), int(max_edits)))
+
+    def sam_records_dev(self, q: DeviceQueries, n_reads: int, strands: int, mode: int, max_edits: int, win_query, win_hits, dist,
+                        begin, end, n_cigar, cigar, mapq, rec_off: torch.Tensor, out: torch.Tensor = None, *, proper=None,
+                        names=None, name_off=None, text_names=None, text_name_off=None, dense_to_io: bytes = None,
+                        status: torch.Tensor = None, workspace: torch.Tensor = None, out_capacity: int = None):
+        """gdx_sam_records_many_dev as it is: lengths, scan, offsets and -- with `out` -- the fill, on the current stream, without a
+        synchronisation.  rec_off: int64[n_reads + 1]; out: uint8 or None (the sizing call); out_capacity: out.numel() unless
+        given.  workspace: at least sam_workspace_bytes(n_reads) bytes, made here when None."""
+        n_reads = int(n_reads)
+        if workspace is None:
+            workspace = torch.empty(self.sam_workspace_bytes(n_reads), dtype=torch.uint8, device=self.dev)
+        lay, qoff = q.layout()
+        a = _lib.SamInputs()
+        opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        a.qbuf, a.qoff, a.nq, a.layout = q.qbuf.data_ptr(), qoff.value, q.nq, (C.pointer(lay) if lay is not None else None)
+        a.n_reads, a.strands, a.mode, a.max_edits = n_reads, int(strands), int(mode), int(max_edits)
+        a.win_query, a.win_hits, a.dist, a.begin, a.end = opt(win_query), opt(win_hits), opt(dist), opt(begin), opt(end)
+        a.n_cigar, a.cigar, a.mapq, a.proper = opt(n_cigar), opt(cigar), opt(mapq), opt(proper)
+        a.names, a.name_off, a.text_names, a.text_name_off = opt(names), opt(name_off), opt(text_names), opt(text_name_off)
+        table = (C.c_uint8 * 16).from_buffer_copy(bytes(dense_to_io)) if dense_to_io is not None else None
+        a.dense_to_io = C.addressof(table) if table is not None else None
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+        a.rec_off, a.out, a.status = opt(rec_off), opt(out), opt(status)
+        a.out_capacity = int(out_capacity) if out_capacity is not None else (out.numel() if out is not None else 0)
+        _lib.check(self.lib.gdx_sam_records_many_dev(self.h, C.byref(a), _stream()))
+
+    def _name_table(self, names, n: int, what: str):
+        """names: a sequence of n str / bytes -> (uint8 tensor, int64 offsets tensor) on the device"""
+        names = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+        if len(names) != n:
+            raise ValueError(f"{what}: {len(names)} names for {n}")
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in names], out=off[1:])
+        buf = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)  # (never empty)
+        return torch.from_numpy(buf.copy()).to(self.dev), torch.from_numpy(off).to(self.dev)
+
+    def sam_inputs(self, q_strands: DeviceQueries, result: dict, *, mode: str, names=None, text_names=None, dense_to_io: bytes = None):
+        """what sam_records() hands to sam_records_dev() for a result of map_reads / map_pairs: (args up to rec_off, keyword
+        arguments, n_reads) -- sam_records_dev(*args, out, out_capacity=..., **kw).  Tools that time the call use it as it is."""
+        if mode not in ("single", "paired"):
+            raise ValueError("mode is 'single' or 'paired'")
+        n = int(result["begin"].numel())
+        strands = q_strands.nq // n if n else 1
+        if strands not in (1, 2) or strands * n != q_strands.nq:
+            raise ValueError("q_strands holds one or two queries per read of the result")
+        cigar = result["cigar"]
+        max_edits = (int(cigar.shape[1]) - 1) // 2
+        reads = torch.arange(max(n, 1), dtype=torch.int64, device=self.dev)[:n]
+        has = result["end"][:n] != -1
+        win_query = torch.where(has, reads * strands + (result["strand"][:n].to(torch.int64) & (strands - 1)),
+                                torch.full_like(reads, 0xFFFFFFFF)).to(torch.int32)  # (wraps to the u32 pattern)
+        win_hits = torch.stack([result["text_id"][:n], torch.zeros_like(result["text_id"][:n])], dim=1).contiguous()
+        mapq, proper = result["mapq"][:n], None
+        if mode == "paired":
+            proper = result["n_proper"] != 0
+            if "resc_mate" in result:
+                proper = proper | (result["resc_mate"] != -1)
+            proper = proper.to(torch.int32).contiguous()
+            pm = result["pair_mapq"].repeat_interleave(2)
+            mapq = torch.where(proper.repeat_interleave(2) != 0, pm, mapq)
+        d_names = self._name_table(names, n, "names") if names is not None else (None, None)
+        d_tnames = self._name_table(text_names, self.index.num_texts(), "text_names") if text_names is not None else (None, None)
+        rec_off = torch.empty(n + 1, dtype=torch.int64, device=self.dev)
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=self.dev)
+        workspace = torch.empty(self.sam_workspace_bytes(n), dtype=torch.uint8, device=self.dev)
+        args = (q_strands, n, strands, _lib.GDX_SAM_PAIRED if mode == "paired" else _lib.GDX_SAM_SINGLE, max_edits, win_query.contiguous(),
+                win_hits, result["dist"][:n].contiguous(), result["begin"][:n].contiguous(), result["end"][:n].contiguous(),
+                result["n_cigar"][:n].contiguous(), cigar.contiguous(), mapq.contiguous(), rec_off)
+        kw = dict(proper=proper, names=d_names[0], name_off=d_names[1], text_names=d_tnames[0], text_name_off=d_tnames[1],
+                  dense_to_io=dense_to_io, status=status, workspace=workspace)
+        return args, kw, n
+
+    def sam_records(self, q_strands: DeviceQueries, result: dict, *, mode: str, names=None, text_names=None, sizing="exact",
+                    dense_to_io: bytes = None):
+        """The SAM records of a batch that map_reads() / map_pairs() has mapped, made on the device.  q_strands: the batch the
+        alignment ran over -- q.with_strands(index, "both") of the mapped batch, or the batch itself when it was mapped with
+        both_strands=False; result: the dict of map_reads (mode "single") or map_pairs (mode "paired"), as it is.  The winners'
+        query numbers are rebuilt on the device from "strand" and the read number (a read with end -1 has none); a mate of a
+        proper pair ("n_proper" != 0, or rescued) gets the pair's "pair_mapq", every other read its own "mapq".
+        names / text_names: one str or bytes per read / per text, or None for numbers.  sizing: "exact" runs the sizing call and
+        reads the total once (one synchronisation); a number is the capacity of `out` in bytes, taken as it is (no
+        synchronisation; records that do not fit whole are left out -- sam_record_bound() gives a safe size).
+        -> (out: uint8 tensor, rec_off: int64[n_reads + 1], status: uint8[n_reads]); record r is out[rec_off[r] : rec_off[r + 1]]."""
+        args, kw, n = self.sam_inputs(q_strands, result, mode=mode, names=names, text_names=text_names, dense_to_io=dense_to_io)
+        rec_off, status = args[-1], kw["status"]
+        if sizing == "exact":
+            self.sam_records_dev(*args, None, **kw)
+            capacity = int(rec_off[n].item())
+        else:
+            capacity = int(sizing)
+        out = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.dev)
+        self.sam_records_dev(*args, out, out_capacity=capacity, **kw)
+        return out[:capacity], rec_off, status[:n]
+
     def map_pairs(self, q: DeviceQueries, reversed_index, *, max_smems: int, min_length: int, max_occ: int, band: int,
                   max_candidates: int, max_edits: int, min_insert: int, max_insert: int, rescue: bool = False) -> dict:
         """map_reads for paired reads.  q: a plain batch with the mates interleaved, reads 2p and 2p + 1 being the mates of pair p

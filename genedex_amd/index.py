@@ -829,6 +829,50 @@ class FmIndex:
                 else Alignment(int(d), int(b), int(e), cigar_string(row[:n]))
                 for d, b, e, n, row in zip(dist, begin, end, n_cigar, cigar)]
 
+    # ---- SAM records (gdx_experimental.h "SAM records") ----------------------------------------------------
+    def sam_records_raw(self, qbuf, qoff, win_query, win_text_ids, dist, begin, end, n_cigar, cigar, mapq, *, strands=1,
+                        mode=_lib.GDX_SAM_SINGLE, max_edits, proper=None, names=None, name_off=None, text_names=None,
+                        text_name_off=None, dense_to_io=None, out_capacity=None, want_status=True):
+        """gdx_sam_records_many -> (out: uint8 array of the records that fit, rec_off: uint64[n_reads + 1], status: uint8[n_reads]).
+        One SAM record per read from the winners (win_query, GDX_CAND_NONE = none; win_text_ids) and what align_raw returned for
+        them; cigar has 2 max_edits + 1 words a read.  out_capacity None: a sizing call first, then everything; a number: the
+        records that fit whole below it; 0 with `out` empty is the sizing call alone.  names / text_names: bytes with their
+        uint64 offsets, or None for numbers.  dense_to_io: 16 bytes, the byte printed in MD for a text symbol of that dense code
+        (0: a symbol outside 1..4), or None for the alphabet's own."""
+        n = int(np.asarray(win_query).size)
+        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8)
+        qoff = np.ascontiguousarray(qoff, dtype=np.uint64)
+        u32 = lambda x: np.ascontiguousarray(np.asarray(x).astype(np.uint32))  # noqa: E731
+        per_read = [self._sized(u32(x), n, "a per-read input") for x in (win_query, dist, begin, end, n_cigar, mapq)]
+        hits = np.ascontiguousarray(np.stack([np.asarray(win_text_ids).astype(np.uint64), np.zeros(n, dtype=np.uint64)], axis=1))
+        cigar = u32(cigar)
+        keep = [qbuf, qoff, hits, cigar] + per_read
+        a = _lib.SamInputs()
+        a.qbuf, a.qoff, a.nq, a.layout = qbuf.ctypes.data, qoff.ctypes.data, max(qoff.size - 1, 0), None
+        a.n_reads, a.strands, a.mode, a.max_edits = n, int(strands), int(mode), int(max_edits)
+        a.win_query, a.dist, a.begin, a.end, a.n_cigar, a.mapq = (x.ctypes.data for x in per_read)
+        a.win_hits, a.cigar = hits.ctypes.data, cigar.ctypes.data
+        for field, x, dtype in (("proper", proper, np.uint32), ("names", names, np.uint8), ("name_off", name_off, np.uint64),
+                                ("text_names", text_names, np.uint8), ("text_name_off", text_name_off, np.uint64),
+                                ("dense_to_io", dense_to_io, np.uint8)):
+            if x is not None:
+                x = np.ascontiguousarray(np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else x, dtype=dtype)
+                x = np.concatenate([x, np.zeros(1, dtype=dtype)]) if x.size == 0 else x  # (an empty array still has an address)
+                keep.append(x)
+                setattr(a, field, x.ctypes.data)
+        rec_off = np.full(n + 1, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+        status = np.full(max(n, 1), 0xA5, dtype=np.uint8)
+        a.rec_off, a.status = rec_off.ctypes.data, (status.ctypes.data if want_status else None)
+        if out_capacity is None:
+            a.out, a.out_capacity = None, 0
+            _lib.check(self._lib.gdx_sam_records_many(self._h, C.byref(a)))
+            out_capacity = int(rec_off[n])
+        out = np.full(max(int(out_capacity), 1), 0xA5, dtype=np.uint8)
+        a.out, a.out_capacity = (out.ctypes.data if out_capacity else None), int(out_capacity)
+        _lib.check(self._lib.gdx_sam_records_many(self._h, C.byref(a)))
+        del keep
+        return out[:int(out_capacity)], rec_off, status[:n]
+
     def cursor_empty(self) -> "Cursor":
         s = C.c_uint64(0)
         e = C.c_uint64(0)

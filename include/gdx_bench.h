@@ -55,6 +55,11 @@ int gdx_debug_set_host_chunking(uint64_t queries, uint64_t bytes);
  * tests run one batch through several shapes, experiments time them.  Process-wide, not meant to change under running calls. */
 int gdx_debug_set_rescue_tiling(uint64_t tile_pairs, uint64_t grid);
 
+/* tile and grid of the fill of gdx_sam_records_many[_dev] (gdx_experimental.h): bytes of `out` per workgroup tile (rounded down to a
+ * multiple of 16, 64 to 4096) and workgroups per launch (at most 8192) of the calls to come, 0 = the launcher's defaults.  The
+ * records do not depend on either: a small tile sends ordinary records down the path of a record larger than a tile. */
+int gdx_debug_set_sam_tiling(uint32_t tile_bytes, uint32_t grid);
+
 /* streaming copy of `bytes` (multiple of 16): the "measured HBM bandwidth" denominator */
 int gdx_bench_stream_copy(void *d_dst, const void *d_src, uint64_t bytes, void *stream);
 /* streaming read of `bytes` (multiple of 16) */

@@ -427,6 +427,93 @@ int gdx_mate_rescue_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint6
                          uint32_t *out_resc_end, uint32_t *out_resc_mate, uint32_t *out_resc_pair_dist, uint32_t *out_resc_span,
                          uint32_t *out_win_query, uint32_t *out_win_begin, gdx_hit_t *out_win_hits);
 
+/* ---- SAM records (the text output behind gdx_align_many: one record per read, made on the device) -------------------------
+ * The chain ends in per-read tensors; a distance and an end do not make a SAM record.  gdx_sam_records_many writes the records of
+ * n_reads reads, record r being read r, into one byte buffer, from the winners, the outputs of gdx_align_many for them, and the
+ * index's text units (for MD).  All arrays travel in one argument block, gdx_sam_inputs_t; set unused pointers to NULL.
+ * Inputs.  The batch: qbuf, qoff, nq, layout -- plain forms only (offsets or uniform); strands is 1 or 2 and nq == n_reads *
+ * strands; with 2, query 2r is read r as given and 2r + 1 its reverse complement (gdx_strands_expand_dev, GDX_STRANDS_BOTH).  Per
+ * read: win_query (u32, GDX_CAND_NONE = no winner), win_hits (only text_id is used), the five outputs of gdx_align_many_dev for
+ * candidate r -- dist, begin, end, n_cigar, cigar with stride 2 * max_edits + 1 -- and mapq (u32).  mode: GDX_SAM_SINGLE or
+ * GDX_SAM_PAIRED; paired needs an even n_reads, reads 2p and 2p + 1 are the mates of pair p, and proper (u32[n_reads / 2], may be
+ * NULL = all 0) says which pairs are proper.  names + name_off (u64[n_reads + 1]): one QNAME per read, or NULL.  text_names +
+ * text_name_off (u64[num_texts + 1]): RNAME per text, or NULL.  dense_to_io: u8[16], a HOST pointer in both forms, or NULL (below).
+ * Mapped.  Read r is mapped when win_query[r] != GDX_CAND_NONE, end[r] != GDX_EDIT_NO_END, win_query[r] lies in [r * strands,
+ * (r + 1) * strands), text_id < num_texts, n_cigar <= 2 * max_edits + 1 and the run lengths of its n_cigar words sum to at most
+ * GDX_SAM_MAX_RUN_SUM.  A read with a winner that fails one of the last four is written as unmapped and its status is
+ * GDX_SAM_BAD_RECORD; every other status is 0.  strand(r) = win_query[r] - r * strands.
+ * The record: eleven tab-separated fields, for a mapped read two more, NM:i:<dist> and MD:Z:<md>, then '\n'.  Numbers are decimal
+ * without padding.  With m = r ^ 1 the mate (paired mode; in single mode the mate counts as unmapped):
+ *   QNAME  the read's name; with names NULL the decimal read number (single) or pair number (paired)
+ *   FLAG   single: 0x4 if unmapped, 0x10 if mapped on strand 1.  Paired: 0x1; 0x40 for even r, 0x80 for odd r; 0x2 if both are
+ *          mapped and proper[r / 2] != 0; 0x4 if r is unmapped; 0x8 if m is unmapped; 0x10 if r is mapped on strand 1; 0x20 if m is
+ *   RNAME  the text's name (with text_names NULL the decimal text id), or * if unmapped
+ *   POS    begin + 1, or 0          MAPQ  min(mapq, 255), or 0
+ *   CIGAR  per word the run length, then "MIDNSHP=X"[op] (? for an op above 8); * if unmapped or n_cigar == 0
+ *   RNEXT  * if m is unmapped; = if both are mapped on one text; otherwise m's text name
+ *   PNEXT  m's begin + 1, or 0
+ *   TLEN   0 unless both are mapped on one text; then span = max(end_r, end_m) - min(begin_r, begin_m), printed as span for the mate
+ *          with the smaller begin (on equal begins the even one) and as -span for the other
+ *   SEQ    the bytes of query win_query[r] if mapped, of query r * strands if not, as they are; * for an empty read
+ *   QUAL   *
+ *   MD     y = begin, n = 0; per run of length l > 0 (a run of length 0 is skipped): '=' n += l, y += l; 'X' per symbol: n, the text
+ *          symbol at y, then n = 0, y += 1; 'D' n, '^', the l text symbols from y, then n = 0, y += l; any other op nothing; at the
+ *          end n.  So 2=1D1X2= over ..AC.. gives 2^A0C2.
+ * Text symbols.  The text unit of position y of text text_id holds the dense code 1..4 of the symbol, or that it is none of them
+ * without saying which (N, IUPAC codes): such a symbol has code 0 here.  The byte printed is dense_to_io[code]; entries 5..15 are
+ * reserved.  With dense_to_io NULL: entry c >= 1 is the smallest byte the alphabet maps to c, entry 0 the smallest byte of the
+ * alphabet's dense code above 4 when there is exactly one such code (N of ascii_dna_with_n), and ? otherwise.  A y at or beyond
+ * the text's length prints ?; nothing outside the text's own units is read.  The CIGAR is not checked against text or read.
+ * Outputs.  rec_off: u64[n_reads + 1], rec_off[0] = 0, record r is bytes [rec_off[r], rec_off[r + 1]) of out.  out with
+ * out_capacity: a record is written only if it fits whole below out_capacity (rec_off[r + 1] <= out_capacity); no byte at or beyond
+ * rec_off[n_reads], and no byte of a record that does not fit, is touched.  out == NULL: the sizing call, only rec_off (and status)
+ * are written and rec_off[n_reads] is the total.  status: u8[n_reads] or NULL.
+ * gdx_sam_record_bound(max_read_len, max_name_len, max_text_name_len, max_edits): a pure host function, an upper bound of one
+ * record's bytes for a caller who must not synchronise, valid for records whose read has at most max_read_len symbols, whose
+ * CIGAR is what gdx_align_many writes for such a read within max_edits (at most 2 max_edits + 1 runs and max_edits 'X' and 'D'
+ * symbols together, no run and no match counter above max_read_len + max_edits) and whose given names are at most that long:
+ *   with d = decimal digits of (max_read_len + max_edits), k = max_edits:
+ *   max(max_name_len, 10) + 4 + 2 * max(max_text_name_len, 10) + 10 + 3 + (2k + 1)(d + 1) + 10 + 11 + max(max_read_len, 1) + 1
+ *   + (5 + 10) + (5 + (k + 1) d + 2k) + 12 tabs + 1
+ * Device form: three small launches (lengths, scan of the workgroup sums, offsets) and, with out != NULL and out_capacity != 0,
+ * the fill; no synchronisation, no allocation.  workspace / workspace_bytes: at least gdx_sam_workspace_bytes(n_reads) (a pure
+ * host function), 8-byte aligned; a smaller one returns GDX_ERR_INVALID_ARGUMENT and writes nothing.  All pointers but
+ * dense_to_io are device pointers; win_hits is gdx_hit32_t[n_reads].  rec_off: 8-byte aligned.  No output may overlap an input.
+ * Host form: host pointers, queries with offsets only (layout must be NULL: a packed one is GDX_ERR_UNSUPPORTED as in the device
+ * form, any other GDX_ERR_INVALID_ARGUMENT), win_hits is gdx_hit_t[n_reads] (a text id or position
+ * of 2^32 or more: GDX_ERR_INVALID_ARGUMENT), workspace is ignored; staged like gdx_align_many (copy in, the launches, copy out).
+ * GDX_ERR_INVALID_ARGUMENT: strands not 1 or 2; nq != n_reads * strands; nq >= 2^32 - 1; an odd n_reads in paired mode; an unknown
+ * mode or layout; max_edits > 256; a null required pointer (rec_off, and with n_reads != 0 qbuf, the nine per-read arrays and qoff
+ * unless uniform); names without their offsets or the reverse.  GDX_ERR_UNSUPPORTED: a packed layout, an index without text units,
+ * a handle of the 64-bit engine.  A refused call writes nothing.  n_reads == 0 is GDX_OK and writes rec_off[0] = 0.
+ * Out of scope: base qualities, BAM, secondary and supplementary records, soft clipping, placing an unmapped mate at its partner's
+ * position, gdx_parts_t and gdx_multi_t. */
+#define GDX_SAM_SINGLE      0u
+#define GDX_SAM_PAIRED      1u
+#define GDX_SAM_BAD_RECORD  1            /* status: a winner that cannot be a record; written as unmapped        */
+#define GDX_SAM_MAX_RUN_SUM 16777216u    /* the run lengths of one CIGAR sum to at most this (2^24)               */
+typedef struct gdx_sam_inputs_t {
+    const void *qbuf, *qoff;             /* the batch, as the verify calls take it                                */
+    uint64_t nq;
+    const gdx_query_layout_t *layout;    /* NULL = offsets                                                        */
+    uint64_t n_reads;
+    uint32_t strands, mode, max_edits, reserved;
+    const void *win_query, *win_hits, *dist, *begin, *end, *n_cigar, *cigar, *mapq;
+    const void *proper;                  /* u32[n_reads / 2] or NULL                                              */
+    const void *names, *name_off, *text_names, *text_name_off; /* or NULL                                         */
+    const uint8_t *dense_to_io;          /* HOST u8[16] or NULL                                                   */
+    void *workspace;                     /* device form only                                                      */
+    uint64_t workspace_bytes;
+    void *rec_off;                       /* u64[n_reads + 1]                                                      */
+    void *out;                           /* u8[out_capacity] or NULL (sizing)                                     */
+    uint64_t out_capacity;
+    void *status;                        /* u8[n_reads] or NULL                                                   */
+} gdx_sam_inputs_t;
+uint64_t gdx_sam_workspace_bytes(uint64_t n_reads);
+uint64_t gdx_sam_record_bound(uint64_t max_read_len, uint64_t max_name_len, uint64_t max_text_name_len, uint32_t max_edits);
+int gdx_sam_records_many_dev(const gdx_index_t *ix, const gdx_sam_inputs_t *in, void *stream);
+int gdx_sam_records_many(const gdx_index_t *ix, const gdx_sam_inputs_t *in);
+
 #ifdef __cplusplus
 }
 #endif
