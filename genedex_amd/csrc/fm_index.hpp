@@ -13,6 +13,7 @@
 #include <mutex>
 #include <vector>
 
+#include "aux_plan.hpp"
 #include "build.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
@@ -22,34 +23,12 @@ struct gdx_sam_inputs_t;  // (include/gdx_experimental.h)
 
 namespace gdx {
 
-// Build-time choices of this implementation that the reference has no counterpart for (gdx_build_options_t).
-// Negative / zero = default.  The GDX_* environment variables named in fm_index.hip only override fields left
-// at their default (debugging aid).
-struct BuildOptions {
-    // (all of jump_bytes / full_sa / text_units / seed_symbols / inverse_sa at -1 and pair lines not switched off: THE DEFAULT
-    // SHAPE -- seed table + text units + full and inverse suffix array + pair lines + top table of depth <= 14, no jump table
-    // -- when it fits the budget; FmIndex::build_aux)
-    int pair_lines = -1;            // -1 default (on for sigma <= 8), 0 off, 1 on
-    int jump_bytes = -1;            // -1 default (none in the default shape, else 32), 0 none, 8, 16, 32
-    int top_depth = -1;             // -1 default (largest even D <= 16 with 4^D <= 2n; <= 14 in the default shape), 0 none, 1..16
-    uint64_t aux_budget_bytes = 0;  // cap for jump + top table; 0 = min(free HBM - reserve, half of the HBM)
-    int full_sa = -1;               // 1: SA[row] of every row as its own array
-    int text_units = -1;            // 1: the text itself, 16 bytes per 32 symbols (layout.hpp)
-    int seed_symbols = -1;          // -1 / 0 none, 1 = seed table with k chosen from the text length, 8..24 = that k
-                                    // (implies text_units)
-    int seed_load_percent = 0;      // slots filled on average, 0 = default (70), 20..100
-    int table_layout = -1;          // -1 / 0: this implementation's own occurrence table (rank lines for sigma <= 8); 1..4: the
-                                    // reference's Condensed64 / Condensed512 / Flat64 / Flat512 layout, queried as it is
-    int inverse_sa = -1;            // 1: ISA[position] = row as its own array (4 bytes per symbol): exact intervals through the
-                                    // seed table
-};
-
 // What the aux build decided (gdx_index_aux_t)
 struct AuxReport {
     uint32_t wanted_jump_bytes = 0, wanted_top_depth = 0;  // before the budget was applied
     uint64_t budget_bytes = 0, aux_bytes = 0;
     double wide_fraction = 0.0;  // share of text positions whose top-table interval is wider than 4 rows
-    bool default_shape = false;  // the options were left at their defaults and the default shape fitted the budget (fm_index.hip)
+    bool default_shape = false;  // the options were left at their defaults and the default shape fitted the budget (aux_plan.hpp)
     // seed table: k, buckets, entries of kind 0 / kind 1, buckets that turned an entry away, largest displacement
     uint64_t seed_k = 0, seed_buckets = 0, seed_single = 0, seed_multi = 0, seed_overflowed = 0, seed_max_disp = 0, seed_bytes = 0, seed_pair_records = 0, seed_quad_records = 0;
 };
@@ -97,15 +76,15 @@ public:
     // kernel choices of the query calls on this handle (gdx_query_options_t); safe against concurrent queries
     void set_query_options(const QueryOptions &q);
     QueryOptions query_options() const;
-    // drops the pair lines / jump table / top table and builds them again with other options (bench ladder;
-    // not safe against concurrent queries)
+    // drops every auxiliary structure and builds them again with other options (bench ladder; not safe against concurrent
+    // queries)
     void rebuild_aux(const BuildOptions &opts);
     // search -> scan -> locate of a device-resident batch on this replica's device, results left in the given buffers
     // (grown as needed): counts u32[nq], status u8[nq], hits gdx_hit32_t[total]; returns the number of hits
     uint64_t locate_shard_dev(const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq, DeviceBuffer<uint32_t> &counts,
                               DeviceBuffer<uint8_t> &status, DeviceBuffer<gdx_hit32_t> &hits, hipStream_t stream) const;
 
-    // ---- host-pointer query API (each call uploads, runs, downloads, synchronises) -------------
+    // ---- host-pointer query API (each call uploads, runs, downloads, synchronises; fm_query.hip) -------------
     // packed: qbuf holds 2-bit codes and qoff counts symbols (include/gdx.h "packed queries")
     int cursors_for_many_queries(const uint8_t *qbuf, const uint64_t *qoff, uint64_t nq, uint64_t *out_start,
                                  uint64_t *out_end, uint64_t *out_count, uint8_t *out_status, bool packed = false,
@@ -217,7 +196,14 @@ private:
     // fit the fused step's 32-bit offsets; refresh: sets the call's hit array anew before that second run
     int locate_wide(HostCall call, const std::function<void(HostCall &)> &refresh = {}) const;
     void finish_from_bwt(const uint8_t *d_bwt_padded, hipStream_t stream);  // table + lookup + view
-    void build_aux(const uint8_t *d_bwt_padded, hipStream_t stream);        // pair lines, jump table, top table
+    // the auxiliary structures, as aux_plan.hpp decides: reset_aux, plan, pair lines, plan the tables, then the builders below
+    void build_aux(const uint8_t *d_bwt_padded, hipStream_t stream);
+    void reset_aux();  // the view forgets every auxiliary structure, then its buffer is released; an empty report
+    void build_pair_lines(const uint8_t *d_bwt_padded, hipStream_t stream);
+    void build_jump_table(uint32_t jump_bytes, hipStream_t stream);
+    void build_top_table(uint32_t top_depth, hipStream_t stream);  // and AuxReport::wide_fraction
+    // full suffix array, text units, seed table, inverse suffix array: those of them the shape wants
+    void build_sa_structures(const AuxShape &shape, hipStream_t stream);
     void build_seed_table(const uint32_t *d_sa, uint32_t k, uint32_t load_percent, hipStream_t stream, uint64_t room_bytes);
     void locate_device(const uint32_t *d_start, const uint32_t *d_end, uint64_t m, uint64_t *out_hit_offsets,
                        gdx_hit_t *hits, uint64_t hits_capacity, uint64_t *out_total, int *rc,

@@ -1,5 +1,5 @@
 // select.hpp -- what the two selection stages behind the verify calls (best_hits.hip, pair_hits.hip) have in common.  For the
-// host: the argument blocks, which capi.hip and fm_index.hip fill and the launch functions of kernels.hpp take.  For the kernels
+// host: the argument blocks, which capi.hip and fm_query.hip fill and the launch functions of kernels.hpp take.  For the kernels
 // (namespace select): the constants, the slot loader with the "live" rule, the same-locus rotation pass, the xor-butterfly
 // minimum, the mapq rule, the winner store with its none pattern and the instance dispatch.  A stage keeps what is its own:
 // best_hits.hip the ballot counts and the per-group stores, pair_hits.hip the combinations pass, its fused butterfly of counts and

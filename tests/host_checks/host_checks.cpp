@@ -8,6 +8,8 @@
 //                                                            exactly sized buffers; prints "ok <hits> <exceptions>"
 //   host_checks chunks <seed>                              the chunk planner and the wire layout of the host-pointer pipeline (host_plan.hpp);
 //                                                            prints "ok <cases> <chunks>"
+//   host_checks auxplan <seed>                             which auxiliary structures an index gets (aux_plan.hpp) against the arithmetic
+//                                                            it replaced; prints "ok <hand-made> <random> <raised> <default shapes> <shrunk>"
 // A malformed input must end in "error: <message>" (exit code 3), never in a sanitizer report.
 #include <cinttypes>
 #include <cstdio>
@@ -17,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "../../genedex_amd/csrc/aux_plan.hpp"
 #include "../../genedex_amd/csrc/fastx.hpp"
 #include "../../genedex_amd/csrc/host_plan.hpp"
 #include "../../genedex_amd/csrc/index_file.hpp"
@@ -349,6 +352,298 @@ int main(int argc, char **argv)
                     cases++;
                 }
             std::printf("ok %" PRIu64 " %" PRIu64 "\n", cases, n_chunks);
+        } else if (mode == "auxplan") {
+            // aux_plan.hpp: which auxiliary structures an index gets.  `expected` is the arithmetic of FmIndex::build_aux as it
+            // stood before the decision became this header -- budget, fit test, k, wants, jump / top wanted, shrink loop --
+            // with the environment as AuxEnv and the two hipMemGetInfo readings as arguments: the planner must agree field
+            // for field, and raise the same error where that raised.
+            using gdx::AuxEnv;
+            using gdx::BuildOptions;
+            uint64_t x = std::strtoull(argv[2], nullptr, 10) * 2654435761ull + 88172645463325252ull;
+            auto rnd = [&]() {
+                x ^= x << 13, x ^= x >> 7, x ^= x << 17;
+                return x;
+            };
+            constexpr uint32_t kSeedTagBitsMax = 21;  // (layout.hpp, which needs HIP)
+            struct Outcome {
+                int status = 0;  // of the error raised, 0: none
+                std::string message;
+                bool default_shape = false, want_pairs = false, want_text = false, want_sa_full = false, want_isa = false, build_any = false;
+                uint32_t seed_k = 0, seed_load_pct = 0, wanted_jump = 0, wanted_top = 0, jump = 0, top = 0;
+                uint64_t budget_bytes = 0;
+            };
+            struct Case {
+                uint64_t n = 0;
+                int sigma = 6, layout = 0, n_searchable = 4;
+                BuildOptions bo;
+                AuxEnv env;
+                uint64_t free1 = 0, free2 = 0, total = 0;  // the readings before anything is allocated and behind the pair lines
+            };
+            auto expected = [](const Case &c, Outcome &o) {
+                const uint64_t n_ = c.n;
+                const BuildOptions &bo = c.bo;
+                auto env_int = [](bool set, int value, int fallback) { return set ? value : fallback; };
+                int want_pairs = bo.pair_lines;
+                if (want_pairs < 0) want_pairs = c.env.no_pair_lines ? 0 : 1;
+                bool default_shape = bo.seed_symbols < 0 && bo.jump_bytes < 0 && bo.full_sa < 0 && bo.inverse_sa < 0 && bo.text_units < 0 &&
+                                     want_pairs != 0 && c.layout == 0 && c.sigma >= 5 && c.n_searchable >= 4 && n_ > 0;
+                if (default_shape && c.env.tables_shape) default_shape = false;
+                uint32_t seed_load_pct = bo.seed_load_percent > 0 ? static_cast<uint32_t>(bo.seed_load_percent) : 70u;
+                auto auto_seed_k = [&] {
+                    uint32_t k = 8;
+                    while (k < 24 && (1ull << (2u * (k - 8u))) < n_) k++;
+                    return k;
+                };
+                if (default_shape) {
+                    const size_t free_b = c.free1, total_b = c.total;
+                    const size_t reserve = total_b / 16 > (4ull << 30) ? total_b / 16 : (4ull << 30);
+                    double budget = free_b > reserve ? static_cast<double>(free_b - reserve) : 0.0;
+                    if (bo.aux_budget_bytes != 0) {
+                        budget = static_cast<double>(bo.aux_budget_bytes) < budget ? static_cast<double>(bo.aux_budget_bytes) : budget;
+                    } else {
+                        if (budget > static_cast<double>(total_b / 2)) budget = static_cast<double>(total_b / 2);
+                        if (c.env.budget_gb != HUGE_VAL) budget = std::min(budget, c.env.budget_gb * 1e9);  // (GDX_AUX_BUDGET_GB is set)
+                    }
+                    const uint32_t k = auto_seed_k();
+                    const uint32_t load = bo.seed_load_percent > 0 ? static_cast<uint32_t>(bo.seed_load_percent) : 60u;
+                    double seed_bytes = 16.0 / (load / 100.0) * static_cast<double>(n_);
+                    if (2u * k > kSeedTagBitsMax) seed_bytes = std::max(seed_bytes, 128.0 * static_cast<double>(1ull << (2u * k - kSeedTagBitsMax)));
+                    const double need = 1.25 * seed_bytes + 8.5 * static_cast<double>(n_);
+                    if (need > budget) default_shape = false;
+                    else seed_load_pct = load;
+                }
+                uint32_t seed_k = 0;
+                if (default_shape) {
+                    seed_k = auto_seed_k();
+                } else if (bo.seed_symbols >= 1 && c.sigma >= 5) {
+                    if (bo.seed_symbols == 1) seed_k = auto_seed_k();
+                    else seed_k = static_cast<uint32_t>(bo.seed_symbols);
+                    if (seed_k < 8u || seed_k > 24u) gdx::fail(GDX_ERR_INVALID_ARGUMENT, "seed_symbols must be 1 (automatic) or 8..24");
+                }
+                const bool want_seed = seed_k != 0;
+                const bool want_text = bo.text_units == 1 || want_seed, want_sa_full = bo.full_sa == 1 || default_shape,
+                           want_isa = bo.inverse_sa == 1 || default_shape;
+                o.default_shape = default_shape, o.want_pairs = want_pairs != 0, o.seed_k = seed_k, o.seed_load_pct = seed_load_pct;
+                o.want_text = want_text, o.want_sa_full = want_sa_full, o.want_isa = want_isa;
+                if (c.layout == 0 && n_ > 0 && (want_pairs || want_text || want_sa_full || want_isa)) {
+                    o.build_any = true;
+                    uint32_t jump_bytes = 32;
+                    if (default_shape) {
+                        jump_bytes = 0;
+                    } else if (bo.jump_bytes >= 0) {
+                        jump_bytes = static_cast<uint32_t>(bo.jump_bytes);
+                    } else {
+                        jump_bytes = static_cast<uint32_t>(c.env.jump_bytes);
+                        if (c.env.no_jump_table) jump_bytes = 0;
+                    }
+                    if (jump_bytes != 0 && jump_bytes != 8 && jump_bytes != 16 && jump_bytes != 32)
+                        gdx::fail(GDX_ERR_INVALID_ARGUMENT, "jump entry bytes must be 0, 8, 16 or 32");
+                    if (!want_pairs) jump_bytes = 0;
+                    uint32_t top_depth = 0;
+                    while (top_depth < 16 && (1ull << (2u * (top_depth + 2u))) <= 2ull * n_) top_depth += 2;
+                    if (bo.top_depth >= 0) top_depth = static_cast<uint32_t>(bo.top_depth);
+                    else top_depth = static_cast<uint32_t>(env_int(c.env.has_top_depth, c.env.top_depth, static_cast<int>(top_depth)));
+                    if (top_depth > 16u) top_depth = 16u;
+                    if (default_shape && bo.top_depth < 0 && top_depth > 14u) top_depth = 14u;
+                    if (c.sigma < 5) top_depth = 0;
+                    if (!want_pairs && !want_text) top_depth = 0;
+                    o.wanted_jump = jump_bytes;
+                    o.wanted_top = top_depth;
+                    {
+                        const size_t free_b = c.free2, total_b = c.total;
+                        const size_t reserve = total_b / 16 > (4ull << 30) ? total_b / 16 : (4ull << 30);
+                        double budget = free_b > reserve ? static_cast<double>(free_b - reserve) : 0.0;
+                        if (bo.aux_budget_bytes != 0) {
+                            budget = static_cast<double>(bo.aux_budget_bytes) < budget ? static_cast<double>(bo.aux_budget_bytes) : budget;
+                        } else {
+                            if (budget > static_cast<double>(total_b / 2)) budget = static_cast<double>(total_b / 2);
+                            if (c.env.budget_gb != HUGE_VAL) {
+                                const double b = c.env.budget_gb * 1e9;
+                                budget = b < budget ? b : budget;
+                            }
+                        }
+                        o.budget_bytes = static_cast<uint64_t>(budget);
+                        const double seed_load = seed_load_pct / 100.0;
+                        double seed_bytes = 0.0;
+                        if (want_seed) {
+                            seed_bytes = 16.0 / seed_load * static_cast<double>(n_);
+                            if (2u * seed_k > kSeedTagBitsMax) seed_bytes = std::max(seed_bytes, 128.0 * static_cast<double>(1ull << (2u * seed_k - kSeedTagBitsMax)));
+                            seed_bytes *= 1.25;
+                            if (seed_bytes > budget && bo.seed_symbols > 1)
+                                gdx::fail(GDX_ERR_INVALID_ARGUMENT,
+                                          "seed_symbols = %u needs a seed table of at least %.1f GB (2^(2k - 21) buckets of 128 bytes, or 16 bytes per "
+                                          "k-mer over the load factor), the budget for auxiliary structures is %.1f GB: choose a smaller k or "
+                                          "seed_symbols = 1", seed_k, seed_bytes / 1.25 / 1e9, budget / 1e9);
+                        }
+                        const double fixed = ((want_sa_full ? 4.0 : 0.0) + (want_isa ? 4.0 : 0.0)) * static_cast<double>(n_) + (want_text ? 0.5 : 0.0) * static_cast<double>(n_) +
+                                             seed_bytes;
+                        auto need = [&] {
+                            return fixed + static_cast<double>(jump_bytes) * static_cast<double>(n_) +
+                                   (top_depth ? 8.0 * static_cast<double>(1ull << (2u * top_depth)) : 0.0);
+                        };
+                        while (need() > budget) {
+                            if (top_depth > 14) top_depth = 14;
+                            else if (jump_bytes == 32) jump_bytes = 16;
+                            else if (top_depth > 12) top_depth = 12;
+                            else if (jump_bytes == 16) jump_bytes = 8;
+                            else if (top_depth > 0) top_depth -= top_depth >= 2 ? 2 : 1;
+                            else if (jump_bytes != 0) jump_bytes = 0;
+                            else break;
+                        }
+                    }
+                    o.jump = jump_bytes;
+                    o.top = top_depth;
+                }
+            };
+            // the planner, called as FmIndex::build_aux calls it
+            auto planned = [](const Case &c, Outcome &o) {
+                const gdx::AuxPlanInput in = {c.n, c.sigma, c.layout, c.n_searchable, kSeedTagBitsMax, c.bo, c.env};
+                const bool asked = gdx::aux_default_shape_asked(in);
+                const gdx::AuxShape s = gdx::plan_aux_shape(in, asked ? c.free1 : 0, asked ? c.total : 0);
+                o.default_shape = s.default_shape, o.want_pairs = s.want_pairs, o.seed_k = s.seed_k, o.seed_load_pct = s.seed_load_percent;
+                o.want_text = s.want_text, o.want_sa_full = s.want_sa_full, o.want_isa = s.want_isa, o.build_any = s.build_any;
+                if (!s.build_any) return;
+                const gdx::AuxTables t = gdx::plan_aux_tables(in, s, c.free2, c.total);
+                o.wanted_jump = t.wanted_jump_bytes, o.wanted_top = t.wanted_top_depth, o.jump = t.jump_bytes, o.top = t.top_depth;
+                o.budget_bytes = t.budget_bytes;
+            };
+            auto outcome = [](const auto &plan, const Case &c) {
+                Outcome o;
+                try {
+                    plan(c, o);
+                } catch (const gdx::Error &e) {
+                    o.status = e.status;
+                    o.message = e.what();
+                }
+                return o;
+            };
+            uint64_t cases = 0, raised = 0, default_shapes = 0, shrunk = 0;
+            auto check = [&](Case c) {
+                c.free2 = c.free1 > 2 * c.n ? c.free1 - 2 * c.n : 0;  // the pair lines: 2 bytes per symbol
+                const Outcome want = outcome(expected, c), got = outcome(planned, c);
+                if (got.status != want.status || got.message != want.message) return 40;
+                if (want.status != 0) {  // (a build that raised holds nothing)
+                    cases++, raised++;
+                    return 0;
+                }
+                if (got.default_shape != want.default_shape || got.want_pairs != want.want_pairs || got.seed_k != want.seed_k) return 41;
+                if (got.seed_load_pct != want.seed_load_pct) return 42;
+                if (got.want_text != want.want_text || got.want_sa_full != want.want_sa_full || got.want_isa != want.want_isa) return 43;
+                if (got.build_any != want.build_any) return 44;
+                if (got.wanted_jump != want.wanted_jump || got.wanted_top != want.wanted_top) return 45;
+                if (got.jump != want.jump || got.top != want.top) return 46;
+                if (got.budget_bytes != want.budget_bytes) return 47;
+                cases++, default_shapes += want.default_shape;
+                shrunk += want.jump != want.wanted_jump || want.top != want.wanted_top;
+                return 0;
+            };
+            const uint64_t gib = 1ull << 30, total288 = 288 * gib;
+            // the two worked examples: a 288 GiB device with 300e9 bytes free, sigma 6, 3.1 G symbols, every option at its default
+            {
+                Case c;
+                c.n = 3'100'000'000ull, c.free1 = 300'000'000'000ull, c.total = total288;
+                if (const int rc = check(c)) return rc;
+                c.free2 = c.free1 - 2 * c.n;
+                Outcome o = outcome(planned, c);
+                if (gdx::aux_budget(c.free1, c.total, 0, c.env) != 154'618'822'656.0 || o.budget_bytes != 154'618'822'656ull) return 50;
+                const double need = gdx::seed_table_estimate(c.n, 24, 60, kSeedTagBitsMax) + 8.5 * static_cast<double>(c.n);
+                if (need < 129.67e9 || need > 129.69e9) return 51;
+                if (o.status != 0 || !o.default_shape || o.seed_k != 24 || o.seed_load_pct != 60 || !o.want_text || !o.want_sa_full || !o.want_isa ||
+                    o.wanted_jump != 0 || o.jump != 0 || o.wanted_top != 14 || o.top != 14)
+                    return 52;
+                c.bo.aux_budget_bytes = 90'000'000'000ull;
+                if (const int rc = check(c)) return rc;
+                o = outcome(planned, c);
+                if (o.status != 0 || o.default_shape || o.seed_k != 0 || o.want_text || o.want_sa_full || o.want_isa || o.wanted_jump != 32 ||
+                    o.wanted_top != 16 || o.jump != 16 || o.top != 14 || o.budget_bytes != 90'000'000'000ull)
+                    return 53;
+            }
+            // build_seed_table's bucket rule through seed_min_buckets, against the two ifs it replaced
+            for (uint32_t k = 8; k <= 24; k++)
+                for (uint64_t b : {uint64_t(0), uint64_t(1), uint64_t(1) << 10, (uint64_t(1) << 27) - 1, uint64_t(1) << 27, uint64_t(1) << 31}) {
+                    uint64_t want = b;
+                    if (want < 1) want = 1;
+                    if (2u * k > kSeedTagBitsMax && want < (1ull << (2u * k - kSeedTagBitsMax))) want = 1ull << (2u * k - kSeedTagBitsMax);
+                    if (std::max<uint64_t>({b, 1, gdx::seed_min_buckets(k, kSeedTagBitsMax)}) != want) return 54;
+                }
+            // hand-made: every value of one thing at a time around a base, over every text length, alphabet and layout
+            const std::vector<uint64_t> lengths = {0, 1, 255, 65536, 65537, 20'000, 1ull << 28, 3'100'000'000ull, 3'700'000'000ull, 0xffffffffull};
+            std::vector<BuildOptions> option_sets(1);
+            auto vary = [&](int BuildOptions::*field, std::initializer_list<int> values) {
+                for (int v : values) {
+                    BuildOptions bo;
+                    bo.*field = v;
+                    option_sets.push_back(bo);
+                }
+            };
+            vary(&BuildOptions::pair_lines, {0, 1});
+            vary(&BuildOptions::jump_bytes, {0, 8, 16, 32, 7, 24, 64});
+            vary(&BuildOptions::top_depth, {0, 1, 5, 12, 13, 14, 16, 17, 400});
+            vary(&BuildOptions::full_sa, {0, 1});
+            vary(&BuildOptions::text_units, {0, 1});
+            vary(&BuildOptions::seed_symbols, {0, 1, 8, 12, 17, 24, 2, 7, 25, 1000});
+            vary(&BuildOptions::seed_load_percent, {20, 40, 100});
+            vary(&BuildOptions::inverse_sa, {0, 1});
+            vary(&BuildOptions::table_layout, {0, 1, 4});
+            {
+                BuildOptions lean;  // (the seed index of the smoke test), and a k with a load factor, without pair lines
+                lean.jump_bytes = 0, lean.top_depth = 0, lean.full_sa = 1, lean.seed_symbols = 1, lean.inverse_sa = 1;
+                option_sets.push_back(lean);
+                lean.seed_symbols = 24, lean.seed_load_percent = 40, lean.pair_lines = 0;
+                option_sets.push_back(lean);
+            }
+            std::vector<AuxEnv> envs(1);
+            envs.emplace_back().no_pair_lines = true;
+            envs.emplace_back().tables_shape = true;
+            for (double gb : {0.0003, 50.0, 120.0, 1000.0}) envs.emplace_back().budget_gb = gb;
+            for (int jb : {0, 8, 16, 7, -8}) envs.emplace_back().jump_bytes = jb;
+            envs.emplace_back().no_jump_table = true;
+            for (int td : {0, 6, 13, 16, 20, -1}) envs.emplace_back().has_top_depth = true, envs.back().top_depth = td;
+            const std::vector<uint64_t> budgets = {0, 1, 300'000, 90'000'000'000ull, 250'000'000'000ull};
+            // free - reserve below half of the device, above it before the pair lines and below it behind them (3.1 G symbols:
+            // 6.2 GB), above it; less than the reserve; and a small device, whose reserve is the 4 GB floor
+            const std::vector<std::pair<uint64_t, uint64_t>> memory = {
+                {100'000'000'000ull, total288}, {total288 / 16 + total288 / 2 + 3'000'000'000ull, total288}, {300'000'000'000ull, total288},
+                {1'000'000'000ull, total288}, {15 * gib, 16 * gib}};
+            for (uint64_t n : lengths)
+                for (int sigma : {4, 5, 6, 9})
+                    for (int layout : {0, 1})
+                        for (int n_searchable : {3, 4})
+                            for (const auto &mem : memory)
+                                for (uint64_t budget : budgets) {
+                                    Case c;
+                                    c.n = n, c.sigma = sigma, c.layout = layout, c.n_searchable = n_searchable;
+                                    c.free1 = mem.first, c.total = mem.second;
+                                    for (const BuildOptions &bo : option_sets) {
+                                        c.bo = bo, c.bo.aux_budget_bytes = budget;
+                                        if (const int rc = check(c)) return rc;
+                                    }
+                                    for (const AuxEnv &env : envs)  // each override alone: on the defaults, and where jump and top are read
+                                        for (int text_units : {-1, 0}) {
+                                            c.bo = BuildOptions(), c.bo.aux_budget_bytes = budget, c.bo.text_units = text_units, c.env = env;
+                                            if (const int rc = check(c)) return rc;
+                                        }
+                                }
+            const uint64_t made = cases;
+            // random combinations of all of it
+            auto pick = [&](std::initializer_list<int> values) { return values.begin()[rnd() % values.size()]; };
+            for (int round = 0; round < 6000; round++) {
+                Case c;
+                c.n = rnd() % 4 == 0 ? lengths[rnd() % lengths.size()] : (rnd() % 2 ? rnd() % 0x100000000ull : rnd() % 100'000);
+                c.sigma = pick({3, 4, 5, 6, 9, 21}), c.layout = pick({0, 0, 1}), c.n_searchable = pick({2, 3, 4, 5});
+                c.bo.pair_lines = pick({-1, -1, 0, 1}), c.bo.jump_bytes = pick({-1, -1, -1, 0, 8, 16, 32, 12});
+                c.bo.top_depth = pick({-1, -1, -1, 0, 3, 8, 12, 14, 15, 16, 30}), c.bo.full_sa = pick({-1, -1, 0, 1});
+                c.bo.text_units = pick({-1, -1, 0, 1}), c.bo.seed_symbols = pick({-1, -1, -1, 0, 1, 9, 16, 22, 24, 3, 30});
+                c.bo.seed_load_percent = pick({0, 0, 20, 55, 100}), c.bo.inverse_sa = pick({-1, -1, 0, 1});
+                c.bo.aux_budget_bytes = rnd() % 2 ? 0 : (rnd() % 2 ? budgets[rnd() % budgets.size()] : rnd() % 200'000'000'000ull);
+                if (rnd() % 3 == 0) c.env = envs[rnd() % envs.size()];
+                if (rnd() % 8 == 0) c.env.no_pair_lines = true;
+                c.total = rnd() % 4 == 0 ? (8 + rnd() % 300) * gib : total288;
+                c.free1 = rnd() % 4 == 0 ? memory[rnd() % 3].first : rnd() % (c.total + 1);
+                if (const int rc = check(c)) return rc;
+            }
+            if (raised == 0 || default_shapes == 0 || shrunk == 0) return 55;
+            std::printf("ok %" PRIu64 " %" PRIu64 " %" PRIu64 " %" PRIu64 " %" PRIu64 "\n", made, cases - made, raised, default_shapes, shrunk);
         } else {
             return 2;
         }

@@ -22,7 +22,7 @@ KINDS = ("cursors", "count", "locate", "near-misses")
 
 
 def has_seed_table(variant):
-    """a seed table is asked for, or the build makes the default shape, which has one (fm_index.hip build_aux: none of its
+    """a seed table is asked for, or the build makes the default shape, which has one (aux_plan.hpp plan_aux_shape: none of its
     structures asked for or switched off, on the library's own table layout)"""
     build = _VARIANTS[variant][1]
     named = ("seed_symbols", "jump_entry_bytes", "full_suffix_array", "inverse_suffix_array", "text_units", "reference_table_layout")

@@ -538,7 +538,7 @@ def test_acceleration_structures_shrink_to_the_memory_budget(budget, want):
     aux = DeviceEngine(g).aux_info()
     n = g.total_text_len()
     if budget is None:
-        # every option at its default and room for it: the default shape (fm_index.hip build_aux) -- seed table, text units,
+        # every option at its default and room for it: the default shape (aux_plan.hpp plan_aux_shape) -- seed table, text units,
         # full and inverse suffix array, pair lines, a top table, no jump table
         assert aux["default_shape"] and aux["seed"]["k"] >= 8 and aux["full_suffix_array"] and aux["inverse_suffix_array"] \
             and aux["text_units"] and aux["pair_lines"] and aux["jump_entry_bytes"] == 0 and 0 < aux["top_table_depth"] <= 14

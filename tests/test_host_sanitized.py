@@ -180,3 +180,16 @@ def test_host_chunk_planner_and_wire_layout(checker):
         rc, out = checker("chunks", seed)
         assert rc == 0 and out.startswith("ok "), (seed, rc, out)
         assert int(out.split()[1]) > 2000 and int(out.split()[2]) > 100000
+
+
+def test_aux_planner_equals_the_arithmetic_it_replaced(checker):
+    """aux_plan.hpp (which auxiliary structures an index gets: the budget, the default shape's fit test, the seed k, the wants,
+    jump and top table wanted and shrunk) under ASan + UBSan against FmIndex::build_aux's arithmetic as it stood, restated in
+    the checker: field for field and error for error over every text length, alphabet, layout, option value, budget, pair
+    of memory readings and environment override taken one at a time, and a few thousand random combinations; two worked
+    examples of a 3.1 G-symbol text on a 288 GiB device are pinned as literals."""
+    for seed in (1, 2, 3):
+        rc, out = checker("auxplan", seed)
+        assert rc == 0 and out.startswith("ok "), (seed, rc, out)
+        made, random, raised, default_shapes, shrunk = map(int, out.split()[1:])
+        assert made > 300000 and random == 6000 and raised > 10000 and default_shapes > 5000 and shrunk > 50000

@@ -2,9 +2,10 @@
 """Compares the kernels of two gfx950 code objects: names, resource use (.vgpr_count, .sgpr_count, .vgpr_spill_count,
 .group_segment_fixed_size, .private_segment_fixed_size from the AMDGPU metadata note) and the disassembly of every kernel,
 symbol by symbol (the order in which a compiler emits them may differ).  Prints one line per differing name and the totals;
-exit status 1 when anything differs.
+exit status 1 when anything differs.  Several B files stand for one translation unit split into these: every name must be in
+exactly one of them.
 
-usage: python tools/compare_code_objects.py A.co B.co
+usage: python tools/compare_code_objects.py A.co B.co [B2.co ...]
 A code object comes out of a device-only compile in two steps:
     hipcc <the Makefile's CXXFLAGS> --cuda-device-only -c search.hip -o search.dev.o
     clang-offload-bundler --unbundle --type=o --targets=hip-amdgcn-amd-amdhsa--gfx950 --input=search.dev.o --output=A.co
@@ -59,19 +60,27 @@ def disassembly(path):
         m = re.match(r"^[0-9a-f]* ?<(.+)>:$", line)
         if m:
             cur = res.setdefault(m.group(1), [])
-        elif cur is not None and line.strip():
+        elif cur is not None and line.strip() and line.strip() != "...":  # ("...": the zero padding behind a symbol)
             cur.append(re.sub(r"\s*//.*$", "", line.strip()))
     return res
 
 
 def main():
-    if len(sys.argv) != 3:
+    if len(sys.argv) < 3:
         raise SystemExit(__doc__)
-    with tempfile.TemporaryDirectory() as tmp:
-        a, b = (code_object(p, tmp) for p in sys.argv[1:])
-        ka, kb = kernels(a), kernels(b)
-        da, db = disassembly(a), disassembly(b)
     differ = 0
+    with tempfile.TemporaryDirectory() as tmp:
+        a = code_object(sys.argv[1], tmp)
+        ka, da = kernels(a), disassembly(a)
+        kb, db = {}, {}
+        for p in sys.argv[2:]:
+            b = code_object(p, tmp)
+            kp, dp = kernels(b), disassembly(b)
+            for name in sorted((set(kp) & set(kb)) | (set(dp) & set(db))):
+                print(f"in more than one B: {name}")
+                differ += 1
+            kb.update(kp)
+            db.update(dp)
     for name in sorted(set(ka) | set(kb)):
         if name not in ka or name not in kb:
             print(f"only in {'A' if name in ka else 'B'}: {name}")
