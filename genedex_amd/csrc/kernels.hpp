@@ -124,6 +124,10 @@ void launch_search_call(const IndexView &ix, const SearchCall &call, hipStream_t
 
 // ---- search.hip ---------------------------------------------------------------------------
 void set_search_variant(int v);  // 0 quad, 1 lane, 2 pair (default), -1 re-read the environment
+// the variant in force (set_search_variant, else GDX_SEARCH_VARIANT, else 2); for search_ops.hip, not exported
+int search_variant() __attribute__((visibility("hidden")));
+
+// ---- search_ops.hip -----------------------------------------------------------------------
 // ASCII -> 2-bit packed queries on the device (include/gdx.h "packed queries")
 void launch_pack_queries(const IndexView &ix, const uint8_t *d_qbuf, uint64_t n_symbols, uint8_t *d_packed,
                          uint8_t *d_bad_flags, unsigned long long *d_bad_symbols, hipStream_t stream);

@@ -1,4 +1,4 @@
-// search.hip -- backward search, cursor extension and the operator-level rank / symbol_at kernels.
+// search.hip -- backward search: the kernels of the search chain and the launcher of one search call.
 //
 // search_pair_kernel4/8 (the default on DNA-sized alphabets): 4 or 8 lanes per query, 16 or 8 queries per
 // wavefront advancing in lock-step -- the shape of the reference's 64-wide BatchComputedCursors
@@ -8,8 +8,9 @@
 // statement of what the pair kernels compute.
 //
 // What is in this file, in its order (DESIGN.md section 4 has a row for each kernel with its bound and its bytes):
-//   query windows        QueryWindow / PackedQueryWindow / FastWindow, query_words: a query's symbols, eight per load, from IO bytes
-//                        (translated through the alphabet's table or two v_perm tables) or from 2-bit codes
+//   (search_device.hpp)  query windows (QueryWindow / PackedQueryWindow / SpanWindow / FastWindow, query_words), top_lookup, the
+//                        length-ordered schedule, the packed resume states, sel4, grid_for_items, GDX_DISPATCH_TABLE: what
+//                        several kernel families, or this file and search_ops.hip, use
 //   general kernels      search_kernel<Table, lanes> (rank lines / generic planes, one LF step per fetch), search_pair_kernel4/8 and
 //                        their _defer variants (pair lines: two symbols per fetch; top table, jump table), search_pair_packed_kernel4
 //                        (the same on 2-bit reads, resumes from a state), search_pair_stats_kernel4/8 (the step counters the bench prints)
@@ -19,10 +20,9 @@
 //                        search_seed_kernel4<translation, exact, cursor> (four lanes per read: exact intervals through the ISA, the
 //                        cursor API's first chunk, alphabets and buffers the lane kernel does not take), search_verify_kernel4
 //                        (listed reads: up to four rows against the text), seed_text_kernel4 (long reads: the text in front of the seed)
-//   operator level       extend_front_kernel (Cursor::extend_query_front), rank_many_kernel, symbol_at_kernel, lf_walk_kernel
-//   tables and helpers   fill_lookup_kernel, fill_top_kernel, top_wide_kernel, pack_queries_kernel, zero_segments_kernel,
-//                        fill_uniform_offsets[_list]_kernel, tile_sums_lists_kernel
-//   launch_search        intervals of a batch with the general kernels (query options choose the variant)
+//   (search_ops.hip)     operator level: extend_front_kernel (Cursor::extend_query_front), suffix segments, SMEMs, rank_many_kernel,
+//                        symbol_at_kernel, lf_walk_kernel, fill_lookup_kernel, fill_top_kernel, top_wide_kernel, pack_queries_kernel
+//   helpers              zero_segments_kernel, fill_uniform_offsets[_list]_kernel, tile_sums_lists_kernel
 //   launch_search_call   ONE search call of any kind (count / records / compact results / exact intervals / cursor chunk) on any
 //                        index shape: picks the kernels above, chains their lists, folds the hit totals -- the only place that
 //                        knows which kernel serves which shape
@@ -31,276 +31,11 @@
 #include <string>
 #include <type_traits>
 
-#include "common.hpp"
-#include "kernels.hpp"
+#include "search_device.hpp"
 
 namespace gdx {
 
 namespace {
-
-constexpr int kBlock = 256;
-
-// Reads the IO symbols of one query right-to-left through aligned 8-byte windows, so a lane
-// issues one global load per 8 LF steps; the next window is requested one window ahead.
-struct QueryWindow {
-    const uint64_t *words;
-    uint64_t cur;        // window holding byte `pos-1`
-    uint64_t next;       // window below it (prefetched)
-    uint64_t cur_word;   // index of `cur`
-    uint64_t first_word; // lowest word that belongs to this query
-
-    __device__ __forceinline__ void init(const uint8_t *qbuf, uint64_t begin, uint64_t pos)
-    {
-        words = reinterpret_cast<const uint64_t *>(qbuf);
-        first_word = begin >> 3;
-        const bool any = pos > begin;
-        cur_word = any ? ((pos - 1) >> 3) : first_word;
-        cur = any ? words[cur_word] : 0ull;
-        next = (any && cur_word > first_word) ? words[cur_word - 1] : 0ull;
-    }
-    // byte at absolute offset `at` (at must walk downwards)
-    __device__ __forceinline__ uint32_t get(uint64_t at)
-    {
-        const uint64_t w = at >> 3;
-        if (w != cur_word) {
-            cur_word = w;
-            cur = next;
-            next = (w > first_word) ? words[w - 1] : 0ull;
-        }
-        return static_cast<uint32_t>(cur >> ((at & 7u) * 8u)) & 0xffu;
-    }
-};
-
-// The same over packed queries (include/gdx.h "packed queries": symbol j of the buffer in bits 2 (j & 7) of 16-bit unit
-// j >> 3, offsets count symbols): one 2-byte load per 8 LF steps; get() returns the 2-bit code (dense symbol - 1).
-struct PackedQueryWindow {
-    const uint16_t *units;
-    uint32_t cur, next;
-    uint64_t cur_unit, first_unit;
-
-    __device__ __forceinline__ void init(const uint8_t *qbuf, uint64_t begin, uint64_t pos)
-    {
-        units = reinterpret_cast<const uint16_t *>(qbuf);
-        first_unit = begin >> 3;
-        const bool any = pos > begin;
-        cur_unit = any ? ((pos - 1) >> 3) : first_unit;
-        cur = any ? units[cur_unit] : 0u;
-        next = (any && cur_unit > first_unit) ? units[cur_unit - 1] : 0u;
-    }
-    __device__ __forceinline__ uint32_t get(uint64_t at)
-    {
-        const uint64_t u = at >> 3;
-        if (u != cur_unit) {
-            cur_unit = u;
-            cur = next;
-            next = (u > first_unit) ? units[u - 1] : 0u;
-        }
-        return (cur >> ((at & 7u) * 2u)) & 3u;
-    }
-};
-
-// Where query q lies in the buffer: [qbeg[q], qend[q]) from the offsets arrays, or -- a UNIFORM batch, ulen != 0: every
-// query has ulen symbols and query q starts at q * ulen (gdx_query_layout_t) -- computed, which saves the kernels the
-// 8 bytes of offsets per query (the arrays may then be null).
-__device__ __forceinline__ uint64_t query_begin(const uint64_t *__restrict__ qbeg, uint32_t ulen, uint64_t q)
-{
-    return ulen != 0u ? q * ulen : qbeg[q];
-}
-__device__ __forceinline__ uint64_t query_end(const uint64_t *__restrict__ qend, uint32_t ulen, uint64_t q)
-{
-    return ulen != 0u ? (q + 1u) * ulen : qend[q];
-}
-// the aligned word (packed, kXlate == 2: the 16-bit unit) that holds the first symbol of a query: fast_window's `wbase`
-template <int kXlate>
-__device__ __forceinline__ const uint64_t *query_words(const uint8_t *__restrict__ qbuf, uint64_t begin)
-{
-    if (kXlate == 2) return reinterpret_cast<const uint64_t *>(reinterpret_cast<const uint16_t *>(qbuf) + (begin >> 3));
-    return reinterpret_cast<const uint64_t *>(qbuf) + (begin >> 3);
-}
-
-// The query as the pair kernels see it: dense codes, one nibble per symbol, eight symbols per 32-bit word, read
-// right-to-left.  The kGroup lanes of a query translate the query COOPERATIVELY: a span of eight 8-byte words (64
-// bytes: a whole 50-mer) is loaded and translated through the alphabet table in LDS by the group at once, each lane
-// its own one (8 lanes) or two (4 lanes) words, and any lane fetches any translated word of the span from its
-// owner with one ds_bpermute (the LDS crossbar, no LDS memory).  Translating every word in every lane -- which is
-// what a plain per-lane window does -- made the kernel VALU-bound: PMC showed 880 VALU instructions per wavefront
-// and 16 queries, 85 % VALU issue utilisation, and no gain from a quarter fewer DRAM requests.
-__device__ __forceinline__ bool all_dna(uint32_t x);
-__device__ __forceinline__ uint32_t to_2bit(uint32_t x);
-constexpr uint32_t kNoCode = 0x10000u;  // compares unequal to every 16-bit entry code
-
-// kPacked: the query buffer holds 2-bit codes (dense symbol - 1 of the four searchable symbols, symbol j of the
-// buffer in bits 2 (j & 3) of byte j >> 2; include/gdx.h "packed queries") and offsets count SYMBOLS: a span word is
-// then a 16-bit unit of the buffer that needs no translation at all.
-template <int kGroup, bool kPacked>
-struct SpanWindow {
-    static constexpr int kWordsPerLane = 8 / kGroup;
-    const uint64_t *base;  // base[0] holds the first byte of the query (packed: the 16-bit unit of its first symbol)
-    uint32_t off0;         // byte (packed: symbol) offset of the query inside base[0] (inside its first unit)
-    uint32_t top_w;        // span word k = query word top_w - k, k = 0 .. 7 (words below 0 read as 0)
-    uint32_t w0, w1;       // this lane's translated span words: k = sub * kWordsPerLane (and + 1)
-    uint32_t p;            // the same words as 2-bit codes (dense - 1), 16 bits each: w0 in the low half, w1 above
-    uint32_t valid8;       // bit k: all eight symbols of span word k are dense codes 1..4 (the same in the group)
-
-    static __device__ __forceinline__ uint32_t translate(uint64_t w, const uint8_t *s_dense)
-    {
-        uint32_t t = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 8; k++) t |= static_cast<uint32_t>(s_dense[(w >> (8u * k)) & 0xffu]) << (4u * k);
-        return t;
-    }
-    __device__ __forceinline__ void init(const uint8_t *qbuf, uint64_t begin)
-    {
-        if (kPacked) base = reinterpret_cast<const uint64_t *>(reinterpret_cast<const uint16_t *>(qbuf) + (begin >> 3));
-        else base = reinterpret_cast<const uint64_t *>(qbuf) + (begin >> 3);
-        off0 = static_cast<uint32_t>(begin & 7u);
-        top_w = 0;
-        w0 = w1 = p = valid8 = 0;
-    }
-    // eight 2-bit codes -> eight nibble codes 1..4
-    static __device__ __forceinline__ uint32_t spread(uint32_t u)
-    {
-        uint32_t x = u & 0xffffu;
-        x = (x | (x << 8)) & 0x00ff00ffu;
-        x = (x | (x << 4)) & 0x0f0f0f0fu;
-        x = (x | (x << 2)) & 0x33333333u;
-        return x + 0x11111111u;
-    }
-    // positions the span so that its first word holds symbol rem - 1 (rem >= 1); group-uniform
-    __device__ __forceinline__ void load(uint32_t rem, const uint8_t *s_dense)
-    {
-        const uint32_t sub = threadIdx.x & (kGroup - 1u);
-        top_w = (off0 + rem - 1u) >> 3;
-        const int32_t first = static_cast<int32_t>(top_w) - static_cast<int32_t>(sub) * kWordsPerLane;
-        if (kPacked) {  // the units ARE the 2-bit span words; every symbol is one of the four searchable ones
-            const uint16_t *units = reinterpret_cast<const uint16_t *>(base);
-            const uint32_t u0 = first >= 0 ? units[first] : 0u;
-            const uint32_t u1 = (kWordsPerLane == 2 && first >= 1) ? units[first - 1] : 0u;
-            p = u0 | (u1 << 16);
-            w0 = spread(u0);
-            w1 = spread(u1);
-            valid8 = 0xffu;
-            return;
-        }
-        uint64_t r0 = 0, r1 = 0;
-        if (kWordsPerLane == 2) {
-            if (first >= 1) {  // both words with one 16-byte load (8-byte aligned)
-                const u32x4 v = *reinterpret_cast<const u32x4 *>(base + (first - 1));
-                r1 = static_cast<uint64_t>(v.x) | (static_cast<uint64_t>(v.y) << 32);
-                r0 = static_cast<uint64_t>(v.z) | (static_cast<uint64_t>(v.w) << 32);
-            } else if (first == 0) {
-                r0 = base[0];
-            }
-        } else if (first >= 0) {
-            r0 = base[first];
-        }
-        finish(r0, r1, s_dense);
-    }
-    // the second half of load(): this lane's raw span words -> translated words, 2-bit form, validity mask
-    __device__ __forceinline__ void finish(uint64_t r0, uint64_t r1, const uint8_t *s_dense)
-    {
-        const uint32_t sub = threadIdx.x & (kGroup - 1u);
-        w0 = translate(r0, s_dense);
-        if (kWordsPerLane == 2) w1 = translate(r1, s_dense);
-        // 2-bit form and the group's validity mask (an OR over the group's lanes by DPP)
-        p = to_2bit(w0);
-        uint32_t m = all_dna(w0) ? 1u : 0u;
-        if (kWordsPerLane == 2) {
-            p |= to_2bit(w1) << 16;
-            m |= all_dna(w1) ? 2u : 0u;
-        }
-        m <<= sub * kWordsPerLane;
-        m |= static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(m), 0xB1, 0xF, 0xF, true));
-        m |= static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(m), 0x4E, 0xF, 0xF, true));
-        if (kGroup == 8) m |= static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(m), 0x141, 0xF, 0xF, true));
-        valid8 = m;
-    }
-    // 2-bit codes of span word k (16 bits)
-    __device__ __forceinline__ uint32_t word2(uint32_t k) const
-    {
-        const uint32_t owner = (threadIdx.x & 63u & ~(kGroup - 1u)) + k / kWordsPerLane;
-        const uint32_t v = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>(owner << 2), static_cast<int>(p)));
-        return (kWordsPerLane == 2 && (k & 1u)) ? v >> 16 : v & 0xffffu;
-    }
-    // 2-bit codes of the symbols r - 1 .. r - 8 (r >= 8, covered by the span), bits 15:14 = symbol r - 1: the form the
-    // jump entries store; kNoCode when a word they touch holds a symbol outside 1..4 (conservative: the caller then
-    // looks at the nibbles)
-    __device__ __forceinline__ uint32_t level(uint32_t r) const
-    {
-        const uint32_t b = off0 + r - 1u, k = top_w - (b >> 3);
-        const uint32_t s = (b & 7u) + 1u;
-        const uint32_t k1 = k + 1u > 7u ? 7u : k + 1u;
-        const uint32_t need = (1u << k) | (s < 8u ? (1u << k1) : 0u);
-        const uint32_t x = (word2(k) << 16) | word2(k1);
-        return (valid8 & need) == need ? ((x >> (2u * s)) & 0xffffu) : kNoCode;
-    }
-    // translated span word k (0 .. 7), k uniform in the group
-    __device__ __forceinline__ uint32_t word(uint32_t k) const
-    {
-        const uint32_t owner = (threadIdx.x & 63u & ~(kGroup - 1u)) + k / kWordsPerLane;
-        const uint32_t mine = (kWordsPerLane == 2 && (k & 1u)) ? w1 : w0;
-        return static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>(owner << 2), static_cast<int>(mine)));
-    }
-    // true when the symbols r - 1 .. r - 8 (those of them that exist) lie inside the span
-    __device__ __forceinline__ bool covers(uint32_t r) const
-    {
-        const uint32_t hi_w = (off0 + r - 1u) >> 3, lo_w = (off0 + (r >= 8u ? r - 8u : 0u)) >> 3;
-        return hi_w <= top_w && top_w - lo_w <= 7u;
-    }
-    // codes of the 8 symbols that end with symbol r - 1 (nibble 7 = symbol r - 1); the span must cover them.
-    // Nibbles of symbols before the start of the query are garbage and must not be used (callers check r).
-    __device__ __forceinline__ uint32_t at(uint32_t r) const
-    {
-        const uint32_t b = off0 + r - 1u, k = top_w - (b >> 3);
-        const uint32_t s = (b & 7u) + 1u;  // nibbles taken from span word k, the rest from word k + 1
-        const uint32_t cur = word(k), next = word(k + 1u > 7u ? 7u : k + 1u);
-        return s == 8u ? cur : __builtin_amdgcn_alignbit(cur, next, 4u * s);
-    }
-    // the same for the symbols the search consumes next (rem >= 1): moves the span down when they have left it
-    __device__ __forceinline__ uint32_t code8(uint32_t rem, const uint8_t *s_dense)
-    {
-        if (!covers(rem)) load(rem, s_dense);
-        return at(rem);
-    }
-};
-
-__device__ __forceinline__ bool has_zero_nibble(uint32_t x) { return ((x - 0x11111111u) & ~x & 0x88888888u) != 0u; }
-
-// Top table (IndexView::top): the interval after the first D = top_depth symbols of the search, i.e. the last D
-// symbols of the query, when all of them are dense codes 1..4.  `a` = code8(rem), `b` = code8(rem - 8) (only its
-// top D - 8 nibbles are used).  The entry of a D-mer that does not occur holds the frozen interval (start == end as
-// they stood at the step that emptied it, like the reference's lookup tables, lookup_table.rs:225-258), so such a
-// query is finished by the lookup.  Returns false when a symbol is outside 1..4: the caller then runs the ordinary
-// steps from the start, which validate symbols as lazily as the reference does.
-__device__ __forceinline__ bool all_dna(uint32_t x);
-__device__ __forceinline__ uint32_t to_2bit(uint32_t x);
-
-__device__ __forceinline__ bool top_lookup(const IndexView &ix, uint32_t a, uint32_t b, uint32_t &lo, uint32_t &hi)
-{
-    const uint32_t d = ix.top_depth;  // 1 .. 16: the top min(d, 8) nibbles of a and the top d - 8 of b
-    const uint32_t ma = d >= 8u ? 0xffffffffu : 0xffffffffu << (4u * (8u - d));
-    const uint32_t mb = d > 8u ? 0xffffffffu << (4u * (16u - d)) : 0u;
-    const uint32_t va = (a & ma) | (0x11111111u & ~ma), vb = (b & mb) | (0x11111111u & ~mb);  // unused := valid
-    if (!all_dna(va) || !all_dna(vb)) return false;
-    const uint32_t idx = ((to_2bit(va) << 16) | to_2bit(vb)) >> (32u - 2u * d);
-    const uint2 e = ix.top[idx];
-    lo = e.x;
-    hi = e.y;
-    return true;
-}
-
-// appends the cursors of this wavefront's `alive` lanes to ca.active_out: one atomic per wavefront
-__device__ __forceinline__ void compact_alive(bool alive, uint32_t q, const CursorArgs &ca)
-{
-    const unsigned long long mask = __ballot(alive);
-    if (mask == 0ull) return;
-    const uint32_t lane = __lane_id();
-    const int leader = __ffsll(static_cast<long long>(mask)) - 1;
-    uint32_t first = 0;
-    if (static_cast<int>(lane) == leader) first = atomicAdd(ca.n_active_out, static_cast<uint32_t>(__popcll(mask)));
-    first = __shfl(first, leader);
-    if (alive) ca.active_out[first + __popcll(mask & ((1ull << lane) - 1ull))] = q;
-}
 
 // kGroup lanes cooperate on one query (1: LineTable / GenericTable, 4: QuadLineTable); control flow is
 // uniform inside a group, lane 0 of the group writes the results.  kResume: cursor extension (see search_pair_body,
@@ -406,133 +141,6 @@ __global__ __launch_bounds__(kBlock) void search_kernel(IndexView ix, const uint
             compact_alive(writer && lo != hi && status == GDX_Q_OK && more_left, static_cast<uint32_t>(q), ca);
     }
     if (step_stats && writer) atomicAdd(step_stats, static_cast<unsigned long long>(lf_steps));
-}
-
-// ---- length-ordered schedule inside a block -----------------------------------------------------------
-// The lock-step kernel idles the lanes of a finished query until the longest query of its wavefront ends.  Every
-// block searches a contiguous range of the batch (at most kMaxRange queries); when the lengths in that range are
-// spread out it first orders the range by length (counting sort in LDS, 4 symbols per bucket, longest first) and
-// its wavefronts take runs of that order, so the queries of a wavefront have nearly the same length.  Results
-// are written at the original query index.  All reads and writes of a block stay inside its range, so the
-// order costs no DRAM locality (an earlier batch-wide permutation did: its gathers were slower than the idle
-// lanes it saved), and there is no pre-pass and no host round trip.  Ranges of (nearly) equal lengths skip it.
-constexpr uint32_t kLenBuckets = 64;
-constexpr uint32_t kMaxRange = 3072;  // queries per block and range: u16 permutation, 6 KB of LDS
-constexpr uint32_t kMaxDefer = 512;   // stragglers a block can park per range (8 KB of LDS); more are finished in place
-constexpr uint32_t kCursorRange = 1024;  // cursor extension: queries per range (their live list is 4 KB of LDS)
-
-__device__ __forceinline__ uint32_t length_bucket(uint64_t len)
-{
-    const uint64_t b = len >> 2;
-    return kLenBuckets - 1u - static_cast<uint32_t>(b < kLenBuckets - 1u ? b : kLenBuckets - 1u);
-}
-
-// Orders queries [base, base + cnt) of the batch by length bucket into s_perm (indices relative to base); returns
-// false (s_perm untouched) when the lengths are uniform enough: max - min <= min / 4.  Block-wide, all threads.
-__device__ __forceinline__ bool order_range_by_length(const uint64_t *__restrict__ qbeg,
-                                                      const uint64_t *__restrict__ qend,
-                                                      const uint32_t *__restrict__ active, uint64_t base, uint32_t cnt,
-                                                      uint16_t *s_perm, uint32_t *s_cnt, uint32_t *s_minmax)
-{
-    if (threadIdx.x < kLenBuckets) s_cnt[threadIdx.x] = 0;
-    if (threadIdx.x == 0) {
-        s_minmax[0] = 0xffffffffu;
-        s_minmax[1] = 0;
-    }
-    __syncthreads();
-    uint32_t mn = 0xffffffffu, mx = 0;
-    for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) {
-        const uint64_t qi = active ? active[base + i] : base + i;
-        const uint64_t len = qend[qi] - qbeg[qi];
-        const uint32_t l = len > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(len);
-        mn = l < mn ? l : mn;
-        mx = l > mx ? l : mx;
-        atomicAdd(&s_cnt[length_bucket(len)], 1u);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t omn = __shfl_xor(mn, off), omx = __shfl_xor(mx, off);
-        mn = omn < mn ? omn : mn;
-        mx = omx > mx ? omx : mx;
-    }
-    if ((threadIdx.x & 63u) == 0) {
-        atomicMin(&s_minmax[0], mn);
-        atomicMax(&s_minmax[1], mx);
-    }
-    __syncthreads();
-    mn = s_minmax[0];
-    mx = s_minmax[1];
-    if (mx - mn <= mn / 4u) return false;
-    if (threadIdx.x < kLenBuckets) {  // exclusive scan of the histogram by the first wavefront
-        const uint32_t v = s_cnt[threadIdx.x];
-        uint32_t x = v;
-        for (int off = 1; off < static_cast<int>(kLenBuckets); off <<= 1) {
-            const uint32_t y = __shfl_up(x, off);
-            if (static_cast<int>(threadIdx.x) >= off) x += y;
-        }
-        s_cnt[threadIdx.x] = x - v;
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) {
-        const uint64_t qi = active ? active[base + i] : base + i;
-        const uint32_t r = atomicAdd(&s_cnt[length_bucket(qend[qi] - qbeg[qi])], 1u);
-        s_perm[r] = static_cast<uint16_t>(i);
-    }
-    __syncthreads();
-    return true;
-}
-
-// all eight nibbles are dense codes 1..4 (searchable DNA symbols)
-__device__ __forceinline__ bool all_dna(uint32_t x)
-{
-    const uint32_t y = x - 0x11111111u;  // per nibble c - 1 when there is no zero nibble (no borrow)
-    return ((y & ~x & 0x88888888u) | (y & 0xccccccccu)) == 0u;
-}
-
-// eight nibble codes 1..4 -> eight 2-bit codes (c - 1), nibble 7 (the symbol consumed first) in bits 15:14: the form
-// the jump entries store (layout.hpp).  Only meaningful when all_dna(x).
-__device__ __forceinline__ uint32_t to_2bit(uint32_t x)
-{
-    uint32_t y = x - 0x11111111u;
-    y = (y & 0x03030303u) | ((y & 0x30303030u) >> 2);
-    y = (y & 0x000f000fu) | ((y & 0x0f000f00u) >> 4);
-    return (y & 0xffu) | ((y >> 8) & 0xff00u);
-}
-
-// Live cursors of a block's range (cursor extension, mode 2) are appended to the global list IN THE ORDER OF THEIR
-// POSITIONS in the range: s_live[p] = the cursor at position p, or kDeadCursor.  A list that starts sorted then stays
-// sorted chunk by chunk, and the next call's gathers of start / end / status / string offsets by cursor number touch
-// neighbouring lines; appending in the order of LDS atomics scattered them over sixteen lines per load instruction,
-// which made a call over 34 M live cursors with empty strings cost 3.3 ms.
-constexpr uint32_t kDeadCursor = 0xffffffffu;
-__device__ __forceinline__ void flush_live_ordered(uint32_t *s_live, uint32_t cnt, uint32_t *s_part, uint32_t *s_base,
-                                                   uint32_t *active_out, uint32_t *n_active_out)
-{
-    constexpr uint32_t kPer = kCursorRange / kBlock;
-    uint32_t v[kPer], mine = 0;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t j = 0; j < kPer; j++) {
-        const uint32_t p = threadIdx.x * kPer + j;
-        v[j] = p < cnt ? s_live[p] : kDeadCursor;
-        s_live[p] = kDeadCursor;  // for the next range
-        mine += v[j] != kDeadCursor ? 1u : 0u;
-    }
-    s_part[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {  // inclusive scan
-        const uint32_t o = static_cast<int>(threadIdx.x) >= off ? s_part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        s_part[threadIdx.x] += o;
-        __syncthreads();
-    }
-    const uint32_t total = s_part[kBlock - 1];
-    if (threadIdx.x == 0 && total != 0u) *s_base = atomicAdd(n_active_out, total);
-    __syncthreads();
-    uint32_t pos = *s_base + s_part[threadIdx.x] - mine;
-#pragma unroll
-    for (uint32_t j = 0; j < kPer; j++)
-        if (v[j] != kDeadCursor) active_out[pos++] = v[j];
-    __syncthreads();
 }
 
 // Backward search on pair lines, the jump table and the top table: kGroup = 4 or 8 lanes per
@@ -1095,6 +703,25 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) 
 {
     search_pair_body<0, 4, false, kJump, kMode, false, true>(GDX_SEARCH_FWD);
 }
+// packed queries (2 bits per symbol): 4 lanes per query, plain loads
+template <int kJump, int kMode>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) void search_pair_packed_kernel4(GDX_SEARCH_ARGS)
+{
+    search_pair_body<0, 4, false, kJump, kMode, true>(GDX_SEARCH_FWD);
+}
+// accounting variants (gdx_search_step_stats_dev): the counters cost registers, so they are kept out of the
+// timed kernels; always the exact mode, whose LF steps are the reference's
+template <int kPolicy, int kJump, int kMode>
+__global__ __launch_bounds__(kBlock) void search_pair_stats_kernel8(GDX_SEARCH_ARGS)
+{
+    search_pair_body<kPolicy, 8, true, kJump, kMode>(GDX_SEARCH_FWD);
+}
+template <int kPolicy, int kJump, int kMode>
+__global__ __launch_bounds__(kBlock) void search_pair_stats_kernel4(GDX_SEARCH_ARGS)
+{
+    search_pair_body<kPolicy, 4, true, kJump, kMode>(GDX_SEARCH_FWD);
+}
+
 // ---- fast path of the count / locate search ----------------------------------------------------------------------
 // What almost every read of a non-repetitive text does is: top table, then jumps, then the lazy tail -- no pair line
 // is ever touched.  This kernel does only that, which leaves out the second line of registers, the pair-step
@@ -1104,25 +731,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) 
 // an N of the text) is appended to `leftover` untouched and searched by the general kernel afterwards
 // (launch_search_call).  Counts and hits of the queries it finishes are the general kernel's, bit for bit.
 // (the few fields of the IndexView it needs, so that the kernel arguments do not eat the SGPR budget of 8+ waves)
-// resume states of the seed kernel's list in their packed form (search_seed_kernel4 -> search_fast_kernel4, state_packed):
-// {lo, rows << 24 | kStatePacked | symbols left, codes hi, codes lo} carries the 32 symbols in front of the seed as 2-bit
-// codes (the one to be consumed next in the top bits of `codes hi`); {lo, kStatePlain | symbols left, hi, 0} an interval
-// of 256+ rows; all zero = from the beginning
-constexpr uint32_t kStatePacked = 1u << 23, kStatePlain = 1u << 22;
-// ... and, for search_verify_kernel4 only (state_packed == 2): {index of the k-mer's record in IndexView::seed_pairs,
-// 2 << 24 | kStatePacked | kStatePair | symbols left (1..32), codes hi, codes lo} -- a k-mer on exactly two rows whose seed
-// entry names such a record (kSeedPairInfo): the read is decided by that one 32-byte record.  3 << 24 / 4 << 24 in the rows' place:
-// the index is that of the k-mer's 64-byte record in IndexView::seed_quads (kSeedQuadInfo)
-constexpr uint32_t kStatePair = 1u << 21;
-// the fields of a packed state's second word: symbols left (bits 0-20), the three flags, rows (bits 24-31, fewer than 256)
-constexpr uint32_t kStateSymbolsMask = 0x1fffffu, kStateRowsShift = 24, kStateRowsMask = 0xffu << kStateRowsShift;
-static_assert((kStatePacked & kStatePlain) == 0u && (kStatePacked & kStatePair) == 0u && (kStatePlain & kStatePair) == 0u,
-              "state flags overlap");
-static_assert(((kStatePacked | kStatePlain | kStatePair) & kStateSymbolsMask) == 0u, "a state flag overlaps the symbols left");
-static_assert(((kStatePacked | kStatePlain | kStatePair) & kStateRowsMask) == 0u, "a state flag overlaps the rows");
-static_assert((kStateSymbolsMask & kStateRowsMask) == 0u && kStateRowsShift + 8u == 32u, "the symbols left overlap the rows, or rows < 256 do not fill the top byte");
-static_assert(kStateSymbolsMask >= 32u && (kStateSymbolsMask & (kStateSymbolsMask + 1u)) == 0u, "symbols left: a low bit field");
-
 struct FastView {
     const uint2 *top;
     const void *jump;
@@ -1146,104 +754,6 @@ __device__ __forceinline__ bool is_sampled(const FastView &ix, uint32_t i)
 //    per lane and four DPP broadcasts instead of two ds_bpermute and ~15 VALU per level;
 //  * a one-row interval with fewer than eight symbols left and no lookahead code (lengths 16 + 40 k + 1..7 with
 //    32-byte entries) is decided by the first level code of its row's entry instead of going to the general kernel.
-struct FastWindow {
-    uint32_t l0, l1, l2, l3;  // level 2 t | level 2 t + 1 << 16 held by lane t of the group (level j = the 2-bit codes
-                              // of the symbols rem - 1 - 8 j .. rem - 8 - 8 j, bits 15:14 = the first of them)
-    uint32_t valid8;          // bit k: every symbol of span word k is one of the four searchable ones
-    uint32_t s0;              // symbols of a level that lie in its first span word (1 .. 8)
-};
-// four query bytes -> their 2-bit codes in 8 bits (byte 0 in bits 1:0); `bad` becomes non-zero on any other byte
-template <class View>
-__device__ __forceinline__ uint32_t fast_pack4(const View &ix, uint32_t c, uint32_t &bad)
-{
-    const uint32_t sel = c & 0x07070707u;
-    const uint32_t code = __builtin_amdgcn_perm(ix.perm_code_hi, ix.perm_code_lo, sel);
-    const uint32_t expect = __builtin_amdgcn_perm(ix.perm_exp_hi, ix.perm_exp_lo, sel);
-    bad |= (c & ix.perm_mask) ^ expect;
-    uint32_t t = (code << 6) | code;
-    t = (t << 12) | t;
-    return (t >> 18) & 0xffu;
-}
-__device__ __forceinline__ uint32_t fast_pack4_lds(const uint8_t *s_dense, uint32_t c, uint32_t &bad)
-{
-    uint32_t out = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++) {
-        const uint32_t d = static_cast<uint32_t>(s_dense[(c >> (8u * k)) & 0xffu]) - 1u;
-        bad |= d & ~3u;
-        out |= (d & 3u) << (2u * k);
-    }
-    return out;
-}
-// positions the window so that level 0 starts at symbol rem - 1 (rem >= 1): each lane loads and translates two of
-// the eight span words (as SpanWindow::load), then the levels are cut out of the group's 128-bit code string
-// kXlate: 0 = bytes through the table in LDS, 1 = bytes through the v_perm tables, 2 = packed queries (the span words
-// are 16-bit units of the buffer, wbase points at the unit of the query's first symbol and off0 counts symbols)
-// the loads of fast_window: this lane's two span words, untranslated (packed queries: both units in .x)
-template <int kXlate>
-__device__ __forceinline__ u32x4 fast_window_load(const uint64_t *wbase, uint32_t off0, uint32_t rem, uint32_t sub)
-{
-    const uint32_t b = off0 + rem - 1u;
-    const int32_t first = static_cast<int32_t>(b >> 3) - static_cast<int32_t>(sub) * 2;
-    u32x4 raw = {0u, 0u, 0u, 0u};  // x, y = word first - 1 (span word 2 sub + 1); z, w = word first (span word 2 sub)
-    if (kXlate == 2) {
-        const uint16_t *units = reinterpret_cast<const uint16_t *>(wbase);
-        const uint32_t u0 = first >= 0 ? units[first] : 0u;
-        const uint32_t u1 = first >= 1 ? units[first - 1] : 0u;
-        raw.x = u0 | (u1 << 16);
-    } else if (first >= 1) {
-        raw = *reinterpret_cast<const u32x4 *>(wbase + (first - 1));
-    } else if (first == 0) {
-        const uint64_t r0 = wbase[0];
-        raw.z = static_cast<uint32_t>(r0);
-        raw.w = static_cast<uint32_t>(r0 >> 32);
-    }
-    return raw;
-}
-template <int kXlate, class View>
-__device__ __forceinline__ FastWindow fast_window_finish(const View &ix, const uint8_t *s_dense, u32x4 raw,
-                                                         uint32_t off0, uint32_t rem, uint32_t sub)
-{
-    const uint32_t b = off0 + rem - 1u;
-    const int32_t first = static_cast<int32_t>(b >> 3) - static_cast<int32_t>(sub) * 2;
-    uint32_t bad0 = 0, bad1 = 0, p;
-    if (kXlate == 2) {
-        p = raw.x;
-    } else {
-        if (kXlate == 1) {
-            p = fast_pack4(ix, raw.z, bad0) | (fast_pack4(ix, raw.w, bad0) << 8) | (fast_pack4(ix, raw.x, bad1) << 16) |
-                (fast_pack4(ix, raw.y, bad1) << 24);
-        } else {
-            p = fast_pack4_lds(s_dense, raw.z, bad0) | (fast_pack4_lds(s_dense, raw.w, bad0) << 8) |
-                (fast_pack4_lds(s_dense, raw.x, bad1) << 16) | (fast_pack4_lds(s_dense, raw.y, bad1) << 24);
-        }
-    }
-    uint32_t m = ((bad0 == 0u && first >= 0) ? 1u : 0u) | ((bad1 == 0u && first >= 1) ? 2u : 0u);
-    m <<= 2u * sub;
-    m |= static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(m), 0xB1, 0xF, 0xF, true));
-    m |= static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(m), 0x4E, 0xF, 0xF, true));
-    FastWindow w;
-    w.valid8 = m;
-    w.s0 = (b & 7u) + 1u;
-    // lane t: words 2 t (low half of p), 2 t + 1 (high half) and, from lane t + 1, word 2 t + 2
-    const uint32_t nxt = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(p), 0xF9, 0xF, 0xF, true));  // quad_perm [1,2,3,3]
-    const uint32_t even = __builtin_amdgcn_alignbit(p, p, 16);       // word 2 t << 16 | word 2 t + 1
-    const uint32_t odd = (p & 0xffff0000u) | (nxt & 0xffffu);         // word 2 t + 1 << 16 | word 2 t + 2
-    const uint32_t sh = 2u * w.s0;                                    // 2 .. 16
-    const uint32_t lv = ((even >> sh) & 0xffffu) | ((odd >> sh) << 16);
-    w.l0 = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(lv), 0x00, 0xF, 0xF, true));
-    w.l1 = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(lv), 0x55, 0xF, 0xF, true));
-    w.l2 = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(lv), 0xAA, 0xF, 0xF, true));
-    w.l3 = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(lv), 0xFF, 0xF, 0xF, true));
-    return w;
-}
-template <int kXlate, class View>
-__device__ __forceinline__ FastWindow fast_window(const View &ix, const uint8_t *s_dense, const uint64_t *wbase,
-                                                  uint32_t off0, uint32_t rem, uint32_t sub)
-{
-    return fast_window_finish<kXlate>(ix, s_dense, fast_window_load<kXlate>(wbase, off0, rem, sub), off0, rem, sub);
-}
-
 // kWide: intervals of up to sixteen rows (four per lane, one load round each) instead of four -- chosen per index
 // (launch_search_call): on a text without repeats almost no read needs it and the loops cost the others 3 %
 template <int kJump, int kXlate, bool kWide>
@@ -1718,15 +1228,6 @@ struct ExactView {
     const u32x4 *seed;
     uint32_t seed_buckets, seed_k, seed_tag_bits;
 };
-
-__device__ __forceinline__ uint32_t sel4(uint32_t i, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
-{
-    uint32_t v = a;
-    v = i == 1u ? b : v;
-    v = i == 2u ? c : v;
-    v = i == 3u ? d : v;
-    return v;
-}
 
 // kText (round 6; an index WITHOUT jump table that holds the full suffix array, the text units and the inverse suffix array --
 // the library's default shape): the jump table's place is taken by the text itself.  An interval of up to four rows that has
@@ -3474,528 +2975,7 @@ __global__ __launch_bounds__(kBlock) void seed_text_kernel4(
     }
 }
 
-// packed queries (2 bits per symbol): 4 lanes per query, plain loads
-template <int kJump, int kMode>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) void search_pair_packed_kernel4(GDX_SEARCH_ARGS)
-{
-    search_pair_body<0, 4, false, kJump, kMode, true>(GDX_SEARCH_FWD);
-}
-// accounting variants (gdx_search_step_stats_dev): the counters cost registers, so they are kept out of the
-// timed kernels; always the exact mode, whose LF steps are the reference's
-template <int kPolicy, int kJump, int kMode>
-__global__ __launch_bounds__(kBlock) void search_pair_stats_kernel8(GDX_SEARCH_ARGS)
-{
-    search_pair_body<kPolicy, 8, true, kJump, kMode>(GDX_SEARCH_FWD);
-}
-template <int kPolicy, int kJump, int kMode>
-__global__ __launch_bounds__(kBlock) void search_pair_stats_kernel4(GDX_SEARCH_ARGS)
-{
-    search_pair_body<kPolicy, 4, true, kJump, kMode>(GDX_SEARCH_FWD);
-}
-
-// Cursor::extend_query_front for m independent cursors (cursor.rs:34-51).  kGroup lanes per cursor as in
-// search_kernel; with pair lines (kPair) a symbol in 1..4 costs one 128-byte fetch and no table lookup.
-template <class Table, int kGroup, bool kPair>
-__global__ __launch_bounds__(kBlock) void extend_front_kernel(IndexView ix, uint32_t *__restrict__ start,
-                                                              uint32_t *__restrict__ end,
-                                                              const uint8_t *__restrict__ io_symbols, uint64_t m,
-                                                              uint8_t *__restrict__ out_status)
-{
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * (kBlock / kGroup);
-    const bool writer = (threadIdx.x % kGroup) == 0;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * (kBlock / kGroup) + threadIdx.x / kGroup; i < m; i += stride) {
-        uint32_t lo = start[i], hi = end[i];
-        const uint32_t c = ix.io_to_dense[io_symbols[i]];  // cursor.rs:34-38: translated before anything else
-        uint32_t status = GDX_Q_OK;
-        if (c == 0) {
-            status = GDX_Q_INVALID_SYMBOL;
-        } else if (lo != hi) {  // cursor.rs:41-48
-            if (kPair && c <= 4u) {
-                PairTable::lf1<1, 8>(ix, c, lo, hi, lo, hi);
-            } else {
-                uint32_t rlo, rhi;
-                Table::rank2(ix, c, lo, hi, rlo, rhi);
-                const uint32_t cc = ix.count[c];
-                lo = cc + rlo;
-                hi = cc + rhi;
-            }
-            if (writer) {
-                start[i] = lo;
-                end[i] = hi;
-            }
-        }
-        if (out_status && writer) out_status[i] = static_cast<uint8_t>(status);
-    }
-}
-
-// gdx_suffix_segments_many[_dev]: the greedy backward factorisation of every read into its longest matching suffix
-// segments (include/gdx.h).  A segment is what Cursor::extend_query_front (cursor.rs:34-51) makes of the read's symbols
-// from position e leftwards, starting from [0, n), until a step would empty the interval: the interval BEFORE that step
-// and the number of steps taken.  The next segment starts in front of it, up to max_segments times, all in one launch.
-// kGroup lanes per read and the table access of search_kernel / extend_front_kernel; control flow is uniform inside a
-// group, its first lane writes.  Three routes, identical results:
-//   LF steps    one per symbol: PairTable::lf1 (one 128-byte fetch) for symbols 1..4 on pair lines, else Table::rank2
-//   top table   a segment that has top_depth symbols 1..4 to start with takes their interval from the top table; the
-//               entry of an absent D-mer only says that the segment is shorter, which is then found step by step
-//   text        (kText: the index holds text units, SA and ISA) once the interval is ONE row the rest of the segment
-//               is read off the text in front of p = SA[row]: every lane compares eight symbols, a round covers
-//               8 kGroup, and the row afterwards is ISA[p - matched].  Text symbols outside 1..4 (sentinels, N, the
-//               pad in front of the text) never match; a READ symbol outside 1..4 hands the segment back to the LF
-//               steps, which know what an N matches and report symbols that are not in the alphabet.
-struct SegmentsOut {
-    uint32_t *n_segments, *remaining, *length, *start, *end;
-    uint8_t *status;
-};
-
-// The fetch chain of a read is dependent and latency-bound, so the kernel lives on reads in flight.  Waves per SIMD from
-// the registers the compiler reports (-Rpass-analysis=kernel-resource-usage): pair lines + text route 83 VGPRs = 5 waves
-// (asked for 6 it spills 20 bytes to scratch), the other text and one-lane instances 6 (61 .. 73 VGPRs), the rest 7
-// (53 .. 71); no scratch in any instance.
-template <class Table, int kGroup, bool kPair, bool kText>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((kText && kPair) ? 5 : ((kText || kGroup == 1) ? 6 : 7)))) void suffix_segments_kernel(
-    IndexView ix, const uint8_t *__restrict__ qbuf, const uint64_t *__restrict__ qoff, uint64_t nq, uint32_t max_segments,
-    SegmentsOut out)
-{
-    __shared__ uint8_t s_dense[256];
-    __shared__ uint32_t s_count[257];
-    for (int i = threadIdx.x; i < 256; i += kBlock) s_dense[i] = ix.io_to_dense[i];
-    for (int i = threadIdx.x; i <= ix.sigma; i += kBlock) s_count[i] = ix.count[i];
-    __syncthreads();
-
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * (kBlock / kGroup);
-    const bool writer = (threadIdx.x % kGroup) == 0;
-    const uint32_t sub = threadIdx.x % kGroup;
-    const uint32_t depth = (ix.top != nullptr && ix.layout == 0) ? ix.top_depth : 0u;
-    for (uint64_t q = static_cast<uint64_t>(blockIdx.x) * (kBlock / kGroup) + threadIdx.x / kGroup; q < nq; q += stride) {
-        const uint64_t begin = qoff[q];
-        const uint32_t m = static_cast<uint32_t>(qoff[q + 1] - begin);
-        const uint64_t slot0 = q * max_segments;
-        uint32_t e = m, n_seg = 0, status = GDX_Q_OK;
-        while (e > 0u && n_seg < max_segments) {
-            uint32_t lo = 0, hi = ix.n, len = 0;
-            if (depth != 0u && e >= depth) {  // the segment's first `depth` symbols as top_lookup takes them
-                uint32_t a = 0, b = 0;
-                for (uint32_t s = 0; s < depth; s++) {
-                    const uint32_t c = s_dense[qbuf[begin + e - 1u - s]];
-                    if (s < 8u) a |= c << (4u * (7u - s));
-                    else b |= c << (4u * (15u - s));
-                }
-                uint32_t tlo, thi;
-                if (top_lookup(ix, a, b, tlo, thi) && tlo != thi) {
-                    lo = tlo;
-                    hi = thi;
-                    len = depth;
-                }
-            }
-            QueryWindow win;
-            win.init(qbuf, begin, begin + (e - len));
-            bool text_open = kText;  // false between a read symbol outside 1..4 and the LF step that takes it
-            while (len < e) {
-                if (kText && text_open && len != 0u && hi - lo == 1u) {
-                    uint32_t p = ix.sa_full[lo];  // the suffix at p starts with the segment so far
-                    bool blocked = false;
-                    while (len < e) {
-                        const uint32_t rem = e - len;
-                        const uint64_t at = begin + rem;  // read symbol j of the round sits at at - 1 - j, text symbol at p - 1 - j
-                        // (a round begins with p >= 0 and looks at most 8 kGroup <= 32 symbols back: inside the pad units)
-                        const uint64_t t_hi = static_cast<uint64_t>(p) + 32u * kTextPadUnits - 1u - 8u * sub, t_lo = t_hi - 7u;
-                        const u32x4 u_hi = ix.text_units[t_hi >> 5];
-                        const u32x4 u_lo = (t_lo >> 5) != (t_hi >> 5) ? ix.text_units[t_lo >> 5] : u_hi;
-                        uint32_t mine = 0, dirty = 0;
-                        for (uint32_t k = 0; k < 8u; k++) {
-                            const uint32_t j = 8u * sub + k;
-                            if (j >= rem) break;
-                            const uint32_t c = s_dense[qbuf[at - 1u - j]];
-                            if (c - 1u >= 4u) {
-                                dirty = 1u;
-                                break;
-                            }
-                            const uint64_t t = t_hi - k;
-                            const u32x4 u = (t >> 5) == (t_hi >> 5) ? u_hi : u_lo;
-                            const uint32_t i = static_cast<uint32_t>(t & 31u);
-                            const uint32_t code = ((i < 16u ? u.x >> (2u * i) : u.y >> (2u * (i - 16u)))) & 3u;
-                            if (((u.z >> i) & 1u) != 0u || code != c - 1u) break;
-                            mine++;
-                        }
-                        const uint32_t v = mine | (dirty << 8);
-                        uint32_t total = 0, stop = 0, stop_dirty = 0;
-#pragma unroll
-                        for (int l = 0; l < kGroup; l++) {
-                            const uint32_t vl = kGroup == 1 ? v : static_cast<uint32_t>(__shfl(static_cast<int>(v), l, kGroup));
-                            if (stop == 0u) {
-                                total += vl & 0xffu;
-                                if ((vl & 0xffu) < 8u) {
-                                    stop = 1u;
-                                    stop_dirty = vl >> 8;
-                                }
-                            }
-                        }
-                        p -= total;
-                        len += total;
-                        if (stop != 0u) {
-                            blocked = stop_dirty == 0u;  // a mismatch, a sentinel, the text's or the read's first symbol
-                            break;
-                        }
-                    }
-                    lo = ix.isa[p];
-                    hi = lo + 1u;
-                    if (blocked || len == e) break;
-                    text_open = false;
-                    win.init(qbuf, begin, begin + (e - len));
-                    continue;
-                }
-                const uint32_t c = s_dense[win.get(begin + (e - len) - 1u)];
-                if (c == 0u) {  // alphabet.rs:195-198: cursor.rs:34-38 translates before anything else
-                    status = GDX_Q_INVALID_SYMBOL;
-                    break;
-                }
-                if (lo == hi) break;  // (an index without rows: nothing occurs)
-                uint32_t nlo, nhi;
-                if (kPair && c <= 4u) {
-                    PairTable::lf1<0, kGroup>(ix, c, lo, hi, nlo, nhi);
-                } else {
-                    Table::rank2(ix, c, lo, hi, nlo, nhi);
-                    const uint32_t cc = s_count[c];
-                    nlo += cc;
-                    nhi += cc;
-                }
-                if (nlo == nhi) break;  // the stop rule: the interval from before the step that emptied it
-                lo = nlo;
-                hi = nhi;
-                len++;
-                text_open = kText;
-            }
-            if (status != GDX_Q_OK) break;
-            if (writer) {
-                out.length[slot0 + n_seg] = len;
-                out.start[slot0 + n_seg] = len != 0u ? lo : 0u;
-                out.end[slot0 + n_seg] = len != 0u ? hi : 0u;
-            }
-            e -= len != 0u ? len : 1u;
-            n_seg++;
-        }
-        if (status != GDX_Q_OK) {
-            n_seg = 0;
-            e = m;
-        }
-        if (writer) {
-            for (uint32_t j = n_seg; j < max_segments; j++) {
-                out.length[slot0 + j] = 0u;
-                out.start[slot0 + j] = 0u;
-                out.end[slot0 + j] = 0u;
-            }
-            out.n_segments[q] = n_seg;
-            out.remaining[q] = e;
-            if (out.status != nullptr) out.status[q] = static_cast<uint8_t>(status);
-        }
-    }
-}
-
-// gdx_smems_many[_dev]: the super-maximal exact matches of every read (include/gdx.h has the definition), found by a walk
-// that alternates between two one-directional indexes: fx over the texts, rx over the same texts each reversed.  From
-// position p a FORWARD pass on rx consumes q[p], q[p + 1], ... (extending in front of the reversed match) and gives the
-// longest e with q[p, e) occurring; a BACKWARD pass on fx from e, the pass of suffix_segments_kernel, gives the longest
-// match [s, e) that ends there and its interval in fx; [s, e) is an SMEM and the walk goes on at p = s - 1.  All in one
-// launch; kGroup lanes per read, control flow uniform inside a group, its first lane writes.  Both passes step as the
-// segments kernel does (PairTable::lf1 for symbols 1..4 on pair lines -- kPair: BOTH views hold them -- else Table::rank2
-// plus count) and enter through their own index's top table when the pass has top_depth symbols 1..4 ahead of it; the
-// entry of an absent D-mer only says that the pass is shorter, which is then found step by step.  io_to_dense and count
-// are the same in both indexes (the host checks it), so the block keeps one copy.
-struct SmemsOut {
-    uint32_t *n_smems, *remaining, *begin, *length, *start, *end;
-    uint8_t *status;
-};
-
-// The query's symbols left to right through aligned 8-byte windows, the next one requested a window ahead: QueryWindow
-// for the forward pass.  Bytes [pos, end) with pos < end; get() must walk upwards from pos.
-struct ForwardQueryWindow {
-    const uint64_t *words;
-    uint64_t cur, next, cur_word, last_word;
-
-    __device__ __forceinline__ void init(const uint8_t *qbuf, uint64_t pos, uint64_t end)
-    {
-        words = reinterpret_cast<const uint64_t *>(qbuf);
-        last_word = (end - 1) >> 3;
-        cur_word = pos >> 3;
-        cur = words[cur_word];
-        next = cur_word < last_word ? words[cur_word + 1] : 0ull;
-    }
-    __device__ __forceinline__ uint32_t get(uint64_t at)
-    {
-        const uint64_t w = at >> 3;
-        if (w != cur_word) {
-            cur_word = w;
-            cur = next;
-            next = w < last_word ? words[w + 1] : 0ull;
-        }
-        return static_cast<uint32_t>(cur >> ((at & 7u) * 8u)) & 0xffu;
-    }
-};
-
-// one cursor step of either pass with dense symbol c >= 1
-template <class Table, int kGroup, bool kPair>
-__device__ __forceinline__ void smems_step(const IndexView &ix, const uint32_t *s_count, uint32_t c, uint32_t lo, uint32_t hi,
-                                           uint32_t &nlo, uint32_t &nhi)
-{
-    if (kPair && c <= 4u) {
-        PairTable::lf1<0, kGroup>(ix, c, lo, hi, nlo, nhi);
-    } else {
-        Table::rank2(ix, c, lo, hi, nlo, nhi);
-        const uint32_t cc = s_count[c];
-        nlo += cc;
-        nhi += cc;
-    }
-}
-
-// The top-table entry of a pass: its first `depth` symbols sit at first[0], first[dir], first[2 dir], ... (first consumed
-// symbol in the highest bits, as top_lookup takes them).  False, lo / hi untouched: a symbol outside 1..4 or a D-mer that
-// does not occur -- the pass then runs step by step from its start.
-__device__ __forceinline__ bool smems_top(const IndexView &ix, uint32_t depth, const uint8_t *s_dense, const uint8_t *first, int dir,
-                                          uint32_t &lo, uint32_t &hi)
-{
-    uint32_t a = 0, b = 0;
-    for (uint32_t s = 0; s < depth; s++) {
-        const uint32_t c = s_dense[first[static_cast<int64_t>(dir) * static_cast<int64_t>(s)]];
-        if (s < 8u) a |= c << (4u * (7u - s));
-        else b |= c << (4u * (15u - s));
-    }
-    uint32_t tlo, thi;
-    if (!top_lookup(ix, a, b, tlo, thi) || tlo == thi) return false;
-    lo = tlo;
-    hi = thi;
-    return true;
-}
-
-// Like the segments kernel this one lives on reads in flight (a dependent, latency-bound fetch chain per read).  Waves per
-// SIMD from the registers the compiler reports (-Rpass-analysis=kernel-resource-usage, gfx950): pair lines 77 VGPRs and
-// one lane per read on rank lines 75 VGPRs = 6 waves; four lanes on rank lines 57 and the generic table 61: 7 asked for,
-// 8 reported; no scratch in any instance (profiles/r09/smems.md).
-template <class Table, int kGroup, bool kPair>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((kPair || std::is_same<Table, LineTable>::value) ? 6 : 7))) void smems_kernel(
-    IndexView fx, IndexView rx, const uint8_t *__restrict__ qbuf, const uint64_t *__restrict__ qoff, uint64_t nq,
-    uint32_t max_smems, uint32_t min_length, SmemsOut out)
-{
-    __shared__ uint8_t s_dense[256];
-    __shared__ uint32_t s_count[257];
-    for (int i = threadIdx.x; i < 256; i += kBlock) s_dense[i] = fx.io_to_dense[i];
-    for (int i = threadIdx.x; i <= fx.sigma; i += kBlock) s_count[i] = fx.count[i];
-    __syncthreads();
-
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * (kBlock / kGroup);
-    const bool writer = (threadIdx.x % kGroup) == 0;
-    const uint32_t fdepth = (fx.top != nullptr && fx.layout == 0) ? fx.top_depth : 0u;
-    const uint32_t rdepth = (rx.top != nullptr && rx.layout == 0) ? rx.top_depth : 0u;
-    for (uint64_t q = static_cast<uint64_t>(blockIdx.x) * (kBlock / kGroup) + threadIdx.x / kGroup; q < nq; q += stride) {
-        const uint64_t begin = qoff[q];
-        const uint32_t m = static_cast<uint32_t>(qoff[q + 1] - begin);
-        const uint64_t slot0 = q * max_smems;
-        uint32_t pe = m, n_smems = 0, status = GDX_Q_OK;  // pe = p + 1: the walk stands at p, 0 = it is through
-        while (pe > 0u && n_smems < max_smems) {
-            const uint32_t p = pe - 1u;
-            // forward pass on rx: the longest e with q[p, e) occurring
-            uint32_t lo = 0, hi = rx.n, e = p;
-            if (rdepth != 0u && m - p >= rdepth && smems_top(rx, rdepth, s_dense, qbuf + begin + p, 1, lo, hi)) e = p + rdepth;
-            if (e < m) {
-                ForwardQueryWindow win;
-                win.init(qbuf, begin + e, begin + m);
-                while (e < m) {
-                    const uint32_t c = s_dense[win.get(begin + e)];
-                    if (c == 0u) {  // also as the symbol that blocks: translation comes before anything else
-                        status = GDX_Q_INVALID_SYMBOL;
-                        break;
-                    }
-                    if (lo == hi) break;  // (an index without rows: nothing occurs)
-                    uint32_t nlo, nhi;
-                    smems_step<Table, kGroup, kPair>(rx, s_count, c, lo, hi, nlo, nhi);
-                    if (nlo == nhi) break;
-                    lo = nlo;
-                    hi = nhi;
-                    e++;
-                }
-            }
-            if (status != GDX_Q_OK) break;
-            if (e == p) {  // q[p] occurs nowhere: no SMEM covers p
-                pe = p;
-                continue;
-            }
-            // backward pass on fx: the longest match that ends at e, with the interval from before the step that emptied it
-            uint32_t len = 0;
-            lo = 0;
-            hi = fx.n;
-            if (fdepth != 0u && e >= fdepth && smems_top(fx, fdepth, s_dense, qbuf + begin + e - 1u, -1, lo, hi)) len = fdepth;
-            QueryWindow win;
-            win.init(qbuf, begin, begin + (e - len));
-            while (len < e) {
-                const uint32_t c = s_dense[win.get(begin + (e - len) - 1u)];
-                if (c == 0u) {
-                    status = GDX_Q_INVALID_SYMBOL;
-                    break;
-                }
-                if (lo == hi) break;
-                uint32_t nlo, nhi;
-                smems_step<Table, kGroup, kPair>(fx, s_count, c, lo, hi, nlo, nhi);
-                if (nlo == nhi) break;
-                lo = nlo;
-                hi = nhi;
-                len++;
-            }
-            if (status != GDX_Q_OK) break;
-            const uint32_t s = e - len;
-            if (len >= min_length) {
-                if (writer) {
-                    out.begin[slot0 + n_smems] = s;
-                    out.length[slot0 + n_smems] = len;
-                    out.start[slot0 + n_smems] = lo;
-                    out.end[slot0 + n_smems] = hi;
-                }
-                n_smems++;
-            }
-            // s <= p when rx indexes the reversed texts of fx; with a companion built from other texts (the host cannot
-            // tell) the walk must still move left
-            pe = s < p ? s : p;
-        }
-        if (status != GDX_Q_OK) {
-            n_smems = 0;
-            pe = m;
-        }
-        if (writer) {
-            for (uint32_t j = n_smems; j < max_smems; j++) {
-                out.begin[slot0 + j] = 0u;
-                out.length[slot0 + j] = 0u;
-                out.start[slot0 + j] = 0u;
-                out.end[slot0 + j] = 0u;
-            }
-            out.n_smems[q] = n_smems;
-            out.remaining[q] = pe;
-            if (out.status != nullptr) out.status[q] = static_cast<uint8_t>(status);
-        }
-    }
-}
-
-template <class Table>
-__global__ __launch_bounds__(kBlock) void rank_many_kernel(IndexView ix, const uint8_t *__restrict__ symbols,
-                                                           const uint32_t *__restrict__ idx, uint64_t m,
-                                                           uint32_t *__restrict__ out, uint32_t *error)
-{
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < m; i += stride) {
-        const uint32_t c = symbols[i], p = idx[i];
-        if (c >= static_cast<uint32_t>(ix.sigma) || p > ix.n) {  // mod.rs:107-108
-            *error = 1;
-            out[i] = 0;
-            continue;
-        }
-        out[i] = Table::rank(ix, c, p);
-    }
-}
-
-template <class Table>
-__global__ __launch_bounds__(kBlock) void symbol_at_kernel(IndexView ix, const uint32_t *__restrict__ idx,
-                                                           uint64_t m, uint8_t *__restrict__ out, uint32_t *error)
-{
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < m; i += stride) {
-        const uint32_t p = idx[i];
-        if (p >= ix.n) {  // condensed.rs:344
-            *error = 1;
-            out[i] = 0;
-            continue;
-        }
-        out[i] = static_cast<uint8_t>(Table::symbol_at(ix, p));
-    }
-}
-
-// gdx_bench_lf_walk_dev: the text read backwards through the occurrence table alone (symbol_at + rank + count, i.e.
-// sampled_suffix_array.rs:118-131 without the samples)
-template <class Table>
-__global__ __launch_bounds__(kBlock) void lf_walk_kernel(IndexView ix, const uint32_t *__restrict__ rows, uint64_t m,
-                                                         uint32_t steps, uint8_t *__restrict__ symbols,
-                                                         uint32_t *__restrict__ end_rows)
-{
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < m; i += stride) {
-        uint32_t row = rows[i];
-        uint8_t *out = symbols + i * steps;
-        uint32_t j = 0;
-        for (; j < steps && row < ix.n; j++) {
-            uint32_t r;
-            const uint32_t c = Table::symbol_and_rank(ix, row, r);
-            out[j] = static_cast<uint8_t>(c);
-            if (c == 0) {
-                j++;
-                break;
-            }
-            row = ix.count[c] + r;
-        }
-        for (; j < steps; j++) out[j] = 0xffu;
-        if (end_rows) end_rows[i] = row;
-    }
-}
-
-// lookup_table.rs:163-258: table[depth][idx] = interval of the depth-mer whose j-th symbol is digit j
-// of idx in base k (+1 to skip the sentinel).  Plain backward search with freeze-on-empty gives the
-// same (start, end) as the reference's recursive fill through the smaller tables.
-template <class Table>
-__global__ __launch_bounds__(kBlock) void fill_lookup_kernel(IndexView ix, uint2 *__restrict__ lookup, int depth,
-                                                             uint64_t entries)
-{
-    const uint32_t k = static_cast<uint32_t>(ix.n_searchable);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    const uint64_t first = lookup_offset(k, static_cast<uint32_t>(depth));
-    for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; e < entries; e += stride) {
-        uint64_t pw = 1;
-        for (int j = 1; j < depth; j++) pw *= k;  // k^(depth-1)
-        uint32_t lo = 0, hi = ix.n;
-        for (int j = depth - 1; j >= 0 && lo != hi; j--) {
-            const uint32_t c = static_cast<uint32_t>((e / pw) % k) + 1u;
-            uint32_t rlo, rhi;
-            Table::rank2(ix, c, lo, hi, rlo, rhi);
-            const uint32_t cc = ix.count[c];
-            lo = cc + rlo;
-            hi = cc + rhi;
-            pw /= k;
-        }
-        lookup[first + e] = make_uint2(lo, hi);
-    }
-}
-
-// top[idx]: idx holds the 2-bit codes (dense - 1) of the D symbols in consumption order, first consumed symbol in
-// the highest bit pair (top_lookup builds the same index from the query's nibble codes).  Plain backward search
-// with freeze-on-empty, exactly fill_lookup_kernel's.
-__global__ __launch_bounds__(kBlock) void fill_top_kernel(IndexView ix, uint2 *__restrict__ top, uint32_t depth,
-                                                          uint64_t entries)
-{
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; e < entries; e += stride) {
-        uint32_t lo = 0, hi = ix.n;
-        for (uint32_t s = 0; s < depth && lo != hi; s++) {
-            const uint32_t c = (static_cast<uint32_t>(e >> (2u * (depth - 1u - s))) & 3u) + 1u;
-            uint32_t rlo, rhi;
-            LineTable::rank2(ix, c, lo, hi, rlo, rhi);
-            const uint32_t cc = ix.count[c];
-            lo = cc + rlo;
-            hi = cc + rhi;
-        }
-        top[e] = make_uint2(lo, hi);  // an empty interval stays as it was when it emptied (the loop stopped there)
-    }
-}
-
 }  // namespace
-
-#define GDX_DISPATCH_TABLE(ix, KERNEL, grid, stream, ...)                                        \
-    do {                                                                                         \
-        if ((ix).layout == 0)                                                                    \
-            hipLaunchKernelGGL(KERNEL<LineTable>, dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); \
-        else                                                                                     \
-            hipLaunchKernelGGL(KERNEL<GenericTable>, dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); \
-    } while (0)
-
-static unsigned grid_for_items(uint64_t items)
-{
-    const uint64_t blocks = (items + kBlock - 1) / kBlock;
-    const uint64_t cap = 256u * 8u;  // 8 blocks of 256 threads per CU
-    return static_cast<unsigned>(blocks < 1 ? 1 : (blocks < cap ? blocks : cap));
-}
 
 // Kernel used on rank lines: 2 = pair lines when the index has them (default), 0 = quad, 1 = one lane
 // per query.  Settable through GDX_SEARCH_VARIANT=pair|quad|lane or gdx_debug_set_search_variant()
@@ -4004,7 +2984,7 @@ static std::atomic<int> g_search_variant{-1};
 
 void set_search_variant(int v) { g_search_variant.store(v); }
 
-static int search_variant()
+int search_variant()
 {
     int v = g_search_variant.load();
     if (v >= 0) return v;
@@ -4066,10 +3046,6 @@ __global__ __launch_bounds__(kBlock) void fill_uniform_offsets_kernel(uint64_t *
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) off[i] = i * ulen;
 }
 
-// The tile sums of a locate that the seed table's lane kernel began (SearchCall::d_tile_sums): the reads on its two lists,
-// once every kernel of the call has written their results.  left: everything listed for the next kernels (compact result
-// "see the record": the record's count, also into *rest); long: reads finished by seed_text_kernel4 (those it handed on
-// are on the left list as well, and counted there).
 // the same for the queries of a list only (its length is a device value): off[q], off[q + 1] -- what the offset-reading
 // kernels behind the seed chain need of a uniform batch, instead of 8 bytes per query of the whole batch
 __global__ __launch_bounds__(kBlock) void fill_uniform_offsets_list_kernel(uint64_t *__restrict__ off, const uint32_t *__restrict__ list,
@@ -4083,6 +3059,10 @@ __global__ __launch_bounds__(kBlock) void fill_uniform_offsets_list_kernel(uint6
     }
 }
 
+// The tile sums of a locate that the seed table's lane kernel began (SearchCall::d_tile_sums): the reads on its two lists,
+// once every kernel of the call has written their results.  left: everything listed for the next kernels (compact result
+// "see the record": the record's count, also into *rest); long: reads finished by seed_text_kernel4 (those it handed on
+// are on the left list as well, and counted there).
 __global__ __launch_bounds__(kBlock) void tile_sums_lists_kernel(const uint4 *__restrict__ rec, const uint32_t *__restrict__ compact,
                                                                  uint32_t max_hits, const uint32_t *__restrict__ left,
                                                                  const uint32_t *__restrict__ n_left, const uint32_t *__restrict__ lng,
@@ -4737,165 +3717,6 @@ void launch_search_call(const IndexView &ix, const SearchCall &call, hipStream_t
         else l.launch_plain<GenericTable, 1>(grid_for_items(l.nq));
     }
     l.finish_fold();  // (e)
-}
-
-// ASCII -> 2-bit: packed byte b holds the codes of bytes 4 b .. 4 b + 3 of the query buffer; *bad_symbols counts the
-// symbols that are not one of the dense codes 1..4 (their code is written as 0), bad_flags (optional, one byte per
-// 64 symbols) marks where they are so that the caller can find the queries they belong to
-__global__ __launch_bounds__(kBlock) void pack_queries_kernel(const uint8_t *__restrict__ io_to_dense,
-                                                              const uint8_t *__restrict__ qbuf, uint64_t n_symbols,
-                                                              uint8_t *__restrict__ packed, uint8_t *__restrict__ bad_flags,
-                                                              unsigned long long *__restrict__ bad_symbols)
-{
-    __shared__ uint8_t s_dense[256];
-    for (int i = threadIdx.x; i < 256; i += kBlock) s_dense[i] = io_to_dense[i];
-    __syncthreads();
-    const uint64_t n_bytes = (n_symbols + 3) / 4;
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    uint32_t bad = 0;
-    for (uint64_t b = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; b < n_bytes; b += stride) {
-        uint32_t out = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) {
-            const uint64_t j = 4 * b + k;
-            if (j < n_symbols) {
-                const uint32_t d = s_dense[qbuf[j]];
-                if (d - 1u < 4u) {
-                    out |= (d - 1u) << (2u * k);
-                } else {
-                    bad++;
-                    if (bad_flags) bad_flags[j >> 6] = 1;
-                }
-            }
-        }
-        packed[b] = static_cast<uint8_t>(out);
-    }
-    if (bad && bad_symbols) atomicAdd(bad_symbols, static_cast<unsigned long long>(bad));
-}
-
-void launch_pack_queries(const IndexView &ix, const uint8_t *d_qbuf, uint64_t n_symbols, uint8_t *d_packed,
-                         uint8_t *d_bad_flags, unsigned long long *d_bad_symbols, hipStream_t stream)
-{
-    if (n_symbols == 0) return;
-    hipLaunchKernelGGL(pack_queries_kernel, dim3(grid_for_items((n_symbols + 3) / 4)), dim3(kBlock), 0, stream,
-                       ix.io_to_dense, d_qbuf, n_symbols, d_packed, d_bad_flags, d_bad_symbols);
-}
-
-void launch_extend_front(const IndexView &ix, uint32_t *d_start, uint32_t *d_end, const uint8_t *d_io_symbols,
-                         uint64_t m, uint8_t *d_out_status, hipStream_t stream)
-{
-    if (m == 0) return;
-    if (ix.layout == 0 && ix.pair_lines != nullptr) {
-        hipLaunchKernelGGL((extend_front_kernel<QuadLineTable, 8, true>), dim3(grid_for_items(m * 8)), dim3(kBlock), 0,
-                           stream, ix, d_start, d_end, d_io_symbols, m, d_out_status);
-    } else if (ix.layout == 0) {
-        hipLaunchKernelGGL((extend_front_kernel<QuadLineTable, 4, false>), dim3(grid_for_items(m * 4)), dim3(kBlock), 0,
-                           stream, ix, d_start, d_end, d_io_symbols, m, d_out_status);
-    } else {
-        hipLaunchKernelGGL((extend_front_kernel<GenericTable, 1, false>), dim3(grid_for_items(m)), dim3(kBlock), 0,
-                           stream, ix, d_start, d_end, d_io_symbols, m, d_out_status);
-    }
-}
-
-void launch_suffix_segments(const IndexView &ix, const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq,
-                            uint32_t max_segments, bool lf_only, uint32_t *d_n_segments, uint32_t *d_remaining,
-                            uint32_t *d_length, uint32_t *d_start, uint32_t *d_end, uint8_t *d_status, hipStream_t stream,
-                            const QueryOptions &qo)
-{
-    if (nq == 0) return;
-    const int variant = qo.search_variant >= 0 ? qo.search_variant : search_variant();
-    const bool text = !lf_only && ix.text_units != nullptr && ix.sa_full != nullptr && ix.isa != nullptr;
-    const SegmentsOut out = {d_n_segments, d_remaining, d_length, d_start, d_end, d_status};
-#define GDX_SEGMENTS_LAUNCH(TABLE, GROUP, PAIR)                                                                          \
-    do {                                                                                                                 \
-        if (text)                                                                                                        \
-            hipLaunchKernelGGL((suffix_segments_kernel<TABLE, GROUP, PAIR, true>), dim3(grid_for_items(nq * GROUP)),     \
-                               dim3(kBlock), 0, stream, ix, d_qbuf, d_qoff, nq, max_segments, out);                      \
-        else                                                                                                             \
-            hipLaunchKernelGGL((suffix_segments_kernel<TABLE, GROUP, PAIR, false>), dim3(grid_for_items(nq * GROUP)),    \
-                               dim3(kBlock), 0, stream, ix, d_qbuf, d_qoff, nq, max_segments, out);                      \
-    } while (0)
-    if (ix.layout == 0 && variant == 2 && ix.pair_lines != nullptr) GDX_SEGMENTS_LAUNCH(QuadLineTable, 4, true);
-    else if (ix.layout == 0 && variant != 1) GDX_SEGMENTS_LAUNCH(QuadLineTable, 4, false);
-    else if (ix.layout == 0) GDX_SEGMENTS_LAUNCH(LineTable, 1, false);
-    else GDX_SEGMENTS_LAUNCH(GenericTable, 1, false);
-#undef GDX_SEGMENTS_LAUNCH
-}
-
-void launch_smems(const IndexView &fx, const IndexView &rx, const uint8_t *d_qbuf, const uint64_t *d_qoff, uint64_t nq,
-                  uint32_t max_smems, uint32_t min_length, uint32_t *d_n_smems, uint32_t *d_remaining, uint32_t *d_begin,
-                  uint32_t *d_length, uint32_t *d_start, uint32_t *d_end, uint8_t *d_status, hipStream_t stream,
-                  const QueryOptions &qo)
-{
-    if (nq == 0) return;
-    const int variant = qo.search_variant >= 0 ? qo.search_variant : search_variant();
-    const SmemsOut out = {d_n_smems, d_remaining, d_begin, d_length, d_start, d_end, d_status};
-#define GDX_SMEMS_LAUNCH(TABLE, GROUP, PAIR)                                                                                  \
-    hipLaunchKernelGGL((smems_kernel<TABLE, GROUP, PAIR>), dim3(grid_for_items(nq * GROUP)), dim3(kBlock), 0, stream, fx, rx, \
-                       d_qbuf, d_qoff, nq, max_smems, min_length, out)
-    // (the callers have checked that both views have the same table layout)
-    if (fx.layout == 0 && variant == 2 && fx.pair_lines != nullptr && rx.pair_lines != nullptr) GDX_SMEMS_LAUNCH(QuadLineTable, 4, true);
-    else if (fx.layout == 0 && variant != 1) GDX_SMEMS_LAUNCH(QuadLineTable, 4, false);
-    else if (fx.layout == 0) GDX_SMEMS_LAUNCH(LineTable, 1, false);
-    else GDX_SMEMS_LAUNCH(GenericTable, 1, false);
-#undef GDX_SMEMS_LAUNCH
-}
-
-void launch_rank_many(const IndexView &ix, const uint8_t *d_symbols, const uint32_t *d_idx, uint64_t m,
-                      uint32_t *d_out, uint32_t *d_error, hipStream_t stream)
-{
-    if (m == 0) return;
-    GDX_DISPATCH_TABLE(ix, rank_many_kernel, grid_for_items(m), stream, ix, d_symbols, d_idx, m, d_out, d_error);
-}
-
-void launch_symbol_at_many(const IndexView &ix, const uint32_t *d_idx, uint64_t m, uint8_t *d_out,
-                           uint32_t *d_error, hipStream_t stream)
-{
-    if (m == 0) return;
-    GDX_DISPATCH_TABLE(ix, symbol_at_kernel, grid_for_items(m), stream, ix, d_idx, m, d_out, d_error);
-}
-
-void launch_lf_walk(const IndexView &ix, const uint32_t *d_rows, uint64_t m, uint32_t steps, uint8_t *d_symbols,
-                    uint32_t *d_end_rows, hipStream_t stream)
-{
-    if (m == 0 || steps == 0) return;
-    GDX_DISPATCH_TABLE(ix, lf_walk_kernel, grid_for_items(m), stream, ix, d_rows, m, steps, d_symbols, d_end_rows);
-}
-
-void launch_fill_lookup(const IndexView &ix, uint2 *d_lookup, int depth, hipStream_t stream)
-{
-    uint64_t entries = 1;
-    for (int j = 0; j < depth; j++) entries *= static_cast<uint64_t>(ix.n_searchable);
-    GDX_DISPATCH_TABLE(ix, fill_lookup_kernel, grid_for_items(entries), stream, ix, d_lookup, depth, entries);
-}
-
-// sum of the interval widths of the top-table entries wider than `rows` rows = the number of text positions whose
-// D-mer stays wider than a jump can take after the top table (a measure of how repetitive the text is)
-__global__ __launch_bounds__(kBlock) void top_wide_kernel(const uint2 *__restrict__ top, uint64_t entries, uint32_t rows,
-                                                          unsigned long long *__restrict__ sum)
-{
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    unsigned long long mine = 0;
-    for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; e < entries; e += stride) {
-        const uint2 v = top[e];
-        const uint32_t w = v.y - v.x;
-        if (w > rows) mine += w;
-    }
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
-    if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(sum, mine);
-}
-
-void launch_top_wide(const uint2 *d_top, uint32_t depth, uint32_t rows, unsigned long long *d_sum, hipStream_t stream)
-{
-    const uint64_t entries = 1ull << (2u * depth);
-    hipLaunchKernelGGL(top_wide_kernel, dim3(grid_for_items(entries)), dim3(kBlock), 0, stream, d_top, entries, rows, d_sum);
-}
-
-void launch_fill_top(const IndexView &ix, uint2 *d_top, uint32_t depth, hipStream_t stream)
-{
-    const uint64_t entries = 1ull << (2u * depth);
-    hipLaunchKernelGGL(fill_top_kernel, dim3(grid_for_items(entries)), dim3(kBlock), 0, stream, ix, d_top, depth,
-                       entries);
 }
 
 }  // namespace gdx

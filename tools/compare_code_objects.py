@@ -3,7 +3,8 @@
 .group_segment_fixed_size, .private_segment_fixed_size from the AMDGPU metadata note) and the disassembly of every kernel,
 symbol by symbol (the order in which a compiler emits them may differ).  Prints one line per differing name and the totals;
 exit status 1 when anything differs.  Several B files stand for one translation unit split into these: every name must be in
-exactly one of them.
+exactly one of them.  The `s_nop 0` padding behind a symbol's last instruction (alignment in front of the
+next symbol, the fill at the end of .text) is not compared: it depends on what stands behind a kernel in its unit.
 
 usage: python tools/compare_code_objects.py A.co B.co [B2.co ...]
 A code object comes out of a device-only compile in two steps:
@@ -62,6 +63,11 @@ def disassembly(path):
             cur = res.setdefault(m.group(1), [])
         elif cur is not None and line.strip() and line.strip() != "...":  # ("...": the zero padding behind a symbol)
             cur.append(re.sub(r"\s*//.*$", "", line.strip()))
+    # s_nop 0 behind a symbol's last instruction is padding: alignment in front of the next symbol, or the fill at the end of
+    # .text; which of the two a kernel gets, and how much, depends on what stands behind it in the unit, not on the kernel
+    for insns in res.values():
+        while insns and insns[-1] == "s_nop 0":
+            insns.pop()
     return res
 
 
