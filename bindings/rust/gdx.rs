@@ -158,6 +158,11 @@ pub const GDX_SAM_SINGLE: u32 = 0;
 pub const GDX_SAM_PAIRED: u32 = 1;
 pub const GDX_SAM_BAD_RECORD: u8 = 1;
 pub const GDX_SAM_MAX_RUN_SUM: u32 = 1 << 24;
+pub const GDX_CIGAR_SOFT_CLIP: u32 = 4;
+pub const GDX_CLIP_NO_SCORE: u32 = 0x8000_0000;
+pub const GDX_CLIP_BAD_CIGAR: u8 = 1;
+pub const GDX_CLIP_MAX_RUN_SUM: u32 = 65536;
+pub const GDX_CLIP_MAX_SCORE_PARAM: u32 = 1024;
 
 /// gdx_query_layout_t
 #[repr(C)]
@@ -429,6 +434,22 @@ extern "C" {
     pub fn gdx_sam_record_bound(max_read_len: u64, max_name_len: u64, max_text_name_len: u64, max_edits: u32) -> u64;
     pub fn gdx_sam_records_many_dev(ix: *const gdx_index_t, input: *const SamInputs, stream: *mut c_void) -> c_int;
     pub fn gdx_sam_records_many(ix: *const gdx_index_t, input: *const SamInputs) -> c_int;
+    /// Soft clipping (include/gdx_experimental.h "soft clipping"): per candidate of gdx_align_many the best-scoring contiguous
+    /// part of its runs under match / mismatch / gap_open / gap_extend, S runs (op 4) around it, begin and end moved inwards,
+    /// the edits that stay and the score (i32; 0x80000000 for a candidate without an alignment); `out_status` may be null
+    pub fn gdx_soft_clip_many_dev(
+        ix: *const gdx_index_t, m: u64, max_edits: u32, r#match: u32, mismatch: u32, gap_open: u32, gap_extend: u32, min_score: u32,
+        d_dist: *const c_void, d_begin: *const c_void, d_end: *const c_void, d_n_cigar: *const c_void, d_cigar: *const c_void,
+        d_out_score: *mut c_void, d_out_dist: *mut c_void, d_out_begin: *mut c_void, d_out_end: *mut c_void,
+        d_out_clip_left: *mut c_void, d_out_clip_right: *mut c_void, d_out_n_cigar: *mut c_void, d_out_cigar: *mut c_void,
+        d_out_status: *mut c_void, stream: *mut c_void,
+    ) -> c_int;
+    pub fn gdx_soft_clip_many(
+        ix: *const gdx_index_t, m: u64, max_edits: u32, r#match: u32, mismatch: u32, gap_open: u32, gap_extend: u32, min_score: u32,
+        dist: *const u32, begin: *const u32, end: *const u32, n_cigar: *const u32, cigar: *const u32, out_score: *mut i32,
+        out_dist: *mut u32, out_begin: *mut u32, out_end: *mut u32, out_clip_left: *mut u32, out_clip_right: *mut u32,
+        out_n_cigar: *mut u32, out_cigar: *mut u32, out_status: *mut u8,
+    ) -> c_int;
     pub fn gdx_rank_many(
         ix: *const gdx_index_t, symbols: *const u8, idx: *const u64, m: u64, out: *mut u64,
     ) -> c_int;

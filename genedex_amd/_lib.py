@@ -55,6 +55,11 @@ GDX_SAM_SINGLE = 0                # gdx_sam_records_many[_dev]: mode
 GDX_SAM_PAIRED = 1
 GDX_SAM_BAD_RECORD = 1            # status of a read whose winner cannot be a record (written as unmapped)
 GDX_SAM_MAX_RUN_SUM = 1 << 24     # the run lengths of one CIGAR sum to at most this
+GDX_CIGAR_SOFT_CLIP = 4           # gdx_soft_clip_many[_dev]: the op of the S runs it adds
+GDX_CLIP_NO_SCORE = -0x80000000   # score (i32) of a candidate that had no alignment to clip: the pattern 0x80000000
+GDX_CLIP_BAD_CIGAR = 1            # status of a candidate whose runs fail the check
+GDX_CLIP_MAX_RUN_SUM = 65536      # the run lengths of one candidate sum to at most this
+GDX_CLIP_MAX_SCORE_PARAM = 1024   # match, mismatch, gap_open, gap_extend at most
 GDX_Q_OK = 0
 GDX_Q_INVALID_SYMBOL = 1
 GDX_Q_UNSEARCHABLE_IN_LOOKUP = 2
@@ -296,6 +301,11 @@ SIGNATURES = {
     "gdx_sam_record_bound": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32],
     "gdx_sam_records_many_dev": [vp, C.POINTER(SamInputs), vp],
     "gdx_sam_records_many": [vp, C.POINTER(SamInputs)],
+    "gdx_soft_clip_many_dev": [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp,
+                               vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "gdx_soft_clip_many": [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p,
+                           u32p, C.POINTER(C.c_int32), u32p, u32p, u32p, u32p, u32p, u32p, u32p, u8p],
+    "gdx_debug_set_clip_grid": [C.c_uint32],
     # gdx_bench.h
     "gdx_index_build_stats": [vp, C.POINTER(BuildStats)],
     "gdx_synth_text_dev": [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp],

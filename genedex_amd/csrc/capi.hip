@@ -1914,6 +1914,40 @@ int gdx_sam_records_many(const gdx_index_t *ix, const gdx_sam_inputs_t *in)
     });
 }
 
+// ---- soft clipping (soft_clip.hip) ------------------------------------------------------------------------------
+
+int gdx_soft_clip_many_dev(const gdx_index_t *ix, uint64_t m, uint32_t max_edits, uint32_t match, uint32_t mismatch, uint32_t gap_open,
+                           uint32_t gap_extend, uint32_t min_score, const void *d_dist, const void *d_begin, const void *d_end,
+                           const void *d_n_cigar, const void *d_cigar, void *d_out_score, void *d_out_dist, void *d_out_begin,
+                           void *d_out_end, void *d_out_clip_left, void *d_out_clip_right, void *d_out_n_cigar, void *d_out_cigar,
+                           void *d_out_status, void *stream)
+{
+    return device_call(ix, stream, [&](DeviceCall &d) {
+        const gdx::ClipArgs a = {m, max_edits, match, mismatch, gap_open, gap_extend, min_score, u32(d_dist), u32(d_begin), u32(d_end),
+                                 u32(d_n_cigar), u32(d_cigar), static_cast<int32_t *>(d_out_score), u32(d_out_dist), u32(d_out_begin),
+                                 u32(d_out_end), u32(d_out_clip_left), u32(d_out_clip_right), u32(d_out_n_cigar), u32(d_out_cigar),
+                                 static_cast<uint8_t *>(d_out_status)};
+        gdx::check_soft_clip(a);
+        if (m == 0) return;
+        d.enter();
+        gdx::launch_soft_clip(a, d.st);
+    });
+}
+
+int gdx_soft_clip_many(const gdx_index_t *ix, uint64_t m, uint32_t max_edits, uint32_t match, uint32_t mismatch, uint32_t gap_open,
+                       uint32_t gap_extend, uint32_t min_score, const uint32_t *dist, const uint32_t *begin, const uint32_t *end,
+                       const uint32_t *n_cigar, const uint32_t *cigar, int32_t *out_score, uint32_t *out_dist, uint32_t *out_begin,
+                       uint32_t *out_end, uint32_t *out_clip_left, uint32_t *out_clip_right, uint32_t *out_n_cigar, uint32_t *out_cigar,
+                       uint8_t *out_status)
+{
+    return guarded([&] {
+        const gdx::ClipArgs a = {m, max_edits, match, mismatch, gap_open, gap_extend, min_score, dist, begin, end, n_cigar, cigar,
+                                 out_score, out_dist, out_begin, out_end, out_clip_left, out_clip_right, out_n_cigar, out_cigar,
+                                 out_status};
+        return gdx::soft_clip_host(deref(ix), a);
+    });
+}
+
 int gdx_rank_many_dev(const gdx_index_t *ix, const void *d_symbols, const void *d_idx, uint64_t m, void *d_out,
                       void *d_error, void *stream)
 {
@@ -2026,6 +2060,12 @@ int gdx_debug_set_rescue_tiling(uint64_t tile_pairs, uint64_t grid)
 int gdx_debug_set_sam_tiling(uint32_t tile_bytes, uint32_t grid)
 {
     gdx::set_sam_tiling(tile_bytes, grid);
+    return GDX_OK;
+}
+
+int gdx_debug_set_clip_grid(uint32_t grid)
+{
+    gdx::set_clip_grid(grid);
     return GDX_OK;
 }
 

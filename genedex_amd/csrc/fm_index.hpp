@@ -246,6 +246,10 @@ void sam_records_dev(const FmIndex &f, const gdx_sam_inputs_t *in, bool packed, 
 // host form: staged like align_many -- copy in, a sizing pass, the records that fit, copy out
 int sam_records_host(const FmIndex &f, const gdx_sam_inputs_t *in);
 
+// ---- soft_clip.hip: the host form of gdx_soft_clip_many, staged like best_hits_many (copy in, one launch, copy out); `host`
+// holds host pointers.  The output rows travel both ways, so that the words from out_n_cigar on stay the caller's
+int soft_clip_host(const FmIndex &f, const ClipArgs &host);
+
 // ---- multi.hip: replicas on several devices behind one handle (gdx_multi_*) ---------------------------------
 // One long-lived worker thread per replica: the host-pointer pipeline keeps its pinned staging and device buffers in
 // per-thread caches (host_api.hip), so the threads have to outlive the calls.

@@ -289,6 +289,25 @@ void launch_sam_records(const IndexView &ix, const SamCall &call, hipStream_t st
 // tests and experiments (gdx_debug_set_sam_tiling): tile bytes and workgroups of the fills to come, 0 = the launcher's choice
 void set_sam_tiling(uint32_t tile_bytes, uint32_t grid);
 
+// ---- soft_clip.hip ------------------------------------------------------------------------
+// gdx_soft_clip_many_dev: m candidates with launch_align's five outputs (cigar rows of stride 2 max_edits + 1) -> per candidate
+// the best-scoring contiguous part of the runs with S runs around it, its score, edit count, text range and the two clip
+// lengths; the words of an output row from out_n_cigar on are untouched.  check_soft_clip is what both forms refuse: max_edits
+// > 256, a scoring parameter out of range, with m != 0 a null pointer (out_status may be null).  One launch.
+struct ClipArgs {
+    uint64_t m;
+    uint32_t max_edits, match, mismatch, gap_open, gap_extend, min_score;
+    const uint32_t *dist, *begin, *end, *n_cigar;  // u32[m]
+    const uint32_t *cigar;                         // u32[m * (2 max_edits + 1)]
+    int32_t *out_score;
+    uint32_t *out_dist, *out_begin, *out_end, *out_clip_left, *out_clip_right, *out_n_cigar, *out_cigar;
+    uint8_t *out_status;  // or null
+};
+void check_soft_clip(const ClipArgs &a);
+void launch_soft_clip(const ClipArgs &a, hipStream_t stream);
+// tests and experiments (gdx_debug_set_clip_grid): at most this many workgroups in the launches to come, 0 = the launcher's choice
+void set_clip_grid(uint32_t grid);
+
 // ---- locate.hip ---------------------------------------------------------------------------
 size_t hit_offsets_temp_bytes(uint64_t m);
 void launch_hit_offsets(const uint32_t *d_start, const uint32_t *d_end, uint64_t m, uint64_t *d_hit_offsets,

@@ -569,6 +569,45 @@ class DeviceEngine:
                                                None, _stream()))
         return out
 
+    # ---- soft clipping (gdx_soft_clip_many_dev) -----------------------------------------------------------------
+    def soft_clip(self, aligned: dict, max_edits: int, scoring, out: dict = None):
+        """One launch: per candidate of align() the best-scoring contiguous part of its runs, S runs (op 4) in place of what lies
+        outside, begin and end moved inwards.  aligned: the dict of align() as it is; scoring = (match, mismatch, gap_open,
+        gap_extend) or with min_score as a fifth.  -> {"score", "dist", "begin", "end", "clip_left", "clip_right", "n_cigar":
+        int32[m], "cigar": int32[m, 2 max_edits + 1], "status": uint8[m]} (tensors of `out` are used where given, the others
+        made here; the words of a cigar row from n_cigar on are not written).  score is signed: the best score, GDX_CLIP_NO_SCORE
+        for a candidate without an alignment.  A candidate whose best score is below max(1, min_score) is clipped away and looks
+        like an unmapped one: end -1, n_cigar 0, dist max_edits + 1.  status 1 (GDX_CLIP_BAD_CIGAR): runs that fail the check."""
+        match, mismatch, gap_open, gap_extend, *rest = (int(x) for x in scoring)
+        min_score = rest[0] if rest else 0
+        m, stride = int(aligned["dist"].numel()), 2 * int(max_edits) + 1
+        if any(aligned[name].numel() != m for name in ("begin", "end", "n_cigar")) or aligned["cigar"].numel() != m * stride:
+            raise ValueError("aligned holds the outputs of align() with this max_edits")
+        if not all(aligned[name].is_contiguous() for name in ("dist", "begin", "end", "n_cigar", "cigar")):
+            raise ValueError("the tensors of aligned are contiguous")
+        out = dict(out) if out else {}
+        for name in ("score", "dist", "begin", "end", "clip_left", "clip_right", "n_cigar"):
+            if out.get(name) is None:
+                out[name] = torch.empty(m, dtype=torch.int32, device=self.dev)
+        if out.get("cigar") is None:
+            out["cigar"] = torch.empty((m, stride), dtype=torch.int32, device=self.dev)
+        if "status" not in out:
+            out["status"] = torch.empty(m, dtype=torch.uint8, device=self.dev)
+        _lib.check(self.lib.gdx_soft_clip_many_dev(
+            self.h, m, int(max_edits), match, mismatch, gap_open, gap_extend, min_score, _ptr(aligned["dist"]), _ptr(aligned["begin"]),
+            _ptr(aligned["end"]), _ptr(aligned["n_cigar"]), _ptr(aligned["cigar"]), _ptr(out["score"]), _ptr(out["dist"]),
+            _ptr(out["begin"]), _ptr(out["end"]), _ptr(out["clip_left"]), _ptr(out["clip_right"]), _ptr(out["n_cigar"]),
+            _ptr(out["cigar"]), _ptr(out["status"]) if out["status"] is not None else None, _stream()))
+        return out
+
+    def _clipped(self, result: dict, aligned: dict, max_edits: int, clip) -> dict:
+        """map_reads / map_pairs with clip given: the clipped alignment in the place of the traced one"""
+        c = self.soft_clip(aligned, max_edits, clip)
+        # (where nothing was aligned the stage's own dist stays; elsewhere the edits that are left, k + 1 for a read clipped away)
+        dist = torch.where(aligned["end"] == -1, result["dist"][:c["dist"].numel()], c["dist"])
+        return {**result, "edit_dist": result["dist"], "dist": dist, "begin": c["begin"], "end": c["end"], "n_cigar": c["n_cigar"],
+                "cigar": c["cigar"], "score": c["score"], "clip_left": c["clip_left"], "clip_right": c["clip_right"]}
+
     # ---- best hit per read (gdx_best_hits_many_dev) -----------------------------------------------------------
     def alloc_best_hits(self, n_groups: int):
         return self._alloc_u32((n_groups, ("best_slot", "best_dist", "sub_dist", "n_live", "n_best", "mapq", "win_query", "win_begin")),
@@ -594,7 +633,7 @@ class DeviceEngine:
         return out
 
     def map_reads(self, q: DeviceQueries, reversed_index, *, max_smems: int, min_length: int, max_occ: int, band: int,
-                  max_candidates: int, max_edits: int, both_strands: bool = True) -> dict:
+                  max_candidates: int, max_edits: int, both_strands: bool = True, clip=None) -> dict:
         """The seed-and-verify chain on resident reads, every stage reading what the one before left in HBM: with_strands ->
         smems -> seed_candidates -> edit_distance -> best_hits -> align over the winners, one slot per read.  q: a plain batch;
         reversed_index as in smems().
@@ -602,7 +641,11 @@ class DeviceEngine:
         "begin", "end" (the alignment's text range), "dist", "sub_dist", "n_best", "mapq", "n_cigar" and "cigar" (int32[reads,
         2 max_edits + 1]).  An unmapped read has mapq 255 (GDX_BEST_MAPQ_NONE), n_best 0, n_cigar 0, begin and end -1, dist and
         sub_dist max_edits + 1; its strand and text_id say nothing.  The align workspace is sized for one candidate per read.
-        No result crosses to the host in between (with_strands reads the batch's symbol count once to size its output)."""
+        No result crosses to the host in between (with_strands reads the batch's symbol count once to size its output).
+        clip = (match, mismatch, gap_open, gap_extend, min_score) puts soft_clip() behind align: "begin", "end", "n_cigar", "cigar"
+        and "dist" are then the clipped ones, and "score", "clip_left", "clip_right" and "edit_dist" (what "dist" is without
+        clip) are added.  A read that is clipped away looks like an unmapped one (end -1, n_cigar 0, dist max_edits + 1), and
+        sam_records() writes it as unmapped.  A caller who expects junk tails raises max_edits."""
         n_reads = q.nq
         sq = q.with_strands(self.index, "both") if both_strands else q
         nq, mc = sq.nq, int(max_candidates)
@@ -613,9 +656,10 @@ class DeviceEngine:
         best = self.best_hits(cands, dist, end, n_reads, mc * (2 if both_strands else 1), max_edits)
         aligned = self.align(sq, best["win_query"][:n_reads], best["win_begin"][:n_reads], best["win_hits"][:n_reads], max_edits)
         strand = best["win_query"] & 1 if both_strands else torch.zeros_like(best["win_query"])  # (win_query = 2 read + strand)
-        return {"strand": strand, "text_id": best["win_hits"][:, 0], "begin": aligned["begin"], "end": aligned["end"],
-                "dist": best["best_dist"], "sub_dist": best["sub_dist"], "n_best": best["n_best"], "mapq": best["mapq"],
-                "n_cigar": aligned["n_cigar"], "cigar": aligned["cigar"]}
+        result = {"strand": strand, "text_id": best["win_hits"][:, 0], "begin": aligned["begin"], "end": aligned["end"],
+                  "dist": best["best_dist"], "sub_dist": best["sub_dist"], "n_best": best["n_best"], "mapq": best["mapq"],
+                  "n_cigar": aligned["n_cigar"], "cigar": aligned["cigar"]}
+        return result if clip is None else self._clipped(result, aligned, max_edits, clip)
 
     # ---- paired-end pairing (gdx_pair_hits_many_dev) -----------------------------------------------------------
     def alloc_pair_hits(self, n_pairs: int):
@@ -780,7 +824,7 @@ class DeviceEngine:
         return out[:capacity], rec_off, status[:n]
 
     def map_pairs(self, q: DeviceQueries, reversed_index, *, max_smems: int, min_length: int, max_occ: int, band: int,
-                  max_candidates: int, max_edits: int, min_insert: int, max_insert: int, rescue: bool = False) -> dict:
+                  max_candidates: int, max_edits: int, min_insert: int, max_insert: int, rescue: bool = False, clip=None) -> dict:
         """map_reads for paired reads.  q: a plain batch with the mates interleaved, reads 2p and 2p + 1 being the mates of pair p
         (an odd q.nq raises ValueError).  with_strands("both") -> smems -> seed_candidates -> edit_distance -> pair_hits ->
         best_hits per mate (for the single-end figures) -> align over the 2 * n_pairs winners of pair_hits.
@@ -791,7 +835,9 @@ class DeviceEngine:
         mate has n_cigar 0, begin and end -1 and dist max_edits + 1.  No result crosses to the host in between.
         rescue=True puts mate_rescue() between pair_hits and align, which then runs over the merged winners, and adds the per-mate
         "rescued" (1 for a mate placed from its partner, else 0) and the per-pair "resc_mate", "resc_pair_dist", "resc_span"; for
-        a rescued mate "strand" and "text_id" are the rescue candidate's and "dist" is align's own distance."""
+        a rescued mate "strand" and "text_id" are the rescue candidate's and "dist" is align's own distance.
+        clip as in map_reads: the per-mate "begin", "end", "n_cigar", "cigar" and "dist" are the clipped ones and the per-mate
+        "score", "clip_left", "clip_right" and "edit_dist" are added; the pairing itself is not done again."""
         if q.nq % 2:
             raise ValueError("map_pairs takes the mates interleaved: an even number of reads")
         n_mates, n_pairs, mc = q.nq, q.nq // 2, int(max_candidates)
@@ -818,6 +864,8 @@ class DeviceEngine:
             per_mate["rescued"] = rescued
             per_mate["dist"] = torch.where(rescued != 0, aligned["dist"], dist_of)
             per_pair.update({name: win[name] for name in ("resc_mate", "resc_pair_dist", "resc_span")})
+        if clip is not None:
+            per_mate = self._clipped(per_mate, aligned, max_edits, clip)
         # (the buffers hold at least one entry: an empty batch gets empty tensors, not that unwritten row)
         return {**{name: t[:n_mates] for name, t in per_mate.items()}, **{name: t[:n_pairs] for name, t in per_pair.items()}}
 

@@ -829,6 +829,34 @@ class FmIndex:
                 else Alignment(int(d), int(b), int(e), cigar_string(row[:n]))
                 for d, b, e, n, row in zip(dist, begin, end, n_cigar, cigar)]
 
+    # ---- soft clipping (gdx_experimental.h "soft clipping") -------------------------------------------------
+    def soft_clip_raw(self, dist, begin, end, n_cigar, cigar, max_edits, match, mismatch, gap_open, gap_extend, min_score=0):
+        """gdx_soft_clip_many -> (score: int32[m]; dist, begin, end, clip_left, clip_right, n_cigar: uint32[m]; cigar: uint32[m,
+        2 max_edits + 1]; status: uint8[m]): per candidate of align_raw the best-scoring contiguous part of its runs under the
+        scoring, S runs (op GDX_CIGAR_SOFT_CLIP) in place of what lies outside, begin and end moved inwards, dist the edits that
+        stay.  A candidate without an alignment passes through with score GDX_CLIP_NO_SCORE; one whose best score is below
+        max(1, min_score) is clipped away (end GDX_EDIT_NO_END, n_cigar 0, dist max_edits + 1, score the best score); one whose
+        runs fail the check gets status GDX_CLIP_BAD_CIGAR.  The words of a cigar row from n_cigar on are zero."""
+        dist, begin, end, n_cigar = (np.ascontiguousarray(x, dtype=np.uint32) for x in (dist, begin, end, n_cigar))
+        m = int(dist.size)
+        # (a limit over GDX_EDIT_MAX_QUERY_LEN is refused by the call before it reads or writes anything)
+        stride = 2 * min(int(max_edits), _lib.GDX_EDIT_MAX_QUERY_LEN) + 1
+        cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+        if any(x.size != m for x in (begin, end, n_cigar)) or (int(max_edits) <= _lib.GDX_EDIT_MAX_QUERY_LEN and cigar.size != m * stride):
+            raise ValueError("dist, begin, end and n_cigar hold m entries, cigar m rows of 2 max_edits + 1 words")
+        if cigar.size == 0:
+            cigar = np.zeros(1, dtype=np.uint32)  # (never a null pointer)
+        score = np.zeros(max(m, 1), dtype=np.int32)
+        outs = [np.zeros(max(m, 1), dtype=np.uint32) for _ in range(6)]
+        out_cigar = np.zeros((max(m, 1), stride), dtype=np.uint32)
+        status = np.zeros(max(m, 1), dtype=np.uint8)
+        pad = lambda x: x if x.size else np.zeros(1, dtype=np.uint32)  # noqa: E731
+        _lib.check(self._lib.gdx_soft_clip_many(self._h, m, int(max_edits), int(match), int(mismatch), int(gap_open), int(gap_extend),
+                                                int(min_score), _p(pad(dist), u32p), _p(pad(begin), u32p), _p(pad(end), u32p),
+                                                _p(pad(n_cigar), u32p), _p(cigar, u32p), score.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                *(_p(o, u32p) for o in outs), _p(out_cigar, u32p), _p(status, _lib.u8p)))
+        return (score[:m],) + tuple(o[:m] for o in outs) + (out_cigar[:m], status[:m])
+
     # ---- SAM records (gdx_experimental.h "SAM records") ----------------------------------------------------
     def sam_records_raw(self, qbuf, qoff, win_query, win_text_ids, dist, begin, end, n_cigar, cigar, mapq, *, strands=1,
                         mode=_lib.GDX_SAM_SINGLE, max_edits, proper=None, names=None, name_off=None, text_names=None,

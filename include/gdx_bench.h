@@ -60,6 +60,10 @@ int gdx_debug_set_rescue_tiling(uint64_t tile_pairs, uint64_t grid);
  * records do not depend on either: a small tile sends ordinary records down the path of a record larger than a tile. */
 int gdx_debug_set_sam_tiling(uint32_t tile_bytes, uint32_t grid);
 
+/* grid of gdx_soft_clip_many[_dev] (gdx_experimental.h): at most this many workgroups in the launches to come, 0 = the launcher's own
+ * choice (at most 4096).  The results do not depend on it: tests run one batch through grids 1, 2, 3 and the default. */
+int gdx_debug_set_clip_grid(uint32_t grid);
+
 /* streaming copy of `bytes` (multiple of 16): the "measured HBM bandwidth" denominator */
 int gdx_bench_stream_copy(void *d_dst, const void *d_src, uint64_t bytes, void *stream);
 /* streaming read of `bytes` (multiple of 16) */

@@ -486,8 +486,8 @@ int gdx_mate_rescue_many(const gdx_index_t *ix, const uint8_t *qbuf, const uint6
  * mode or layout; max_edits > 256; a null required pointer (rec_off, and with n_reads != 0 qbuf, the nine per-read arrays and qoff
  * unless uniform); names without their offsets or the reverse.  GDX_ERR_UNSUPPORTED: a packed layout, an index without text units,
  * a handle of the 64-bit engine.  A refused call writes nothing.  n_reads == 0 is GDX_OK and writes rec_off[0] = 0.
- * Out of scope: base qualities, BAM, secondary and supplementary records, soft clipping, placing an unmapped mate at its partner's
- * position, gdx_parts_t and gdx_multi_t. */
+ * Out of scope: base qualities, BAM, secondary and supplementary records, placing an unmapped mate at its partner's position,
+ * gdx_parts_t and gdx_multi_t.  Soft clipping is a stage of its own before this one, gdx_soft_clip_many below. */
 #define GDX_SAM_SINGLE      0u
 #define GDX_SAM_PAIRED      1u
 #define GDX_SAM_BAD_RECORD  1            /* status: a winner that cannot be a record; written as unmapped        */
@@ -513,6 +513,68 @@ uint64_t gdx_sam_workspace_bytes(uint64_t n_reads);
 uint64_t gdx_sam_record_bound(uint64_t max_read_len, uint64_t max_name_len, uint64_t max_text_name_len, uint32_t max_edits);
 int gdx_sam_records_many_dev(const gdx_index_t *ix, const gdx_sam_inputs_t *in, void *stream);
 int gdx_sam_records_many(const gdx_index_t *ix, const gdx_sam_inputs_t *in);
+
+/* ---- soft clipping (the scored post-pass between gdx_align_many and gdx_sam_records_many) ----------------------------------
+ * The alignments of gdx_align_many are end-to-end in the read: a read with a few bad cycles or an adapter tail, or one that hangs
+ * over the end of a text, comes out with a string of X and I operations over symbols that align to nothing.  gdx_soft_clip_many
+ * finds, per candidate, the best-scoring contiguous part of the traced alignment under a match / mismatch / gap-open / gap-extend
+ * scoring, replaces what lies outside it by S runs, moves begin and end inwards, recomputes the edit count (NM) and returns the
+ * score (AS).  The clipped dist, begin, end, n_cigar and cigar go into gdx_sam_records_many in place of the traceback's: it prints
+ * op 4 as S, formats SEQ whole and skips S in MD.  The call never looks at the queries or at the index's arrays.
+ * A read still has to pass the verify limit to reach the traceback at all: a caller who expects junk tails raises max_edits.  The
+ * bit-parallel verify does not get slower with it, and the traceback's workspace grows as gdx_align_many's formula says.
+ * Inputs: the five outputs of gdx_align_many[_dev] for m candidates as they are -- dist, begin, end, n_cigar (u32[m]) and cigar
+ * (u32[m * stride], stride = 2 k + 1, k = max_edits <= 256), candidate c having the runs w_1 .. w_n, n = n_cigar[c], each word
+ * len << 4 | op.  Scoring: match, mismatch, gap_extend in 1 .. GDX_CLIP_MAX_SCORE_PARAM, gap_open in 0 .. GDX_CLIP_MAX_SCORE_PARAM,
+ * min_score <= 2^30.
+ * Per candidate c:
+ *  1. Pass through.  end[c] == GDX_EDIT_NO_END: the candidate gets the NONE PATTERN -- out_begin = out_end = GDX_EDIT_NO_END,
+ *     out_n_cigar = 0, out_clip_left = out_clip_right = 0 -- with out_score = GDX_CLIP_NO_SCORE and out_dist = dist[c] as it came
+ *     (GDX_EDIT_INVALID, GDX_EDIT_TOO_LONG and k + 1 survive); status 0.
+ *  2. Check.  The candidate is bad unless n <= stride, every op is one of I (1), D (2), = (7), X (8), every len >= 1, the lens
+ *     sum to at most GDX_CLIP_MAX_RUN_SUM, begin <= end and end - begin equals the sum of the lens of the =, X and D runs.  A bad
+ *     candidate gets status GDX_CLIP_BAD_CIGAR and the none pattern with out_dist = k + 1 and out_score = GDX_CLIP_NO_SCORE (the
+ *     device form cannot report an argument error without synchronising).  No word at or beyond n, or beyond the stride, is read.
+ *  3. Score.  The value of a run: = is +match * len, X is -mismatch * len, I or D is -(gap_open + gap_extend * len).  Among all
+ *     run intervals [i, j], 1 <= i <= j <= n, the one with the greatest sum of values is taken; among equals the smallest i, then
+ *     the greatest j.  best = that sum; best = 0 for n == 0.  The parameter bounds make every run but = strictly negative, so a
+ *     positive optimum begins and ends with an = run, and cutting inside a run never helps: the definition works on runs.
+ *  4. Keep or drop.  The candidate is kept when best >= max(1, min_score).  Otherwise it is clipped away: the none pattern with
+ *     out_dist = k + 1 and out_score = best, which is informative and may be negative.  An empty read (n == 0 with a valid end)
+ *     has best = 0 and is therefore clipped away.
+ *  5. Kept.  out_score = best; out_begin = begin + the text symbols (=, X, D) of the runs before i; out_end = end - the text
+ *     symbols of the runs after j; out_clip_left / out_clip_right = the read symbols (=, X, I) of the runs before i / after j;
+ *     out_dist = the sum of the lens of the runs other than = in [i, j].  The output row holds clip_left << 4 | 4 if clip_left > 0,
+ *     then w_i .. w_j verbatim, then clip_right << 4 | 4 if clip_right > 0, and out_n_cigar is the number of those words; the
+ *     words of the row from there on are NOT written.  A removed side holds at least one run and adds at most one S, so
+ *     out_n_cigar <= n and the stride stays 2 k + 1; a removed side that holds only D runs adds no S.
+ * Scores fit i32: at most GDX_CLIP_MAX_RUN_SUM * 2 * GDX_CLIP_MAX_SCORE_PARAM in magnitude.  out_score is i32[m], the six other
+ * per-candidate outputs u32[m], out_cigar u32[m * stride], status u8[m] or NULL.  No output may overlap an input.
+ * Device form: ONE launch, no synchronisation, no allocation; returns GDX_OK.  Host form: the same arguments as host pointers
+ * without the stream, staged like gdx_best_hits_many (copy in, one launch, copy out).
+ * GDX_ERR_INVALID_ARGUMENT, nothing written: max_edits > 256; match, mismatch or gap_extend outside 1 .. 1024; gap_open > 1024;
+ * min_score > 2^30; a null required pointer (only the status may be null).  GDX_ERR_UNSUPPORTED: a handle of the 64-bit engine.
+ * m == 0 is GDX_OK and writes nothing.  gdx_parts_t and gdx_multi_t have no such call.
+ * Out of scope: re-aligning with affine gaps (the alignment stays the unit-cost one of gdx_align_many; only its ends are judged
+ * by the scoring), choosing the best hit by score, an AS tag in the SAM records (gdx_sam_inputs_t has no field for it), hard clips,
+ * supplementary records for the clipped part. */
+#define GDX_CIGAR_SOFT_CLIP      4u           /* 'S': read symbols outside the kept part                              */
+#define GDX_CLIP_NO_SCORE        0x80000000u  /* score of a candidate that had no alignment to clip                   */
+#define GDX_CLIP_BAD_CIGAR       1            /* status: the candidate fails the check of step 2                      */
+#define GDX_CLIP_MAX_RUN_SUM     65536u       /* the run lengths of one candidate sum to at most this                 */
+#define GDX_CLIP_MAX_SCORE_PARAM 1024u        /* match, mismatch, gap_open, gap_extend at most                        */
+int gdx_soft_clip_many_dev(const gdx_index_t *ix, uint64_t m, uint32_t max_edits, uint32_t match, uint32_t mismatch,
+                           uint32_t gap_open, uint32_t gap_extend, uint32_t min_score, const void *d_dist, const void *d_begin,
+                           const void *d_end, const void *d_n_cigar /*u32[m] each*/,
+                           const void *d_cigar /*u32[m * (2 max_edits + 1)]*/, void *d_out_score /*i32[m]*/, void *d_out_dist,
+                           void *d_out_begin, void *d_out_end, void *d_out_clip_left, void *d_out_clip_right,
+                           void *d_out_n_cigar /*u32[m] each*/, void *d_out_cigar /*u32[m * (2 max_edits + 1)]*/,
+                           void *d_out_status /*u8[m] or NULL*/, void *stream);
+int gdx_soft_clip_many(const gdx_index_t *ix, uint64_t m, uint32_t max_edits, uint32_t match, uint32_t mismatch, uint32_t gap_open,
+                       uint32_t gap_extend, uint32_t min_score, const uint32_t *dist, const uint32_t *begin, const uint32_t *end,
+                       const uint32_t *n_cigar, const uint32_t *cigar, int32_t *out_score, uint32_t *out_dist, uint32_t *out_begin,
+                       uint32_t *out_end, uint32_t *out_clip_left, uint32_t *out_clip_right, uint32_t *out_n_cigar,
+                       uint32_t *out_cigar, uint8_t *out_status /*or NULL*/);
 
 #ifdef __cplusplus
 }
